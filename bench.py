@@ -16,6 +16,13 @@ keypoints + descriptors to rank 0 that BASELINE config 3 describes.  Default is 
 `--dry --backend gloo` runs the same launcher / rendezvous / sharding / gather / timing plumbing on CPU tensors without
 the engine (CI without a GPU: tests/test_bench_launcher.py).
 
+A plain run sets up, warms up, times `--steps` steps and prints the line.  `--full` adds everything else the line can
+carry, each measured after the timed region: the CPU baseline (`cpu_baseline`), the PCIe-fed rates (`config.pcie_fed`),
+BASELINE configs 1 / 4 / 5 with the dense regimes (`config.other_configs`) and the box's streaming ceiling
+(`config.box_streaming_ceiling_GBps`); `--no-cpu-baseline`, `--no-host-fed` and `--no-other-configs` leave parts of it out.
+`--dump-outputs DIR` writes what rank 0's last timed chunk computed (the described keypoints and descriptors a caller of
+the batch path receives) as float32 / float64 .npy files: see dump_outputs().
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -261,8 +268,13 @@ def parse_args(argv):
     ap.add_argument("--streams", type=int, default=1, help="internal stream slices per chunk (1..8)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo with --dry)")
     ap.add_argument("--dry", action="store_true", help="no engine, no GPU: launcher / sharding / gather / timing plumbing only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-fed", action="store_true", help="skip the PCIe-fed (host frames) measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the CPU baseline, the PCIe-fed rates, the other BASELINE configs and "
+                         "dense regimes, and the box's streaming ceiling (a plain run measures the bench line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the keypoints + descriptors of rank 0's last timed chunk into DIR as .npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-host-fed", action="store_true", help="with --full: skip the PCIe-fed (host frames) measurement")
     ap.add_argument("--force-gather", action="store_true", help="run the RCCL result gather even with one rank (self-test)")
     ap.add_argument("--gather", default="torch", choices=["torch", "capi"],
                     help="result gather of the N-GPU batch path: torch.distributed (RCCL through torch) or the engine's own "
@@ -274,12 +286,15 @@ def parse_args(argv):
                          "density: 24 bits on this sparse stream); reported in config.integral_format_bits")
     ap.add_argument("--min-region-s", type=float, default=2.0,
                     help="--frames mode: the step is repeated until the timed region is at least this long")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip BASELINE configs 1 / 4 / 5 and the dense regimes (config.other_configs)")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip BASELINE configs 1 / 4 / 5 and the dense regimes (config.other_configs)")
     ap.add_argument("--config", default="", help="profiling: run ONLY this entry of config.other_configs (1, 4, 4_uniform, 5, dense30, dense50, threads, multi_image) "
                                                  "for --config-seconds and print its object")
     ap.add_argument("--config-seconds", type=float, default=0.5)
     ap.add_argument("--fail-rank", type=int, default=-1, help="launcher self-test: this rank exits with code 7 at start-up")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.dump_outputs and (args.dry or args.config):
+        ap.error("--dump-outputs needs the timed engine run (not --dry or --config)")
+    return args
 
 
 def main():
@@ -305,7 +320,7 @@ def main():
 
     # the CPU baseline workers are forked before torch / HIP exist in this process (rank 0, N=1 only)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.dry and not args.config:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not args.dry and not args.config:
         cpu = CpuBaseline()
 
     import numpy as np
@@ -469,6 +484,8 @@ def main():
     stage_ms, ncalls = ctx.profile_read()
     fpl = ctx.profile_frames_per_launch() or chunk   # frames per timed kernel launch (one stream slice)
     ctx.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, chunk, strings, args.dump_outputs)   # (before anything else reuses the engine's result buffers)
 
     # per-rank throughput (own frames / own time) and what the result gather costs when nothing hides it
     nsteps = args.steps * reps
@@ -553,15 +570,16 @@ def main():
                              + "every kernel group: config.kernel_groups"},
     }
     if rank == 0:
-        try:
-            cp, rd = ctx.stream_ceiling(1 << 30)
-            out["config"]["box_streaming_ceiling_GBps"] = {"float4_copy_read_plus_write": round(cp, 1),
-                                                           "float4_read_only": round(rd, 1)}
-        except Exception as e:  # reported, never fatal for the measurement
-            out["config"]["box_streaming_ceiling_GBps"] = "failed: %r" % (e,)
-        if world == 1 and not args.no_host_fed and hasattr(ctx, "detect_describe_batch_host"):
+        if args.full:
+            try:
+                cp, rd = ctx.stream_ceiling(1 << 30)
+                out["config"]["box_streaming_ceiling_GBps"] = {"float4_copy_read_plus_write": round(cp, 1),
+                                                               "float4_read_only": round(rd, 1)}
+            except Exception as e:  # reported, never fatal for the measurement
+                out["config"]["box_streaming_ceiling_GBps"] = "failed: %r" % (e,)
+        if world == 1 and args.full and not args.no_host_fed and hasattr(ctx, "detect_describe_batch_host"):
             out["config"]["pcie_fed"] = host_fed(ctx, ext, host, chunk, strings)
-        if world == 1 and not args.no_other_configs:
+        if world == 1 and args.full and not args.no_other_configs:
             try:
                 out["config"]["other_configs"] = other_configs(local_rank)
             except Exception as e:  # reported, never fatal for the bench line
@@ -575,6 +593,46 @@ def main():
         gather.close()   # (the C-ABI communicator: brisk_hip_comm_destroy)
     if use_dist:
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE_FRAMES = 64
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(ctx, chunk, strings, out_dir):
+    """--dump-outputs: what the batch path hands its caller after the last timed chunk (every chunk of a step runs the
+    same frames), through the per-frame download a caller uses (ctx.batch_download).  Files in out_dir:
+      counts.npy       float64 [chunk]           described keypoints of every frame of the chunk
+      frames.npy       float64 [S]               the sampled frames: min(chunk, 64) drawn with a fixed seed, ascending
+      keypoints.npy    float32 [M, 7]            x, y, size, angle, response, octave, class_id of the sampled frames'
+                                                 keypoints, frame after frame (counts[frames] rows each)
+      descriptors.npy  float32 [M, strings]      their descriptor bytes (0..255)
+    A sampled frame whose rows would take keypoints + descriptors past 64 MB ends the sample there."""
+    import numpy as np
+    import ethzasl_brisk_amd as B
+    os.makedirs(out_dir, exist_ok=True)
+    fields = B.KEYPOINT.names
+    rng = np.random.default_rng(20261016)
+    sample = set(rng.choice(chunk, min(chunk, DUMP_SAMPLE_FRAMES), replace=False).tolist())
+    counts = np.zeros(chunk, np.float64)
+    kept, kps, descs, nbytes, cut = [], [], [], 0, False
+    for f in range(chunk):
+        k, d = ctx.batch_download(f, True, strings)
+        counts[f] = len(k)
+        if cut or f not in sample:
+            continue
+        rows = len(k) * (len(fields) + strings) * 4
+        if nbytes + rows > DUMP_MAX_BYTES:
+            cut = True
+            continue
+        nbytes += rows
+        kept.append(f)
+        kps.append(np.stack([k[n].astype(np.float32) for n in fields], 1).reshape(len(k), len(fields)))
+        descs.append(d.astype(np.float32).reshape(len(k), strings))
+    np.save(os.path.join(out_dir, "counts.npy"), counts)
+    np.save(os.path.join(out_dir, "frames.npy"), np.array(kept, np.float64))
+    np.save(os.path.join(out_dir, "keypoints.npy"), np.concatenate(kps) if kps else np.zeros((0, len(fields)), np.float32))
+    np.save(os.path.join(out_dir, "descriptors.npy"), np.concatenate(descs) if descs else np.zeros((0, strings), np.float32))
 
 
 def _timed_calls(fn, sync, seconds, min_reps=3):

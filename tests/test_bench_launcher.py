@@ -72,3 +72,41 @@ def test_frames_mode_repeats_the_step_until_the_region_is_long_enough():
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     d = json.loads(r.stdout.decode().strip().splitlines()[-1])
     assert d["config"]["timed_region_s"] >= 0.45 and d["config"]["steps_effective"] >= 2 and d["config"]["steps_effective"] % 2 == 0
+
+
+def test_dump_outputs_writes_a_fixed_float_sample(tmp_path):
+    """--dump-outputs: every frame's count, a seeded sample of frames with their keypoint rows and descriptor bytes, all
+    float32 / float64 .npy, the same files from the same results (here a stand-in for the engine's per-frame download)."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    import ethzasl_brisk_amd as B
+
+    class Results:
+        def batch_download(self, f, described, strings):
+            n = (f * 37) % 50
+            k = np.zeros(n, B.KEYPOINT)
+            k["x"], k["y"], k["octave"] = np.arange(n) + f, f, f % 4
+            return k, (np.arange(n * strings).reshape(n, strings) + f).astype(np.uint8)
+
+    for d in ("a", "b"):
+        bench.dump_outputs(Results(), 300, 48, str(tmp_path / d))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["counts.npy", "descriptors.npy", "frames.npy", "keypoints.npy"]
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    counts, frames = np.load(tmp_path / "a" / "counts.npy"), np.load(tmp_path / "a" / "frames.npy").astype(int)
+    kp, desc = np.load(tmp_path / "a" / "keypoints.npy"), np.load(tmp_path / "a" / "descriptors.npy")
+    assert np.array_equal(counts, [(f * 37) % 50 for f in range(300)])
+    assert len(frames) == bench.DUMP_SAMPLE_FRAMES and np.all(np.diff(frames) > 0)
+    assert kp.shape == (counts[frames].sum(), 7) and desc.shape == (len(kp), 48)
+    f = frames[0]
+    n = int(counts[f])
+    assert np.array_equal(kp[:n, 0], np.arange(n) + f) and np.all(kp[:n, 5] == f % 4)
+    assert np.array_equal(desc[:n], (np.arange(n * 48).reshape(n, 48) + f).astype(np.uint8))
+
+
+def test_dump_outputs_needs_the_engine_run():
+    r = _run(["--gpus", "1", "--dry", "--dump-outputs", "unused"])
+    assert r.returncode == 2 and b"--dump-outputs" in r.stderr

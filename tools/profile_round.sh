@@ -8,14 +8,15 @@
 #   pmc_fetch_b64.csv / pmc_write_b64.csv   separate PMC passes (FETCH_SIZE, WRITE_SIZE) of a 64-frame run, engine kernels only
 #   traffic.json             tools/pmc_traffic.py on those two passes (per kernel and per group, tagged with the kernel revision)
 #   sq_counters.txt          SQ occupancy / stall / instruction counters per kernel (tools/pmc_sq.sh)
-#   bench.json               the bench line of an un-profiled default run
+#   bench.json               the bench line of an un-profiled bench.py --full run
 tag=$1; shift
+repo=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 configs=""
 while [ $# -gt 0 ]; do case $1 in --config) configs="$configs $2"; shift 2;; *) shift;; esac; done
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-python3 $GRAFT_REPO_ROOT/bench.py > $out/bench.json 2> $out/bench.err
+python3 "$repo/bench.py" --full > $out/bench.json 2> $out/bench.err
 # the default command (512 frames per launch: what the bench line is quoted on) ...
 timeout 300 rocprofv3 --kernel-trace --stats -d $out/ks5 -o r --output-format csv -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-host-fed --no-other-configs --steps 2 --warmup 1 --inner 4 > $out/ks5.log 2>&1
 cp $(find $out/ks5 -name "*kernel_stats.csv" | head -1) $out/kernel_stats_b512.csv

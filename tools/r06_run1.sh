@@ -7,7 +7,7 @@ timeout 900 python -m pytest tests/test_gpu_round6.py -x -q -m gpu > $out/pytest
 tail -5 $out/pytest_round6.log | tee -a $out/summary.txt
 for n in 1 2 4 8 16; do timeout 120 tests/cpp/test_threads --time $n 2 | tee -a $out/threads_default.jsonl; done
 for b in 1 2 4; do for n in 1 4 16; do echo "bands $b" >> $out/threads_bands.jsonl; BRISK_TR_BANDS=$b timeout 120 tests/cpp/test_threads --time $n 2 | tee -a $out/threads_bands.jsonl; done; done
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc=$?" | tee -a $out/summary.txt
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc=$?" | tee -a $out/summary.txt
 python tools/show_bench.py $out/bench.json 2>/dev/null | head -40
 python - <<PY
 import json
