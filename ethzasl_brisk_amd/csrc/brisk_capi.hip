@@ -22,6 +22,7 @@
 #include "brisk_kernels.h"
 #include "brisk_pattern.h"
 #include "brisk_device_describe.h"
+#include "brisk_hostmem.h"
 
 static_assert(sizeof(brisk_hip_keypoint) == 28 && sizeof(BriskKeyPoint) == 28, "cv::KeyPoint layout");
 
@@ -44,12 +45,13 @@ struct brisk_hip_ctx {
   int slots = 0;
   long pyr_elems_alloc = 0;
   long iframe_elems_alloc = 0;
-  BriskDetectBuffers B{};
+  BriskDetectBuffers B{};  // (the kernels take these two by value: raw pointers, set by ensure_buffers from the owners in ws)
   BriskDescribeBuffers D{};
-  uint8_t* d_stage = nullptr;  // staging for host-buffer calls (image + mask)
-  size_t stage_bytes = 0;
-  BriskKeyPoint* d_kp_in = nullptr;  // host-provided keypoints (describe-only)
-  int* d_n_in = nullptr;
+  struct {  // owners of the arrays of B / D, named after them: allocated and freed together (ensure_buffers / free_buffers)
+    DeviceBuf pyr, smap, cand, blocks, tie_idx, keys, counters, kp_out, integral, bandsum, dkp, dscale, dperm, drec, dp_work, desc;
+  } ws;
+  DeviceBuf d_kp_in, d_n_in;  // host-provided keypoints (describe-only) and their counts; allocated and freed with ws
+  DeviceBuf d_stage;  // staging for host-buffer calls (image + mask)
   // last geometry
   BriskGeom G{};
   BriskTileTable T{};
@@ -80,25 +82,19 @@ struct brisk_hip_ctx {
   int uni_max = 0x7FFFFFFF;
   // the other post-filter of the reference (KeyPointBucketing; used when uniformity enforcement is off): 0 buckets = off
   int bk_u = 0, bk_v = 0, bk_max = 0;
-  uint8_t* d_occ = nullptr;
-  size_t occ_bytes = 0;
-  BriskKeyPoint* d_uni_tmp = nullptr;
-  int* d_uni_order = nullptr;
-  size_t uni_items = 0;
+  DeviceBuf d_occ, d_uni_tmp, d_uni_order;  // scratch of the post-filters (ensure_filter_buffers)
   // candidate density of the last detect + describe batch (k_batch_density writes it into pinned host memory; read without
   // synchronisation by the next batch: integral_format)
-  long long* h_density = nullptr;
+  PinnedBuf h_density;
   int integral_fmt = 0;  // brisk_hip_set_integral_format: 0 auto, 24, 32
   // results of a one-frame host-buffer call land here (pinned) behind the kernels: one wait per call (download_single)
-  uint8_t* h_res = nullptr;
-  int* d_pub_done = nullptr;  // k_publish_single: workgroups that have written their share
+  PinnedBuf h_res;
+  DeviceBuf d_pub_done;  // k_publish_single: workgroups that have written their share
   unsigned pub_seq = 0;       // sequence word of the last call (the host polls for it)
   int spec_nkp = 1024;        // keypoints the next detect call is expected to return (sizes the publishing kernel's grid)
   double density_mpx = 0.0;  // megapixels per frame of the batch the word belongs to
-  void* d_img16[3] = {nullptr, nullptr, nullptr};  // scratch of the 16-bit image functions (source, destination, row sums): grown, never shrunk
-  size_t img16_bytes[3] = {0, 0, 0};
-  void* d_match = nullptr;  // workspace of brisk_hip_match_knn_device
-  size_t match_bytes = 0;
+  DeviceBuf d_img16[3];  // scratch of the 16-bit image functions (source, destination, row sums)
+  DeviceBuf d_match;     // workspace of brisk_hip_match_knn_device
   // Calls share one workspace but may be issued on different streams: every call that uses the workspace first makes
   // its stream wait for the end of the previous one (event recorded at the end of each call).
   hipEvent_t done_ev = nullptr;
@@ -107,18 +103,14 @@ struct brisk_hip_ctx {
   hipStream_t last_stream = nullptr;
   hipEvent_t block_ev = nullptr;  // blocking-sync event of the one-frame calls (download_single: when polling would starve other threads)
   // host-fed batches: two device staging buffers filled over a copy stream while the previous slice computes
-  uint8_t* d_hstage[2] = {nullptr, nullptr};
-  size_t hstage_bytes = 0;
-  uint8_t* d_imgs = nullptr;  // brisk_hip_detect_images / _describe_images: all frames of a call, resident until the next such call
-  size_t imgs_bytes = 0;
+  DeviceBuf d_hstage[2];
+  DeviceBuf d_imgs;  // brisk_hip_detect_images / _describe_images: all frames of a call, resident until the next such call
   // pageable images of the multi-image calls: copied into these pinned buffers by a few host threads (a pageable hipMemcpy is a
   // staging copy on the CALLING thread: 95 us per 2 MB image), then moved by one DMA per slice
-  uint8_t* h_pin[2] = {nullptr, nullptr};
-  size_t pin_bytes = 0;
+  PinnedBuf h_pin[2];
   hipEvent_t pin_ev[2] = {nullptr, nullptr};
   bool pin_used[2] = {false, false};
-  uint8_t* h_kin_pin = nullptr;  // brisk_hip_describe_images: the provided keypoint lists, packed (pinned)
-  size_t kin_pin_bytes = 0;
+  PinnedBuf h_kin_pin;  // brisk_hip_describe_images: the provided keypoint lists, packed
   hipEvent_t kin_pin_ev = nullptr;
   bool kin_pin_used = false;
   int image_reuse_multi = 0;  // describe_images calls that took the frames of the last multi-image call from the device
@@ -145,10 +137,8 @@ struct brisk_hip_ctx {
   } img_cache;
   // brisk_hip_batch_download_all: two slots of {device slab, pinned bounce buffer, events, the transfer in flight}
   struct ExportSlot {
-    void* slab = nullptr;
-    size_t slab_bytes = 0;
-    uint8_t* bounce = nullptr;  // pinned staging for destinations the device cannot write (pageable memory)
-    size_t bounce_bytes = 0;
+    DeviceBuf slab;
+    PinnedBuf bounce;  // staging for destinations the device cannot write (pageable memory)
     hipEvent_t packed = nullptr, done = nullptr;
     bool done_valid = false;  // `done` has been recorded: the slab is in use until it fires
     bool pending = false;     // the transfer has not been completed by a wait yet
@@ -314,12 +304,12 @@ static void make_geometry(int w, int h, int threshold, int octaves, BriskGeom* G
 }
 
 static void free_buffers(brisk_hip_ctx* c) {
-  hipFree(c->B.pyr); hipFree(c->B.smap); hipFree(c->B.cand); hipFree(c->B.blocks); hipFree(c->B.tie_idx); hipFree(c->B.keys);
-  hipFree(c->B.counters); hipFree(c->B.kp_out); hipFree(c->D.integral); hipFree(c->B.bandsum); hipFree(c->D.dkp); hipFree(c->D.dscale); hipFree(c->D.dperm); hipFree(c->D.drec); hipFree(c->D.dp_work);
-  hipFree(c->D.desc); hipFree(c->d_kp_in); hipFree(c->d_n_in);
+  auto& w = c->ws;
+  for (DeviceBuf* b : {&w.pyr, &w.smap, &w.cand, &w.blocks, &w.tie_idx, &w.keys, &w.counters, &w.kp_out, &w.integral, &w.bandsum, &w.dkp,
+                       &w.dscale, &w.dperm, &w.drec, &w.dp_work, &w.desc, &c->d_kp_in, &c->d_n_in})
+    b->reset();
   c->B = BriskDetectBuffers{};
   c->D = BriskDescribeBuffers{};
-  c->d_kp_in = nullptr; c->d_n_in = nullptr;
   c->slots = 0; c->pyr_elems_alloc = 0; c->iframe_elems_alloc = 0;
 }
 
@@ -342,26 +332,33 @@ static int ensure_buffers(brisk_hip_ctx* c, int nframes, const BriskGeom& G) {
   free_buffers(c);
   c->B.cand_cap = c->cand_cap; c->B.kp_cap = c->kp_cap; c->B.tie_cap = c->tie_cap;
   c->B.band_h = 96;  // band height of the detector's pyramid kernel (the descriptor-only call uses its own)
-  HIPCHK(c, hipMalloc(&c->B.pyr, (size_t)slots * pyr + 256));
-  HIPCHK(c, hipMalloc(&c->B.smap, ((size_t)slots * pyr + 256) * sizeof(uint16_t)));
-  HIPCHK(c, hipMalloc(&c->B.cand, (size_t)slots * c->cand_cap * sizeof(BriskCand)));
-  HIPCHK(c, hipMalloc(&c->B.blocks, (size_t)slots * c->cand_cap * 64));
-  HIPCHK(c, hipMalloc(&c->B.tie_idx, (size_t)slots * BRISK_MAX_LAYERS * c->tie_cap * sizeof(int)));
-  HIPCHK(c, hipMalloc(&c->B.keys, (size_t)slots * c->cand_cap * 2 * sizeof(unsigned)));
-  HIPCHK(c, hipMalloc(&c->B.counters, (size_t)slots * sizeof(BriskFrameCounters)));
-  HIPCHK(c, hipMalloc(&c->B.kp_out, (size_t)slots * c->kp_cap * sizeof(BriskKeyPoint)));
-  HIPCHK(c, hipMalloc(&c->D.integral, (size_t)slots * ifr * sizeof(uint32_t)));
-  HIPCHK(c, hipMalloc(&c->B.bandsum, (size_t)slots * ((ifr / 64) + 4 * 8192 + 64) * sizeof(uint32_t)));
-  HIPCHK(c, hipMalloc(&c->D.dkp, (size_t)slots * c->kp_cap * sizeof(BriskKeyPoint)));
-  HIPCHK(c, hipMalloc(&c->D.dscale, (size_t)slots * c->kp_cap * sizeof(int)));
-  HIPCHK(c, hipMalloc(&c->D.dperm, (size_t)slots * c->kp_cap * sizeof(int)));
-  HIPCHK(c, hipMalloc(&c->D.drec, ((size_t)slots * c->kp_cap + 4) * sizeof(uint4)));
+  auto& w = c->ws;
+  HIPCHK(c, w.pyr.grow((size_t)slots * pyr + 256));
+  HIPCHK(c, w.smap.grow(((size_t)slots * pyr + 256) * sizeof(uint16_t)));
+  HIPCHK(c, w.cand.grow((size_t)slots * c->cand_cap * sizeof(BriskCand)));
+  HIPCHK(c, w.blocks.grow((size_t)slots * c->cand_cap * 64));
+  HIPCHK(c, w.tie_idx.grow((size_t)slots * BRISK_MAX_LAYERS * c->tie_cap * sizeof(int)));
+  HIPCHK(c, w.keys.grow((size_t)slots * c->cand_cap * 2 * sizeof(unsigned)));
+  HIPCHK(c, w.counters.grow((size_t)slots * sizeof(BriskFrameCounters)));
+  HIPCHK(c, w.kp_out.grow((size_t)slots * c->kp_cap * sizeof(BriskKeyPoint)));
+  HIPCHK(c, w.integral.grow((size_t)slots * ifr * sizeof(uint32_t)));
+  HIPCHK(c, w.bandsum.grow((size_t)slots * ((ifr / 64) + 4 * 8192 + 64) * sizeof(uint32_t)));
+  HIPCHK(c, w.dkp.grow((size_t)slots * c->kp_cap * sizeof(BriskKeyPoint)));
+  HIPCHK(c, w.dscale.grow((size_t)slots * c->kp_cap * sizeof(int)));
+  HIPCHK(c, w.dperm.grow((size_t)slots * c->kp_cap * sizeof(int)));
+  HIPCHK(c, w.drec.grow(((size_t)slots * c->kp_cap + 4) * sizeof(uint4)));
   c->D.dp_work_stride = brisk_dp_work_ints(c->kp_cap);
-  HIPCHK(c, hipMalloc(&c->D.dp_work, (size_t)slots * c->D.dp_work_stride * sizeof(int)));
+  HIPCHK(c, w.dp_work.grow((size_t)slots * c->D.dp_work_stride * sizeof(int)));
   c->D.desc_pitch = c->desc_pitch;
-  HIPCHK(c, hipMalloc(&c->D.desc, (size_t)slots * c->kp_cap * c->D.desc_pitch));
-  HIPCHK(c, hipMalloc(&c->d_kp_in, (size_t)slots * c->kp_cap * sizeof(BriskKeyPoint)));
-  HIPCHK(c, hipMalloc(&c->d_n_in, (size_t)slots * sizeof(int)));
+  HIPCHK(c, w.desc.grow((size_t)slots * c->kp_cap * c->D.desc_pitch));
+  HIPCHK(c, c->d_kp_in.grow((size_t)slots * c->kp_cap * sizeof(BriskKeyPoint)));
+  HIPCHK(c, c->d_n_in.grow((size_t)slots * sizeof(int)));
+  // all there: the pointers that B / D carry to the kernels
+  c->B.pyr = w.pyr.as<uint8_t>(); c->B.smap = w.smap.as<uint16_t>(); c->B.cand = w.cand.as<BriskCand>(); c->B.blocks = w.blocks.as<uint8_t>();
+  c->B.tie_idx = w.tie_idx.as<int>(); c->B.keys = w.keys.as<unsigned>(); c->B.counters = w.counters.as<BriskFrameCounters>();
+  c->B.kp_out = w.kp_out.as<BriskKeyPoint>(); c->B.bandsum = w.bandsum.as<uint32_t>();
+  c->D.integral = w.integral.as<uint32_t>(); c->D.dkp = w.dkp.as<BriskKeyPoint>(); c->D.dscale = w.dscale.as<int>(); c->D.dperm = w.dperm.as<int>();
+  c->D.drec = w.drec.as<uint4>(); c->D.dp_work = w.dp_work.as<int>(); c->D.desc = w.desc.as<uint8_t>();
   HIPCHK(c, hipMemset(c->B.pyr, 0, (size_t)slots * pyr + 256));
   // the score-state map is kept all-zero between batches: k_detect writes detections only, the next detect batch
   // first clears what the previous one left (k_smap_clear)
@@ -380,14 +377,10 @@ static int ensure_buffers(brisk_hip_ctx* c, int nframes, const BriskGeom& G) {
 }
 
 static int ensure_stage(brisk_hip_ctx* c, size_t bytes) {
-  if (bytes <= c->stage_bytes) return BRISK_HIP_OK;
+  if (bytes <= c->d_stage.cap) return BRISK_HIP_OK;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->img_cache.valid = false;
-  hipFree(c->d_stage);
-  c->d_stage = nullptr;
-  c->stage_bytes = 0;
-  HIPCHK(c, hipMalloc(&c->d_stage, bytes + 256));
-  c->stage_bytes = bytes;
+  HIPCHK(c, c->d_stage.grow(bytes, 256));
   return BRISK_HIP_OK;
 }
 
@@ -412,8 +405,8 @@ static void integral_format(const brisk_hip_ctx* ctx, const brisk_hip_pattern* p
   if (ctx->integral_fmt == BRISK_HIP_INTEGRAL_U24) { *ibits = 24; return; }
   if (!batch_with_detect) return;
   double density = 0.0;  // candidates per megapixel of the last batch (none yet: sparse is the common case)
-  if (ctx->h_density && ctx->density_mpx > 0.0) {
-    const long long wv = __atomic_load_n(ctx->h_density, __ATOMIC_RELAXED);
+  if (ctx->h_density.p && ctx->density_mpx > 0.0) {
+    const long long wv = __atomic_load_n(ctx->h_density.as<long long>(), __ATOMIC_RELAXED);
     const long long frames = wv >> 40, cands = wv & 0xFFFFFFFFFFll;
     if (frames > 0) density = (double)cands / ((double)frames * ctx->density_mpx);
   }
@@ -496,38 +489,21 @@ void brisk_hip_destroy(brisk_hip_ctx* c) {
   if (!c) return;
   hipSetDevice(c->device);
   hipDeviceSynchronize();
-  free_buffers(c);
-  hipFree(c->d_stage);
-  if (c->d_match) hipFree(c->d_match);
-  for (int i = 0; i < 3; ++i) if (c->d_img16[i]) hipFree(c->d_img16[i]);
-  if (c->h_density) hipHostFree(c->h_density);
-  if (c->h_res) hipHostFree(c->h_res);
-  if (c->d_pub_done) hipFree(c->d_pub_done);
+  // (the buffers go with the context, below: after the synchronisation, and after the streams - memory outlives its stream)
   if (c->done_ev) hipEventDestroy(c->done_ev);
   if (c->block_ev) hipEventDestroy(c->block_ev);
   for (int i = 0; i < 2; ++i) {
-    if (c->d_hstage[i]) hipFree(c->d_hstage[i]);
     if (c->copied_ev[i]) hipEventDestroy(c->copied_ev[i]);
     if (c->consumed_ev[i]) hipEventDestroy(c->consumed_ev[i]);
-  }
-  if (c->d_imgs) hipFree(c->d_imgs);
-  if (c->h_kin_pin) hipHostFree(c->h_kin_pin);
-  if (c->kin_pin_ev) hipEventDestroy(c->kin_pin_ev);
-  for (int i = 0; i < 2; ++i) {
-    if (c->h_pin[i]) hipHostFree(c->h_pin[i]);
     if (c->pin_ev[i]) hipEventDestroy(c->pin_ev[i]);
   }
+  if (c->kin_pin_ev) hipEventDestroy(c->kin_pin_ev);
   if (c->copy_stream) hipStreamDestroy(c->copy_stream);
   for (auto& E : c->ex) {
-    if (E.slab) hipFree(E.slab);
-    if (E.bounce) hipHostFree(E.bounce);
     if (E.packed) hipEventDestroy(E.packed);
     if (E.done) hipEventDestroy(E.done);
   }
   if (c->egress) hipStreamDestroy(c->egress);
-  if (c->d_occ) hipFree(c->d_occ);
-  if (c->d_uni_tmp) hipFree(c->d_uni_tmp);
-  if (c->d_uni_order) hipFree(c->d_uni_order);
   brisk_prof_destroy(&c->prof);
   if (c->side) { hipStreamDestroy(c->side); hipEventDestroy(c->side_fork); hipEventDestroy(c->side_join); }
   if (c->sub_created) {
@@ -701,22 +677,11 @@ static int ensure_filter_buffers(brisk_hip_ctx* ctx, int w, int h, int nframes, 
     need = (size_t)(((long)oh * ow + 255) / 256 * 256) * nframes + 64;
   }
   const size_t items = (size_t)ctx->slots * ctx->kp_cap;
-  if (need > ctx->occ_bytes || items > ctx->uni_items) {
+  if (need > ctx->d_occ.cap || items * sizeof(BriskKeyPoint) > ctx->d_uni_tmp.cap || items * sizeof(int) > ctx->d_uni_order.cap) {
     HIPCHK(ctx, hipDeviceSynchronize());
-    if (need > ctx->occ_bytes) {
-      if (ctx->d_occ) (void)hipFree(ctx->d_occ);
-      ctx->d_occ = nullptr; ctx->occ_bytes = 0;
-      HIPCHK(ctx, hipMalloc(&ctx->d_occ, need));
-      ctx->occ_bytes = need;
-    }
-    if (items > ctx->uni_items) {
-      if (ctx->d_uni_tmp) (void)hipFree(ctx->d_uni_tmp);
-      if (ctx->d_uni_order) (void)hipFree(ctx->d_uni_order);
-      ctx->d_uni_tmp = nullptr; ctx->d_uni_order = nullptr; ctx->uni_items = 0;
-      HIPCHK(ctx, hipMalloc(&ctx->d_uni_tmp, items * sizeof(BriskKeyPoint)));
-      HIPCHK(ctx, hipMalloc(&ctx->d_uni_order, items * sizeof(int)));
-      ctx->uni_items = items;
-    }
+    HIPCHK(ctx, ctx->d_occ.grow(need));
+    HIPCHK(ctx, ctx->d_uni_tmp.grow(items * sizeof(BriskKeyPoint)));
+    HIPCHK(ctx, ctx->d_uni_order.grow(items * sizeof(int)));
   }
   return BRISK_HIP_OK;
 }
@@ -814,17 +779,19 @@ static int batch_slice(brisk_hip_ctx* ctx, const BatchArgs& A, const uint8_t* d_
     brisk_launch_detect(Gs, ctx->T, Bi, nf, d_frames, A.frame_pitch, A.row_pitch,
                         A.d_mask ? A.d_mask + f0 * A.mask_frame_pitch : nullptr, A.mask_frame_pitch, A.mask_row_pitch, si, prof, ovp);
   }
+  int* const uni_order = ctx->d_uni_order.as<int>();
+  BriskKeyPoint* const uni_tmp = ctx->d_uni_tmp.as<BriskKeyPoint>();
   if (A.do_detect && A.uni_radius > 0.0) {
     // EnforceKeyPointUniformity as a post-filter of the detected keypoints (brisk_uniformity.hip)
     const float scaling = (float)(15.0 / (float)A.uni_radius);
     const int oh = (int)(A.h * ceil(scaling) + 32), ow = (int)(A.w * ceil(scaling) + 32);
     const long occ_frame = ((long)oh * ow + 255) / 256 * 256;
-    brisk_launch_uniformity(Bi.kp_out, Bi.counters, ctx->d_uni_order + f0 * Bi.kp_cap, ctx->d_uni_tmp + f0 * Bi.kp_cap,
-                            ctx->d_occ + f0 * occ_frame, occ_frame, ow, Bi.kp_cap, scaling, A.uni_max, nf, si);
+    brisk_launch_uniformity(Bi.kp_out, Bi.counters, uni_order + f0 * Bi.kp_cap, uni_tmp + f0 * Bi.kp_cap,
+                            ctx->d_occ.as<uint8_t>() + f0 * occ_frame, occ_frame, ow, Bi.kp_cap, scaling, A.uni_max, nf, si);
   }
   if (A.do_detect && !(A.uni_radius > 0.0) && A.bk_u > 0) {
     // KeyPointBucketing as a post-filter of the detected keypoints (brisk_uniformity.hip)
-    brisk_launch_bucketing(Bi.kp_out, Bi.counters, ctx->d_uni_order + f0 * Bi.kp_cap, ctx->d_uni_tmp + f0 * Bi.kp_cap, Bi.kp_cap,
+    brisk_launch_bucketing(Bi.kp_out, Bi.counters, uni_order + f0 * Bi.kp_cap, uni_tmp + f0 * Bi.kp_cap, Bi.kp_cap,
                            A.h, A.w, A.bk_u, A.bk_v, A.bk_max, nf, si);
   }
   if (A.do_detect) brisk_prof_mark(prof, BRISK_STG_INTEGRAL, si);  // end of the post-filter interval
@@ -837,12 +804,12 @@ static int batch_slice(brisk_hip_ctx* ctx, const BatchArgs& A, const uint8_t* d_
 
 static int batch_end(brisk_hip_ctx* ctx, const BatchArgs& A, int nframes, hipStream_t s) {
   if (A.do_detect && A.do_describe) {  // candidate density of this batch for the next one's choice of integral format
-    if (!ctx->h_density) {
-      HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_density, sizeof(long long), hipHostMallocMapped));
-      *ctx->h_density = 0;
+    if (!ctx->h_density.p) {
+      HIPCHK(ctx, ctx->h_density.grow(sizeof(long long), 0, hipHostMallocMapped));
+      *ctx->h_density.as<long long>() = 0;
     }
     ctx->density_mpx = (double)A.w * (double)A.h / 1e6;
-    brisk_launch_batch_density(ctx->B.counters, nframes, ctx->B.cand_cap, ctx->h_density, s);
+    brisk_launch_batch_density(ctx->B.counters, nframes, ctx->B.cand_cap, ctx->h_density.as<long long>(), s);
   }
   if (ctx->prof.on) ctx->prof.calls++;
   HIPCHK(ctx, hipGetLastError());
@@ -953,22 +920,19 @@ static int upload_frames(brisk_hip_ctx* ctx, uint8_t* d_dst, size_t dframe, int 
       HIPCHK(ctx, hipMemcpy2DAsync(d_dst + (size_t)f * dframe, dpitch, ptrs[f], stride, w, h, hipMemcpyHostToDevice, cs));
     return BRISK_HIP_OK;
   }
-  if (ctx->pin_bytes < dframe * BRISK_STAGED_SLICE) {
+  if (ctx->h_pin[0].cap < dframe * BRISK_STAGED_SLICE || ctx->h_pin[1].cap < dframe * BRISK_STAGED_SLICE) {
     for (int i = 0; i < 2; ++i) {
       if (ctx->pin_used[i]) HIPCHK(ctx, hipEventSynchronize(ctx->pin_ev[i]));
       ctx->pin_used[i] = false;
-      if (ctx->h_pin[i]) (void)hipHostFree(ctx->h_pin[i]);
-      ctx->h_pin[i] = nullptr;
+      ctx->h_pin[i].reset();
     }
-    ctx->pin_bytes = 0;
     for (int i = 0; i < 2; ++i) {
-      HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_pin[i], dframe * BRISK_STAGED_SLICE + 256, hipHostMallocDefault));
+      HIPCHK(ctx, ctx->h_pin[i].grow(dframe * BRISK_STAGED_SLICE, 256));
       if (!ctx->pin_ev[i]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->pin_ev[i], hipEventDisableTiming));
     }
-    ctx->pin_bytes = dframe * BRISK_STAGED_SLICE;
   }
   if (ctx->pin_used[b]) HIPCHK(ctx, hipEventSynchronize(ctx->pin_ev[b]));  // the DMA that last read this buffer (two slices ago)
-  uint8_t* const pin = ctx->h_pin[b];
+  uint8_t* const pin = ctx->h_pin[b].as<uint8_t>();
   // work items = quarter frames (row bands): a few threads stay busy to the end of the slice
   std::atomic<int> next{0};
   const int items = nf * 4;
@@ -1033,15 +997,10 @@ static int batch_host_locked(brisk_hip_ctx* ctx, const brisk_hip_pattern* pat, c
     }
     fresh = true;
   }
-  if (!d_resident && ctx->hstage_bytes < dframe * slice) {
+  if (!d_resident && (ctx->d_hstage[0].cap < dframe * slice || ctx->d_hstage[1].cap < dframe * slice)) {
     HIPCHK(ctx, hipDeviceSynchronize());
-    for (int i = 0; i < 2; ++i) {
-      if (ctx->d_hstage[i]) (void)hipFree(ctx->d_hstage[i]);
-      ctx->d_hstage[i] = nullptr;
-    }
-    ctx->hstage_bytes = 0;
-    for (int i = 0; i < 2; ++i) HIPCHK(ctx, hipMalloc(&ctx->d_hstage[i], dframe * slice + 256));
-    ctx->hstage_bytes = dframe * slice;
+    for (int i = 0; i < 2; ++i) ctx->d_hstage[i].reset();
+    for (int i = 0; i < 2; ++i) HIPCHK(ctx, ctx->d_hstage[i].grow(dframe * slice, 256));
     fresh = true;
   }
   A.frame_pitch = (long)dframe;
@@ -1057,7 +1016,7 @@ static int batch_host_locked(brisk_hip_ctx* ctx, const brisk_hip_pattern* pat, c
   for (long f0 = 0; f0 < nframes; f0 += slice, ++k) {
     const int nf = (int)((nframes - f0 < slice) ? nframes - f0 : slice);
     const int b = k & 1;
-    uint8_t* const dslice = d_resident ? d_resident + (size_t)f0 * dframe : ctx->d_hstage[b];
+    uint8_t* const dslice = d_resident ? d_resident + (size_t)f0 * dframe : ctx->d_hstage[b].as<uint8_t>();
     if (!d_resident) HIPCHK(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->consumed_ev[b], 0));
     else if (k == 0 && ctx->done_valid && !ensure_done_event(ctx)) HIPCHK(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->done_ev, 0));  // (the previous call may still read the resident frames)
     const uint8_t* src = frame_ptrs ? nullptr : h_frames + f0 * frame_pitch;
@@ -1231,11 +1190,11 @@ struct PollerScope {
 // the pinned block of the one-frame calls: [0] sequence word (device -> host), [16] the provided-keypoint count of a describe call
 // (host -> device: the kernels read it where it is - no copy, no runtime call), [64] counter record, then the rows
 static int ensure_single_buffer(brisk_hip_ctx* ctx) {
-  if (ctx->h_res) return BRISK_HIP_OK;
-  HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_res, BRISK_SINGLE_BYTES, hipHostMallocCoherent));
-  memset(ctx->h_res, 0, 64);
-  HIPCHK(ctx, hipMalloc((void**)&ctx->d_pub_done, 64));
-  HIPCHK(ctx, hipMemset(ctx->d_pub_done, 0, 64));
+  if (ctx->d_pub_done.p) return BRISK_HIP_OK;  // (the second of the two: both are there)
+  HIPCHK(ctx, ctx->h_res.grow(BRISK_SINGLE_BYTES, 0, hipHostMallocCoherent));
+  memset(ctx->h_res.p, 0, 64);
+  HIPCHK(ctx, ctx->d_pub_done.grow(64));
+  HIPCHK(ctx, hipMemset(ctx->d_pub_done.p, 0, 64));
   HIPCHK(ctx, hipDeviceSynchronize());
   return BRISK_HIP_OK;
 }
@@ -1243,6 +1202,7 @@ static int download_single(brisk_hip_ctx* ctx, int which, brisk_hip_keypoint* kp
                            int desc_stride, int strings, int dev_pitch, int expect) {
   const bool want_desc = desc && which;
   if (int rcb = ensure_single_buffer(ctx)) return rcb;
+  uint8_t* const h_res = ctx->h_res.as<uint8_t>();
   const unsigned o_cnt = 64, o_kp = (unsigned)((o_cnt + sizeof(BriskFrameCounters) + 255) & ~(size_t)255);
   const size_t row = sizeof(BriskKeyPoint) + (want_desc ? (size_t)dev_pitch : 0);
   // (debug bit 25: a 16 KB limit, so that tests reach the staged-copy path with a few hundred keypoints)
@@ -1255,14 +1215,14 @@ static int download_single(brisk_hip_ctx* ctx, int which, brisk_hip_keypoint* kp
   if (!ctx->pub_seq) ctx->pub_seq = 1;
   const unsigned seq = ctx->pub_seq;
   brisk_launch_publish_single(ctx->B.counters, which ? ctx->D.dkp : ctx->B.kp_out, want_desc ? ctx->D.desc : nullptr, which, (int)max_kp,
-                              dev_pitch, expect < max_kp ? expect : (int)max_kp, ctx->h_res, o_cnt, o_kp, o_desc, ctx->d_pub_done, seq, ctx->stream);
+                              dev_pitch, expect < max_kp ? expect : (int)max_kp, h_res, o_cnt, o_kp, o_desc, ctx->d_pub_done.as<int>(), seq, ctx->stream);
   HIPCHK(ctx, hipGetLastError());
   // The host polls the sequence word (a one-frame call lasts 0.1 ... 0.7 ms and the word arrives microseconds after the
   // last kernel; a blocking wait costs 12 us of wake-up) - but only for a bounded time: after 2 ms (a stream held up behind
   // foreign work, a 4K frame at a low threshold) the thread stops burning its core and sleeps in hipStreamSynchronize;
   // a kernel that failed never writes the word, which the synchronisation reports.  (Round-4 advisor finding: the poll had
   // no deadline.)
-  volatile unsigned* flag = reinterpret_cast<volatile unsigned*>(ctx->h_res);
+  volatile unsigned* flag = reinterpret_cast<volatile unsigned*>(h_res);
   unsigned v = 0;
   // Polling needs a core per waiting thread: with more callers than the process has CPUs (round 6: 32 threads on 16 CPUs fell from
   // 9 k to 4 k frames/s, every thread burning its time slice on the flag while the threads that had work waited for a core) the
@@ -1287,7 +1247,7 @@ static int download_single(brisk_hip_ctx* ctx, int which, brisk_hip_keypoint* kp
   }
   if (v & 0x80000000u) return download_locked(ctx, 0, which, kps, cap, n, desc, desc_stride, strings, dev_pitch);  // more than the pinned buffer holds
   BriskFrameCounters c;
-  memcpy(&c, ctx->h_res + o_cnt, sizeof(c));
+  memcpy(&c, h_res + o_cnt, sizeof(c));
   int rc = overflow_to_rc(ctx, c.overflow);
   if (rc) return rc;
   const int cnt = which ? c.ndesc : c.nkp;
@@ -1295,9 +1255,9 @@ static int download_single(brisk_hip_ctx* ctx, int which, brisk_hip_keypoint* kp
   if (!which) ctx->spec_nkp = cnt + cnt / 4 + 64;
   if (!kps || cnt == 0) return BRISK_HIP_OK;
   if (cnt > cap) return fail(ctx, BRISK_HIP_ERR_CAPACITY, want_desc ? "output descriptor buffer too small" : "output keypoint buffer too small");
-  memcpy(kps, ctx->h_res + o_kp, (size_t)cnt * sizeof(BriskKeyPoint));
+  memcpy(kps, h_res + o_kp, (size_t)cnt * sizeof(BriskKeyPoint));
   if (want_desc) {
-    const uint8_t* src = ctx->h_res + o_desc;
+    const uint8_t* src = h_res + o_desc;
     if (dev_pitch == desc_stride && strings == desc_stride) memcpy(desc, src, (size_t)cnt * strings);
     else for (int i = 0; i < cnt; ++i) memcpy(desc + (size_t)i * desc_stride, src + (size_t)i * dev_pitch, strings);
   }
@@ -1420,12 +1380,9 @@ static int download_all_locked(brisk_hip_ctx* ctx, int which, const brisk_hip_ba
     export_finish(ctx, E);
   }
   const ExportLayout LY(dst->frames_cap, dst->rows_cap, dstride);
-  if (LY.bytes > E.slab_bytes) {
+  if (LY.bytes > E.slab.cap) {
     if (E.done_valid) HIPCHK(ctx, hipEventSynchronize(E.done));
-    if (E.slab) (void)hipFree(E.slab);
-    E.slab = nullptr; E.slab_bytes = 0;
-    HIPCHK(ctx, hipMalloc(&E.slab, LY.bytes));
-    E.slab_bytes = LY.bytes;
+    HIPCHK(ctx, E.slab.grow(LY.bytes));
   }
   // where the egress kernel writes: the caller's arrays when the device can reach all of them, else the bounce buffer
   brisk_hip_batch_host_results W = *dst;
@@ -1437,17 +1394,13 @@ static int download_all_locked(brisk_hip_ctx* ctx, int which, const brisk_hip_ba
     W.counts = static_cast<int*>(dv[0]); W.flags = static_cast<int*>(dv[1]); W.offsets = static_cast<long long*>(dv[2]);
     W.kps = static_cast<brisk_hip_keypoint*>(dv[3]); W.desc = want_desc ? static_cast<uint8_t*>(dv[4]) : nullptr;
   } else {
-    if (LY.bytes > E.bounce_bytes) {
-      if (E.bounce) (void)hipHostFree(E.bounce);
-      E.bounce = nullptr; E.bounce_bytes = 0;
-      HIPCHK(ctx, hipHostMalloc((void**)&E.bounce, LY.bytes, hipHostMallocDefault));
-      E.bounce_bytes = LY.bytes;
-    }
-    W.counts = reinterpret_cast<int*>(E.bounce + LY.counts); W.flags = reinterpret_cast<int*>(E.bounce + LY.flags);
-    W.offsets = reinterpret_cast<long long*>(E.bounce + LY.offsets); W.kps = reinterpret_cast<brisk_hip_keypoint*>(E.bounce + LY.kps);
-    W.desc = want_desc ? E.bounce + LY.desc : nullptr;
+    HIPCHK(ctx, E.bounce.grow(LY.bytes));
+    uint8_t* const bo = E.bounce.as<uint8_t>();
+    W.counts = reinterpret_cast<int*>(bo + LY.counts); W.flags = reinterpret_cast<int*>(bo + LY.flags);
+    W.offsets = reinterpret_cast<long long*>(bo + LY.offsets); W.kps = reinterpret_cast<brisk_hip_keypoint*>(bo + LY.kps);
+    W.desc = want_desc ? bo + LY.desc : nullptr;
   }
-  uint8_t* sl = static_cast<uint8_t*>(E.slab);
+  uint8_t* sl = E.slab.as<uint8_t>();
   const BriskExportSlab S{reinterpret_cast<int*>(sl + LY.counts), reinterpret_cast<int*>(sl + LY.flags),
                           reinterpret_cast<long long*>(sl + LY.offsets), reinterpret_cast<uint32_t*>(sl + LY.kps),
                           reinterpret_cast<uint32_t*>(sl + LY.desc)};
@@ -1536,13 +1489,10 @@ int brisk_hip_detect_describe_batch_host_results(brisk_hip_ctx* ctx, const brisk
 // ---- the multi-image overloads of the reference's base classes as batches -------------------------------------------------------
 static int ensure_images(brisk_hip_ctx* ctx, int nimages, int w, int h) {
   const size_t dframe = (size_t)brisk_align_up(w, 64) * h;
-  if (ctx->imgs_bytes < dframe * (size_t)nimages) {
+  if (ctx->d_imgs.cap < dframe * (size_t)nimages) {
     HIPCHK(ctx, hipDeviceSynchronize());
-    if (ctx->d_imgs) (void)hipFree(ctx->d_imgs);
-    ctx->d_imgs = nullptr; ctx->imgs_bytes = 0;
     ctx->imgs.n = 0;
-    HIPCHK(ctx, hipMalloc(&ctx->d_imgs, dframe * (size_t)nimages + 256));
-    ctx->imgs_bytes = dframe * (size_t)nimages;
+    HIPCHK(ctx, ctx->d_imgs.grow(dframe * (size_t)nimages, 256));
   }
   return BRISK_HIP_OK;
 }
@@ -1564,7 +1514,7 @@ int brisk_hip_detect_images(brisk_hip_ctx* ctx, const uint8_t* const* images, in
   int rc = ensure_images(ctx, nimages, w, h);
   if (rc) return rc;
   ctx->imgs.n = 0;
-  rc = batch_host_locked(ctx, nullptr, nullptr, nimages, w, h, 0, stride, threshold, octaves, images, ctx->d_imgs);
+  rc = batch_host_locked(ctx, nullptr, nullptr, nimages, w, h, 0, stride, threshold, octaves, images, ctx->d_imgs.as<uint8_t>());
   if (rc) return rc;
   remember_images(ctx, images, nimages, w, h, stride);
   return download_all_locked(ctx, 0, dst, ctx->stream, ticket);
@@ -1616,7 +1566,7 @@ int brisk_hip_describe_images(brisk_hip_ctx* ctx, const brisk_hip_pattern* pat, 
     const int step = staged ? BRISK_STAGED_SLICE : nimages;
     for (int f0 = 0, k = 0; f0 < nimages; f0 += step, ++k) {
       const int nf = nimages - f0 < step ? nimages - f0 : step;
-      rc = upload_frames(ctx, ctx->d_imgs + (size_t)f0 * dframe, dframe, dpitch, images + f0, nf, w, h, stride, staged, k & 1, s);
+      rc = upload_frames(ctx, ctx->d_imgs.as<uint8_t>() + (size_t)f0 * dframe, dframe, dpitch, images + f0, nf, w, h, stride, staged, k & 1, s);
       if (rc) return rc;
     }
     remember_images(ctx, images, nimages, w, h, stride);
@@ -1628,29 +1578,26 @@ int brisk_hip_describe_images(brisk_hip_ctx* ctx, const brisk_hip_pattern* pat, 
   {
     const size_t kpitch = sizeof(BriskKeyPoint) * (size_t)(nmax > 0 ? nmax : 1);
     const size_t need = sizeof(int) * (size_t)nimages + 256 + kpitch * (size_t)nimages;
-    if (need > ctx->kin_pin_bytes) {
+    if (need > ctx->h_kin_pin.cap) {
       if (ctx->kin_pin_used) HIPCHK(ctx, hipEventSynchronize(ctx->kin_pin_ev));
       ctx->kin_pin_used = false;
-      if (ctx->h_kin_pin) (void)hipHostFree(ctx->h_kin_pin);
-      ctx->h_kin_pin = nullptr; ctx->kin_pin_bytes = 0;
-      HIPCHK(ctx, hipHostMalloc((void**)&ctx->h_kin_pin, need + need / 4, hipHostMallocDefault));
-      ctx->kin_pin_bytes = need + need / 4;
+      HIPCHK(ctx, ctx->h_kin_pin.grow(need + need / 4));
       if (!ctx->kin_pin_ev) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->kin_pin_ev, hipEventDisableTiming));
     }
     if (ctx->kin_pin_used) HIPCHK(ctx, hipEventSynchronize(ctx->kin_pin_ev));  // (the previous call's copy out of the block)
-    int* h_n = reinterpret_cast<int*>(ctx->h_kin_pin);
-    uint8_t* h_k = ctx->h_kin_pin + ((sizeof(int) * (size_t)nimages + 255) & ~(size_t)255);
+    int* h_n = ctx->h_kin_pin.as<int>();
+    uint8_t* h_k = ctx->h_kin_pin.as<uint8_t>() + ((sizeof(int) * (size_t)nimages + 255) & ~(size_t)255);
     for (int f = 0; f < nimages; ++f) {
       h_n[f] = nkps[f];
       if (nkps[f] > 0) memcpy(h_k + (size_t)f * kpitch, kps[f], sizeof(BriskKeyPoint) * (size_t)nkps[f]);
     }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_n_in, h_n, sizeof(int) * (size_t)nimages, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_n_in.p, h_n, sizeof(int) * (size_t)nimages, hipMemcpyHostToDevice, s));
     if (nmax > 0)
-      HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_kp_in, sizeof(BriskKeyPoint) * (size_t)ctx->B.kp_cap, h_k, kpitch, kpitch, (size_t)nimages, hipMemcpyHostToDevice, s));
+      HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_kp_in.p, sizeof(BriskKeyPoint) * (size_t)ctx->B.kp_cap, h_k, kpitch, kpitch, (size_t)nimages, hipMemcpyHostToDevice, s));
     HIPCHK(ctx, hipEventRecord(ctx->kin_pin_ev, s));
     ctx->kin_pin_used = true;
   }
-  rc = describe_batch_locked(ctx, pat, ctx->d_imgs, nimages, w, h, (long)dframe, dpitch, rotation_invariant, scale_invariant, nmax, s);
+  rc = describe_batch_locked(ctx, pat, ctx->d_imgs.as<uint8_t>(), nimages, w, h, (long)dframe, dpitch, rotation_invariant, scale_invariant, nmax, s);
   if (rc) return rc;
   if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
   return download_all_locked(ctx, 1, dst, s, ticket);
@@ -1675,16 +1622,17 @@ static int detect_host(brisk_hip_ctx* ctx, const uint8_t* img, int w, int h, int
   const size_t img_bytes = (size_t)brisk_align_up(w, 64) * h;
   rc = ensure_stage(ctx, img_bytes * 2);
   if (rc) return rc;
+  uint8_t* const d_stage = ctx->d_stage.as<uint8_t>();
   const int pitch = brisk_align_up(w, 64);
   if (workspace_acquire(ctx, ctx->stream)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
   WorkspaceGuard guard(ctx, ctx->stream);  // (run_batch records the event again at its own end: harmless)
-  HIPCHK(ctx, upload_rows(ctx->d_stage, pitch, img, stride, w, h, ctx->stream));
+  HIPCHK(ctx, upload_rows(d_stage, pitch, img, stride, w, h, ctx->stream));
   const uint8_t* d_mask = nullptr;
   if (mask) {
-    HIPCHK(ctx, upload_rows(ctx->d_stage + img_bytes, pitch, mask, mask_stride, w, h, ctx->stream));
-    d_mask = ctx->d_stage + img_bytes;
+    HIPCHK(ctx, upload_rows(d_stage + img_bytes, pitch, mask, mask_stride, w, h, ctx->stream));
+    d_mask = d_stage + img_bytes;
   }
-  rc = run_batch(ctx, nullptr, ctx->d_stage, 1, w, h, (long)img_bytes, pitch, threshold, octaves, d_mask, (long)img_bytes,
+  rc = run_batch(ctx, nullptr, d_stage, 1, w, h, (long)img_bytes, pitch, threshold, octaves, d_mask, (long)img_bytes,
                  pitch, ctx->stream, true, false, uni_radius, uni_max, !suppress_scale_nonmaxima, BRISK_LOWER_THRESHOLD, bucketing);
   if (rc) return rc;
   ctx->img_cache.valid = true;
@@ -1738,14 +1686,15 @@ int brisk_hip_compute_scale(brisk_hip_ctx* ctx, const uint8_t* img, int w, int h
   const size_t img_bytes = (size_t)pitch * h;
   rc = ensure_stage(ctx, img_bytes * 2);
   if (rc) return rc;
+  uint8_t* const d_stage = ctx->d_stage.as<uint8_t>();
   if (workspace_acquire(ctx, ctx->stream)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
   WorkspaceGuard guard(ctx, ctx->stream);
   ctx->img_cache.valid = false;
-  HIPCHK(ctx, upload_rows(ctx->d_stage, pitch, img, stride, w, h, ctx->stream));
+  HIPCHK(ctx, upload_rows(d_stage, pitch, img, stride, w, h, ctx->stream));
   if (n_in == 0) {
     // an empty list makes GetKeypoints detect (brisk-scale-space.cc:104): plain detection on the pyramid ComputeScale
     // builds (lowerThreshold_ = 0, brisk-feature-detector.cc:90), without the mask filter
-    rc = run_batch(ctx, nullptr, ctx->d_stage, 1, w, h, (long)img_bytes, pitch, threshold, octaves, nullptr, 0, 0, ctx->stream,
+    rc = run_batch(ctx, nullptr, d_stage, 1, w, h, (long)img_bytes, pitch, threshold, octaves, nullptr, 0, 0, ctx->stream,
                    true, false, 0.0, 0x7FFFFFFF, !suppress_scale_nonmaxima, 0);
     if (rc) return rc;
     return download_single(ctx, 0, out, cap, n, nullptr, 0, 0, 0, ctx->spec_nkp < cap ? ctx->spec_nkp : cap);
@@ -1758,9 +1707,9 @@ int brisk_hip_compute_scale(brisk_hip_ctx* ctx, const uint8_t* img, int w, int h
   if (ctx->dirty_frames > 0) brisk_launch_smap_clear(ctx->dirtyG, ctx->B, ctx->dirty_frames, ctx->stream);
   ctx->dirtyG = ctx->G;
   ctx->dirty_frames = 1;  // (the kernel marks the frame for a complete clear: the walk writes the cache anywhere)
-  HIPCHK(ctx, hipMemcpyAsync(ctx->d_kp_in, in, sizeof(BriskKeyPoint) * (size_t)n_in, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->d_kp_in.p, in, sizeof(BriskKeyPoint) * (size_t)n_in, hipMemcpyHostToDevice, ctx->stream));
   ctx->last_l0_ext = nullptr;
-  brisk_launch_compute_scale(ctx->G, ctx->B, ctx->d_stage, pitch, ctx->d_kp_in, n_in, suppress_scale_nonmaxima ? 1 : 0,
+  brisk_launch_compute_scale(ctx->G, ctx->B, d_stage, pitch, ctx->d_kp_in.as<BriskKeyPoint>(), n_in, suppress_scale_nonmaxima ? 1 : 0,
                              ctx->stream);
   HIPCHK(ctx, hipGetLastError());
   ctx->last_nframes = 1;
@@ -1783,6 +1732,7 @@ static int describe_host(brisk_hip_ctx* ctx, const brisk_hip_pattern* pat, const
   const size_t img_bytes = (size_t)pitch * h;
   int rc = ensure_stage(ctx, img_bytes * 2);
   if (rc) return rc;
+  uint8_t* const d_stage = ctx->d_stage.as<uint8_t>();
   make_geometry(w, h, 20, 0, &ctx->G, &ctx->T);  // only layer 0 is needed
   if (pat->host.strings > ctx->desc_pitch) ctx->desc_pitch = brisk_align_up(pat->host.strings, 16);
   rc = ensure_buffers(ctx, 1, ctx->G);
@@ -1796,14 +1746,14 @@ static int describe_host(brisk_hip_ctx* ctx, const brisk_hip_pattern* pat, const
                      (same_image || (image_hash_reuse_enabled() && ctx->img_cache.hash == image_sample_hash(img, w, h, stride)));
   ctx->img_cache.valid = reuse;  // an uploaded image overwrites the staging buffer (and is not remembered itself)
   if (reuse) ctx->img_cache.hits++;
-  if (!reuse) HIPCHK(ctx, upload_rows(ctx->d_stage, pitch, img, stride, w, h, ctx->stream));
+  if (!reuse) HIPCHK(ctx, upload_rows(d_stage, pitch, img, stride, w, h, ctx->stream));
   const int n_in = *n;
   // (the count where the kernels read it: a word of the context's pinned block - the call is synchronous, nothing of an earlier
   // call still reads it)
   if (int rcb = ensure_single_buffer(ctx)) return rcb;
-  int* const h_n_in = reinterpret_cast<int*>(ctx->h_res + 16);
+  int* const h_n_in = reinterpret_cast<int*>(ctx->h_res.as<uint8_t>() + 16);
   __atomic_store_n(h_n_in, n_in, __ATOMIC_RELEASE);
-  if (n_in) HIPCHK(ctx, hipMemcpyAsync(ctx->d_kp_in, kps, sizeof(BriskKeyPoint) * (size_t)n_in, hipMemcpyHostToDevice, ctx->stream));
+  if (n_in) HIPCHK(ctx, hipMemcpyAsync(ctx->d_kp_in.p, kps, sizeof(BriskKeyPoint) * (size_t)n_in, hipMemcpyHostToDevice, ctx->stream));
   if (ctx->dirty_frames > 0) {  // the clear needs the last detect batch's counters, which are reset below
     brisk_launch_smap_clear(ctx->dirtyG, ctx->B, ctx->dirty_frames, ctx->stream);
     ctx->dirty_frames = 0;
@@ -1821,7 +1771,7 @@ static int describe_host(brisk_hip_ctx* ctx, const brisk_hip_pattern* pat, const
     ctx->last_l0_pitch = (long)img_bytes;
   } else {
     ctx->last_l0_ext = nullptr;
-    brisk_launch_layer0_only(ctx->G, ctx->B, 1, ctx->d_stage, (long)img_bytes, pitch, ctx->stream);
+    brisk_launch_layer0_only(ctx->G, ctx->B, 1, d_stage, (long)img_bytes, pitch, ctx->stream);
     Bd.band_h = 64;  // brisk_launch_layer0_only: k_pyramid_even's 64-row band sums
   }
   brisk_prof_mark(&ctx->prof, BRISK_STG_DETECT, ctx->stream);
@@ -1833,7 +1783,7 @@ static int describe_host(brisk_hip_ctx* ctx, const brisk_hip_pattern* pat, const
   BriskDescribeBuffers Dd = ctx->D;
   integral_format(ctx, pat, false, &Dd.ibits);
   if (desc_stride == pat->host.strings && pat->host.strings % 8 == 0 && pat->host.strings <= ctx->D.desc_pitch) Dd.desc_pitch = pat->host.strings;
-  brisk_launch_describe(ctx->G, P, Bd, Dd, 1, ctx->d_kp_in, h_n_in, sizeof(int), ctx->stream, &ctx->prof, nullptr, n_in);
+  brisk_launch_describe(ctx->G, P, Bd, Dd, 1, ctx->d_kp_in.as<BriskKeyPoint>(), h_n_in, sizeof(int), ctx->stream, &ctx->prof, nullptr, n_in);
   if (ctx->prof.on) ctx->prof.calls++;
   HIPCHK(ctx, hipGetLastError());
   ctx->last_nframes = 1;
@@ -1861,18 +1811,6 @@ int brisk_hip_describe_same_image(brisk_hip_ctx* ctx, const brisk_hip_pattern* p
 // Hamming brute-force matcher
 // ---------------------------------------------------------------------------------------------------------------
 static_assert(sizeof(brisk_hip_dmatch) == 16 && sizeof(BriskDMatch) == 16, "cv::DMatch layout");
-
-namespace {
-struct DevBuf {  // frees its allocations when the call returns
-  std::vector<void*> ptrs;
-  ~DevBuf() { for (void* p : ptrs) (void)hipFree(p); }
-  hipError_t alloc(void** p, size_t bytes) {
-    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-    if (e == hipSuccess) ptrs.push_back(*p);
-    return e;
-  }
-};
-}  // namespace
 
 // mode 0: knn (param k), mode 1: radius (param cap)
 static int match_host(brisk_hip_ctx* ctx, const uint8_t* query, int nq, int q_pitch, int dim, int nimg,
@@ -1907,19 +1845,19 @@ static int match_host(brisk_hip_ctx* ctx, const uint8_t* query, int nq, int q_pi
   long qblock = (256L << 20) / (dist_pitch * 2);                // <= 256 MB of distances at a time
   if (qblock < 64) qblock = 64;
   if (qblock > nq) qblock = nq;
-  DevBuf mem;
-  uint8_t *d_q = nullptr, *d_t = nullptr, *d_mask = nullptr;
-  uint16_t* d_dist = nullptr;
-  int *d_start = nullptr, *d_has = nullptr, *d_masked = nullptr, *d_cnt = nullptr;
-  BriskDMatch* d_out = nullptr;
-  HIPCHK(ctx, mem.alloc((void**)&d_q, (size_t)nq * dim16));
-  HIPCHK(ctx, mem.alloc((void**)&d_t, (size_t)(nt > 0 ? nt : 1) * tp));
-  HIPCHK(ctx, mem.alloc((void**)&d_dist, (size_t)qblock * dist_pitch * 2));
-  HIPCHK(ctx, mem.alloc((void**)&d_start, sizeof(int) * (nimg + 1)));
-  HIPCHK(ctx, mem.alloc((void**)&d_has, sizeof(int) * (nimg > 0 ? nimg : 1)));
-  HIPCHK(ctx, mem.alloc((void**)&d_masked, sizeof(int) * (size_t)qblock));
-  HIPCHK(ctx, mem.alloc((void**)&d_cnt, sizeof(int) * (size_t)nq));
-  HIPCHK(ctx, mem.alloc((void**)&d_out, sizeof(BriskDMatch) * (size_t)nq * (k_or_cap > 0 ? k_or_cap : 1)));
+  DeviceBuf m_q, m_t, m_dist, m_start, m_has, m_masked, m_cnt, m_out, m_mask;  // this call's scratch: freed when it returns (every size below is at least one element)
+  HIPCHK(ctx, m_q.grow((size_t)nq * dim16));
+  HIPCHK(ctx, m_t.grow((size_t)(nt > 0 ? nt : 1) * tp));
+  HIPCHK(ctx, m_dist.grow((size_t)qblock * dist_pitch * 2));
+  HIPCHK(ctx, m_start.grow(sizeof(int) * (nimg + 1)));
+  HIPCHK(ctx, m_has.grow(sizeof(int) * (nimg > 0 ? nimg : 1)));
+  HIPCHK(ctx, m_masked.grow(sizeof(int) * (size_t)qblock));
+  HIPCHK(ctx, m_cnt.grow(sizeof(int) * (size_t)nq));
+  HIPCHK(ctx, m_out.grow(sizeof(BriskDMatch) * (size_t)nq * (k_or_cap > 0 ? k_or_cap : 1)));
+  uint8_t *const d_q = m_q.as<uint8_t>(), *const d_t = m_t.as<uint8_t>(), *d_mask = nullptr;
+  uint16_t* const d_dist = m_dist.as<uint16_t>();
+  int *const d_start = m_start.as<int>(), *const d_has = m_has.as<int>(), *const d_masked = m_masked.as<int>(), *const d_cnt = m_cnt.as<int>();
+  BriskDMatch* const d_out = m_out.as<BriskDMatch>();
   hipStream_t s = ctx->stream;
   HIPCHK(ctx, hipMemcpy2DAsync(d_q, dim16, query, q_pitch, dim16, nq, hipMemcpyHostToDevice, s));
   for (int i = 0; i < nimg; ++i)
@@ -1931,7 +1869,8 @@ static int match_host(brisk_hip_ctx* ctx, const uint8_t* query, int nq, int q_pi
   long mpitch = 0;
   if (any_mask && nt > 0) {  // concatenated mask, nq x nt (255 where an image has no mask)
     mpitch = nt;
-    HIPCHK(ctx, mem.alloc((void**)&d_mask, (size_t)nq * mpitch));
+    HIPCHK(ctx, m_mask.grow((size_t)nq * mpitch));
+    d_mask = m_mask.as<uint8_t>();
     HIPCHK(ctx, hipMemsetAsync(d_mask, 0xFF, (size_t)nq * mpitch, s));
     for (int i = 0; i < nimg; ++i)
       if (has_mask[i])
@@ -2014,14 +1953,11 @@ int brisk_hip_match_knn_device(brisk_hip_ctx* ctx, const uint8_t* d_query, int n
   const long dist_pitch = ((long)nt + 63) / 64 * 64 + 64;
   const size_t need = (size_t)nq * dist_pitch * 2;
   if (workspace_acquire(ctx, st)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
-  if (ctx->match_bytes < need) {  // workspace kept by the context (the call is asynchronous)
+  if (ctx->d_match.cap < need) {  // workspace kept by the context (the call is asynchronous)
     HIPCHK(ctx, hipDeviceSynchronize());
-    if (ctx->d_match) (void)hipFree(ctx->d_match);
-    ctx->d_match = nullptr; ctx->match_bytes = 0;
-    HIPCHK(ctx, hipMalloc(&ctx->d_match, need));
-    ctx->match_bytes = need;
+    HIPCHK(ctx, ctx->d_match.grow(need));
   }
-  uint16_t* d_dist = static_cast<uint16_t*>(ctx->d_match);
+  uint16_t* d_dist = ctx->d_match.as<uint16_t>();
   brisk_launch_match_dist(d_query, q_pitch, 0, nq, d_train, t_pitch, nt, dim16 / 8, nullptr, 0, d_dist, dist_pitch, st);
   brisk_launch_match_knn(d_dist, dist_pitch, 0, nq, nt, nullptr, 1, nullptr, k,
                          reinterpret_cast<BriskDMatch*>(d_out), d_out_count, st);
@@ -2075,16 +2011,13 @@ static int image16_call(brisk_hip_ctx* ctx, int which, const uint16_t* src, int 
   // scratch kept by the context (the functions may be called per frame): grown when a call needs more, never shrunk
   const size_t need[3] = {(size_t)w * h * 2, (size_t)dw * dh * delem, which == 2 ? (size_t)w * h * 4 : 0};
   for (int i = 0; i < 3; ++i) {
-    if (need[i] <= ctx->img16_bytes[i]) continue;
+    if (need[i] <= ctx->d_img16[i].cap) continue;
     HIPCHK(ctx, hipStreamSynchronize(s));
-    if (ctx->d_img16[i]) (void)hipFree(ctx->d_img16[i]);
-    ctx->d_img16[i] = nullptr; ctx->img16_bytes[i] = 0;
-    HIPCHK(ctx, hipMalloc(&ctx->d_img16[i], need[i]));
-    ctx->img16_bytes[i] = need[i];
+    HIPCHK(ctx, ctx->d_img16[i].grow(need[i]));
   }
-  uint16_t* d_src = static_cast<uint16_t*>(ctx->d_img16[0]);
-  void* d_dst = ctx->d_img16[1];
-  float* d_tmp = static_cast<float*>(ctx->d_img16[2]);
+  uint16_t* d_src = ctx->d_img16[0].as<uint16_t>();
+  void* d_dst = ctx->d_img16[1].p;
+  float* d_tmp = ctx->d_img16[2].as<float>();
   HIPCHK(ctx, hipMemcpy2DAsync(d_src, (size_t)w * 2, src, (size_t)src_stride * 2, (size_t)w * 2, h, hipMemcpyHostToDevice, s));
   if (which == 0) brisk_launch_halfsample16(d_src, w, w, h, (uint16_t*)d_dst, dw, s);
   else if (which == 1) brisk_launch_twothirdsample16(d_src, w, w, h, (uint16_t*)d_dst, dw, s);
@@ -2167,9 +2100,10 @@ int brisk_hip_stream_ceiling(brisk_hip_ctx* ctx, size_t bytes, double* copy_GBps
   if (!ctx || bytes < (1u << 20)) return BRISK_HIP_ERR_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  void *a = nullptr, *b = nullptr;
-  HIPCHK(ctx, hipMalloc(&a, bytes));
-  if (hipMalloc(&b, bytes) != hipSuccess) { (void)hipFree(a); return fail(ctx, BRISK_HIP_ERR_HIP, "hipMalloc failed"); }
+  DeviceBuf ma, mb;
+  HIPCHK(ctx, ma.grow(bytes));
+  if (mb.grow(bytes) != hipSuccess) return fail(ctx, BRISK_HIP_ERR_HIP, "hipMalloc failed");
+  void *const a = ma.p, *const b = mb.p;
   (void)hipMemset(a, 1, bytes);
   (void)hipMemset(b, 2, bytes);
   (void)hipDeviceSynchronize();  // (null-stream memsets are not ordered against the context's non-blocking stream)
@@ -2190,8 +2124,6 @@ int brisk_hip_stream_ceiling(brisk_hip_ctx* ctx, size_t bytes, double* copy_GBps
     }
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
-  (void)hipFree(a);
-  (void)hipFree(b);
   if (copy_GBps) *copy_GBps = best[0];
   if (read_GBps) *read_GBps = best[1];
   HIPCHK(ctx, hipGetLastError());
@@ -2277,7 +2209,7 @@ int brisk_hip_debug_filter_keypoints(brisk_hip_ctx* ctx, const brisk_hip_keypoin
   const float scaling = (float)(15.0 / (float)radius);
   const int oh = (int)(rows * ceil(scaling) + 32), ow = (int)(cols * ceil(scaling) + 32);
   const long occ_frame = ((long)oh * ow + 255) / 256 * 256;
-  brisk_launch_uniformity(ctx->B.kp_out, ctx->B.counters, ctx->d_uni_order, ctx->d_uni_tmp, ctx->d_occ, occ_frame, ow, ctx->B.kp_cap, scaling,
+  brisk_launch_uniformity(ctx->B.kp_out, ctx->B.counters, ctx->d_uni_order.as<int>(), ctx->d_uni_tmp.as<BriskKeyPoint>(), ctx->d_occ.as<uint8_t>(), occ_frame, ow, ctx->B.kp_cap, scaling,
                           max_keypoints, 1, s);
   HIPCHK(ctx, hipGetLastError());
   ctx->last_nframes = 1;

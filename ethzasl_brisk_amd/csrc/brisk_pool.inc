@@ -43,22 +43,19 @@ struct PoolGroup {
   int rc = BRISK_HIP_OK;
   std::string err;
   // staging (pinned host) and device frames, [maxb] slots of `frame_bytes`
-  uint8_t* h_frames = nullptr;
-  uint8_t* d_frames = nullptr;
-  size_t frame_cap = 0;      // bytes per slot the two buffers were allocated for
+  PinnedBuf h_frames;
+  DeviceBuf d_frames;
   size_t frame_bytes = 0;    // bytes per slot of the current use (dpitch * h)
   int dpitch = 0;
   std::vector<const uint8_t*> src_dev;  // describe: per member, the retained device copy of its frame (null: the frame was staged)
   // describe: provided keypoints (pinned), [maxb][kin_cap]
-  brisk_hip_keypoint* h_kin = nullptr;
-  int* h_nin = nullptr;
-  int kin_cap = 0;
+  PinnedBuf h_kin, h_nin;
+  int kin_cap = 0;           // rows per slot of h_kin
   hipEvent_t copied_ev = nullptr;  // the group's frames are on the device
   // results (pinned)
   brisk_hip_batch_host_results res{};
-  size_t res_bytes = 0;
   int res_stride_cap = 0;
-  uint8_t* res_mem = nullptr;
+  PinnedBuf res_mem;
 };
 }  // namespace
 
@@ -104,40 +101,34 @@ static int pool_prepare_group(brisk_hip_pool* P, std::unique_lock<std::mutex>& l
   const int dpitch = brisk_align_up(key.w, 64);
   const size_t fb = (size_t)dpitch * key.h;
   if (hipSetDevice(P->device) != hipSuccess) return BRISK_HIP_ERR_HIP;
-  if (fb > G.frame_cap) {
+  if (fb * P->maxb > G.d_frames.cap) {  // (the second of the pair)
     // The buffer is FREE: every group that used it is done.  But a describe group that closed and has not reached the
     // device yet may still name frames in it (a token): its copies must be queued before the buffer goes away.
     while (P->submit_seq != P->next_seq) P->cv.wait(lk);
-    if (G.h_frames) (void)hipHostFree(G.h_frames);
-    if (G.d_frames) (void)hipFree(G.d_frames);
-    G.h_frames = nullptr; G.d_frames = nullptr; G.frame_cap = 0;
-    if (hipHostMalloc((void**)&G.h_frames, fb * P->maxb + 256, hipHostMallocDefault) != hipSuccess) return BRISK_HIP_ERR_HIP;
-    if (hipMalloc((void**)&G.d_frames, fb * P->maxb + 256) != hipSuccess) return BRISK_HIP_ERR_HIP;
-    G.frame_cap = fb;
+    G.h_frames.reset();
+    G.d_frames.reset();
+    if (G.h_frames.grow(fb * P->maxb, 256) != hipSuccess || G.d_frames.grow(fb * P->maxb, 256) != hipSuccess) return BRISK_HIP_ERR_HIP;
   }
   if (key.kind == 2 && kin_need > G.kin_cap) {
-    if (G.h_kin) (void)hipHostFree(G.h_kin);
-    G.h_kin = nullptr; G.kin_cap = 0;
     const int cap = ((kin_need > 4096 ? kin_need : 4096) + 1023) / 1024 * 1024;
-    if (hipHostMalloc((void**)&G.h_kin, sizeof(brisk_hip_keypoint) * (size_t)cap * P->maxb, hipHostMallocDefault) != hipSuccess) return BRISK_HIP_ERR_HIP;
+    G.kin_cap = 0;
+    if (G.h_kin.grow(sizeof(brisk_hip_keypoint) * (size_t)cap * P->maxb) != hipSuccess) return BRISK_HIP_ERR_HIP;
     G.kin_cap = cap;
   }
-  if (!G.h_nin && hipHostMalloc((void**)&G.h_nin, sizeof(int) * (size_t)P->maxb, hipHostMallocDefault) != hipSuccess) return BRISK_HIP_ERR_HIP;
+  if (G.h_nin.grow(sizeof(int) * (size_t)P->maxb) != hipSuccess) return BRISK_HIP_ERR_HIP;
   const int rstride = key.kind == 2 ? key.pat->host.strings : 4;  // descriptor rows packed at the descriptor size
-  if (!G.res_mem || rstride > G.res_stride_cap) {
-    if (G.res_mem) (void)hipHostFree(G.res_mem);
-    G.res_mem = nullptr;
+  if (!G.res_mem.p || rstride > G.res_stride_cap) {
     G.res_stride_cap = rstride > 64 ? rstride : 64;
     const ExportLayout LY(P->maxb, P->rows_per_group, G.res_stride_cap);
-    if (hipHostMalloc((void**)&G.res_mem, LY.bytes, hipHostMallocDefault) != hipSuccess) return BRISK_HIP_ERR_HIP;
-    G.res_bytes = LY.bytes;
+    if (G.res_mem.grow(LY.bytes) != hipSuccess) return BRISK_HIP_ERR_HIP;
+    uint8_t* const m = G.res_mem.as<uint8_t>();
     G.res.frames_cap = P->maxb;
     G.res.rows_cap = P->rows_per_group;
-    G.res.counts = reinterpret_cast<int*>(G.res_mem + LY.counts);
-    G.res.flags = reinterpret_cast<int*>(G.res_mem + LY.flags);
-    G.res.offsets = reinterpret_cast<long long*>(G.res_mem + LY.offsets);
-    G.res.kps = reinterpret_cast<brisk_hip_keypoint*>(G.res_mem + LY.kps);
-    G.res.desc = G.res_mem + LY.desc;
+    G.res.counts = reinterpret_cast<int*>(m + LY.counts);
+    G.res.flags = reinterpret_cast<int*>(m + LY.flags);
+    G.res.offsets = reinterpret_cast<long long*>(m + LY.offsets);
+    G.res.kps = reinterpret_cast<brisk_hip_keypoint*>(m + LY.kps);
+    G.res.desc = m + LY.desc;
   }
   G.res.desc_stride = rstride;
   G.key = key;
@@ -179,7 +170,7 @@ static int describe_batch_locked(brisk_hip_ctx* ctx, const brisk_hip_pattern* pa
   Pd.scale_invariant = scl ? 1 : 0;
   BriskDescribeBuffers Dd = ctx->D;
   integral_format(ctx, pat, false, &Dd.ibits);
-  brisk_launch_describe(ctx->G, Pd, Bd, Dd, nframes, ctx->d_kp_in, ctx->d_n_in, sizeof(int), s, &ctx->prof, nullptr, n_in_max);
+  brisk_launch_describe(ctx->G, Pd, Bd, Dd, nframes, ctx->d_kp_in.as<BriskKeyPoint>(), ctx->d_n_in.as<int>(), sizeof(int), s, &ctx->prof, nullptr, n_in_max);
   if (ctx->prof.on) ctx->prof.calls++;
   HIPCHK(ctx, hipGetLastError());
   ctx->last_nframes = nframes;
@@ -199,18 +190,18 @@ static int pool_submit_copies(brisk_hip_pool* P, PoolGroup& G) {
   if (!G.copied_ev) HIPCHK(ctx, hipEventCreateWithFlags(&G.copied_ev, hipEventDisableTiming));
   if (G.key.kind == 1) {
     // one copy for the whole group (staging slots are contiguous)
-    HIPCHK(ctx, hipMemcpyAsync(G.d_frames, G.h_frames, G.frame_bytes * (size_t)G.n, hipMemcpyHostToDevice, P->copy));
+    HIPCHK(ctx, hipMemcpyAsync(G.d_frames.p, G.h_frames.p, G.frame_bytes * (size_t)G.n, hipMemcpyHostToDevice, P->copy));
   } else {
     // describe: retained device copies (D2D) or staged frames (H2D); runs of staged slots go as one copy
     for (int i = 0; i < G.n;) {
-      uint8_t* dst = G.d_frames + (size_t)i * G.frame_bytes;
+      uint8_t* dst = G.d_frames.as<uint8_t>() + (size_t)i * G.frame_bytes;
       if (G.src_dev[i]) {
         HIPCHK(ctx, hipMemcpyAsync(dst, G.src_dev[i], G.frame_bytes, hipMemcpyDeviceToDevice, P->copy));
         ++i;
       } else {
         int j = i + 1;
         while (j < G.n && !G.src_dev[j]) ++j;
-        HIPCHK(ctx, hipMemcpyAsync(dst, G.h_frames + (size_t)i * G.frame_bytes, G.frame_bytes * (size_t)(j - i), hipMemcpyHostToDevice, P->copy));
+        HIPCHK(ctx, hipMemcpyAsync(dst, G.h_frames.as<uint8_t>() + (size_t)i * G.frame_bytes, G.frame_bytes * (size_t)(j - i), hipMemcpyHostToDevice, P->copy));
         i = j;
       }
     }
@@ -229,13 +220,13 @@ static int pool_submit_batch(brisk_hip_pool* P, PoolGroup& G, unsigned* ticket) 
   if (K.kind == 1) {
     HIPCHK(ctx, hipStreamWaitEvent(s, G.copied_ev, 0));
     // (the batch reads the frames where they are: the group's buffer is not touched again before the group is done)
-    int rc = run_batch(ctx, nullptr, G.d_frames, G.n, K.w, K.h, (long)G.frame_bytes, G.dpitch, K.threshold, K.octaves, nullptr, 0, 0, s, true,
+    int rc = run_batch(ctx, nullptr, G.d_frames.as<uint8_t>(), G.n, K.w, K.h, (long)G.frame_bytes, G.dpitch, K.threshold, K.octaves, nullptr, 0, 0, s, true,
                        false, 0.0, 0x7FFFFFFF, false, BRISK_LOWER_THRESHOLD, nullptr);
     if (rc) return rc;
     return download_all_locked(ctx, 0, &G.res, s, ticket, true, true);
   }
   int nmax = 0;
-  for (int i = 0; i < G.n; ++i) nmax = G.h_nin[i] > nmax ? G.h_nin[i] : nmax;
+  for (int i = 0; i < G.n; ++i) nmax = G.h_nin.as<int>()[i] > nmax ? G.h_nin.as<int>()[i] : nmax;
   if (nmax > ctx->kp_cap) return fail(ctx, BRISK_HIP_ERR_CAPACITY, "more keypoints than the pool's capacity");
   if (int rcp = check_pattern_device(ctx, K.pat)) return rcp;
   BriskGeom Gd;
@@ -247,12 +238,12 @@ static int pool_submit_batch(brisk_hip_pool* P, PoolGroup& G, unsigned* ticket) 
   if (workspace_acquire(ctx, s)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
   WorkspaceGuard guard(ctx, s);
   // the provided keypoints into the context's own buffers: on the compute stream, behind the kernels that still read them
-  HIPCHK(ctx, hipMemcpyAsync(ctx->d_n_in, G.h_nin, sizeof(int) * (size_t)G.n, hipMemcpyHostToDevice, s));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->d_n_in.p, G.h_nin.p, sizeof(int) * (size_t)G.n, hipMemcpyHostToDevice, s));
   if (nmax > 0)
-    HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_kp_in, sizeof(BriskKeyPoint) * (size_t)ctx->B.kp_cap, G.h_kin, sizeof(brisk_hip_keypoint) * (size_t)G.kin_cap,
+    HIPCHK(ctx, hipMemcpy2DAsync(ctx->d_kp_in.p, sizeof(BriskKeyPoint) * (size_t)ctx->B.kp_cap, G.h_kin.p, sizeof(brisk_hip_keypoint) * (size_t)G.kin_cap,
                                  sizeof(brisk_hip_keypoint) * (size_t)nmax, (size_t)G.n, hipMemcpyHostToDevice, s));
   HIPCHK(ctx, hipStreamWaitEvent(s, G.copied_ev, 0));
-  rc = describe_batch_locked(ctx, K.pat, G.d_frames, G.n, K.w, K.h, (long)G.frame_bytes, G.dpitch, K.rot, K.scl, nmax, s);
+  rc = describe_batch_locked(ctx, K.pat, G.d_frames.as<uint8_t>(), G.n, K.w, K.h, (long)G.frame_bytes, G.dpitch, K.rot, K.scl, nmax, s);
   if (rc) return rc;
   if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
   return download_all_locked(ctx, 1, &G.res, s, ticket, true, true);
@@ -305,20 +296,20 @@ static int pool_run(brisk_hip_pool* P, const PoolKey& key, const uint8_t* img, i
       // (FREE is fine: the frames stay in the buffer until it is prepared for another use, which changes the generation)
       if (S.state != PG_FORMING && S.state != PG_PREP && S.gen == (unsigned)((token >> 16) & 0xFFFFFFu) && sslot < S.n && S.key.w == key.w &&
           S.key.h == key.h && S.key.kind == 1 && S.rc == BRISK_HIP_OK)
-        retained = S.d_frames + (size_t)sslot * S.frame_bytes;
+        retained = S.d_frames.as<uint8_t>() + (size_t)sslot * S.frame_bytes;
     }
   }
   G.src_dev[slot] = retained;
-  if (key.kind == 2) G.h_nin[slot] = nin;
+  if (key.kind == 2) G.h_nin.as<int>()[slot] = nin;
   lk.unlock();
   clk.lap(0);
   // staging: plain CPU copies into pinned memory, every member on its own thread
   if (!retained) {
-    uint8_t* dst = G.h_frames + (size_t)slot * G.frame_bytes;
+    uint8_t* dst = G.h_frames.as<uint8_t>() + (size_t)slot * G.frame_bytes;
     if (stride == G.dpitch) memcpy(dst, img, (size_t)G.dpitch * (key.h - 1) + key.w);
     else for (int y = 0; y < key.h; ++y) memcpy(dst + (size_t)y * G.dpitch, img + (size_t)y * stride, (size_t)key.w);
   }
-  if (key.kind == 2 && nin > 0) memcpy(G.h_kin + (size_t)slot * G.kin_cap, kin, sizeof(brisk_hip_keypoint) * (size_t)nin);
+  if (key.kind == 2 && nin > 0) memcpy(G.h_kin.as<brisk_hip_keypoint>() + (size_t)slot * G.kin_cap, kin, sizeof(brisk_hip_keypoint) * (size_t)nin);
   clk.lap(1);
   lk.lock();
   G.copied++;
@@ -439,14 +430,8 @@ void brisk_hip_pool_destroy(brisk_hip_pool* P) {
   if (!P) return;
   (void)hipSetDevice(P->device);
   (void)hipDeviceSynchronize();
-  for (PoolGroup& G : P->g) {
-    if (G.h_frames) (void)hipHostFree(G.h_frames);
-    if (G.d_frames) (void)hipFree(G.d_frames);
-    if (G.h_kin) (void)hipHostFree(G.h_kin);
-    if (G.h_nin) (void)hipHostFree(G.h_nin);
-    if (G.res_mem) (void)hipHostFree(G.res_mem);
+  for (PoolGroup& G : P->g)  // (the groups' buffers go with the pool, below)
     if (G.copied_ev) (void)hipEventDestroy(G.copied_ev);
-  }
   if (P->copy) (void)hipStreamDestroy(P->copy);
   for (brisk_hip_ctx* c : P->ctx) if (c) brisk_hip_destroy(c);
   delete P;
