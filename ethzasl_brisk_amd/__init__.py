@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "brisk_hip_detect_images", "brisk_hip_describe_images",
     "brisk_hip_pool_create", "brisk_hip_pool_destroy", "brisk_hip_pool_last_error", "brisk_hip_pool_detect", "brisk_hip_pool_describe", "brisk_hip_pool_stats",
     "brisk_hip_batch_download_all", "brisk_hip_batch_download_wait", "brisk_hip_detect_describe_batch_host_results",
+    "brisk_hip_batch_desc_set", "brisk_hip_match_knn_pairs_device",
 ]
 # every symbol include/brisk_hip_debug.h declares: test / tuning builds (BRISK_HIP_TUNING) only
 DEBUG_SYMBOLS = [
@@ -62,6 +63,19 @@ class BatchHostResults(C.Structure):
 
 
 ROWS_CUT = 0x100
+
+
+class DescSet(C.Structure):
+    """brisk_hip_desc_set: `frames` frames of descriptor rows in device memory, the row counts in device memory too"""
+    _fields_ = [("d_desc", C.c_void_p), ("d_counts", C.c_void_p), ("count_stride", C.c_int), ("frame_pitch", C.c_long),
+                ("row_pitch", C.c_int), ("frames", C.c_int)]
+
+
+class PairSpec(C.Structure):
+    """brisk_hip_pair_spec: pair p = (query_first + p * query_step, train_first + p * train_step), or - d_pairs set - a
+    device array of npairs x {query frame, train frame}"""
+    _fields_ = [("npairs", C.c_int), ("query_first", C.c_int), ("query_step", C.c_int), ("train_first", C.c_int),
+                ("train_step", C.c_int), ("d_pairs", C.c_void_p)]
 
 
 class HostResults:
@@ -178,6 +192,9 @@ def load_library():
     L.brisk_hip_match_radius.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_float,
                                          C.c_int, vp, vp]
     L.brisk_hip_match_knn_device.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    L.brisk_hip_batch_desc_set.argtypes = [vp, C.POINTER(DescSet), ip]
+    L.brisk_hip_match_knn_pairs_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(PairSpec), C.c_int, C.c_int,
+                                                   C.c_int, C.c_int, vp, vp, vp, vp]
     L.brisk_hip_reserve.argtypes = [vp, C.c_int, C.c_int]
     L.brisk_hip_detect_uniform.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
                                            C.c_double, C.c_int, vp, C.c_int, ip]
@@ -446,6 +463,44 @@ class Context:
         self.check(self._L.brisk_hip_batch_download(self._h, frame, int(described), _ptr(kps), len(kps), C.byref(n),
                                                     _ptr(desc) if described else None, strings))
         return _kcopy(kps, n.value), (desc[:n.value].copy() if described else None)
+
+    # -- all frame pairs of a batch matched in one call --
+    def batch_desc_set(self):
+        """(DescSet of the last batch's described rows, descriptor bytes); valid until the context's next batch"""
+        st, dim = DescSet(), C.c_int()
+        self.check(self._L.brisk_hip_batch_desc_set(self._h, C.byref(st), C.byref(dim)))
+        return st, dim.value
+
+    def match_knn_pairs(self, query, train, pairs, k, cross_check=False, rows_cap=None, stream=None, dim_bytes=None, out=None,
+                        download=False):
+        """brisk_hip_match_knn_pairs_device.  query / train: DescSet; pairs: PairSpec.  rows_cap None = the context's keypoint
+        capacity, dim_bytes None = the last batch's descriptor size.  Returns the device tensors (matches [npairs, rows_cap, k, 4]
+        int32 - DMATCH records -, counts [npairs, rows_cap], pair_rows [npairs]); `out` = such a triple to be written instead of
+        new (uninitialised) tensors.  Asynchronous unless download=True: that synchronises and returns, per pair, the list of
+        per-query DMATCH arrays BruteForceMatcher.knnMatch returns (a pair with pair_rows -1: an empty list)."""
+        import torch
+        if dim_bytes is None:
+            dim_bytes = self.batch_desc_set()[1]
+        if rows_cap is None:
+            cap = C.c_int()
+            self.check(self._L.brisk_hip_batch_results(self._h, None, None, None, None, None, None, C.byref(cap), None))
+            rows_cap = cap.value
+        n = pairs.npairs
+        if out is None:
+            dev = "cuda:%d" % self.device
+            out = (torch.empty((max(n, 0), max(rows_cap, 0), max(k, 1), 4), dtype=torch.int32, device=dev),
+                   torch.empty((max(n, 0), max(rows_cap, 0)), dtype=torch.int32, device=dev),
+                   torch.empty(max(n, 0), dtype=torch.int32, device=dev))
+        m, cnt, rows = out
+        self.check(self._L.brisk_hip_match_knn_pairs_device(self._h, C.byref(query), C.byref(train), C.byref(pairs), int(dim_bytes), int(k),
+                                                            int(bool(cross_check)), int(rows_cap), m.data_ptr(), cnt.data_ptr(),
+                                                            rows.data_ptr(), C.c_void_p(stream) if stream else None))
+        if not download:
+            return out
+        torch.cuda.synchronize(self.device)
+        hm = m.cpu().numpy().view(DMATCH).reshape(n, rows_cap, max(k, 1))
+        hc, hr = cnt.cpu().numpy(), rows.cpu().numpy()
+        return [[hm[p, q, :hc[p, q]].copy() for q in range(min(max(int(hr[p]), 0), rows_cap))] for p in range(n)]
 
 
 class Pool:

@@ -1966,6 +1966,68 @@ int brisk_hip_match_knn_device(brisk_hip_ctx* ctx, const uint8_t* d_query, int n
   return BRISK_HIP_OK;
 }
 
+int brisk_hip_batch_desc_set(brisk_hip_ctx* ctx, brisk_hip_desc_set* set, int* dim_bytes) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!set) return fail(ctx, BRISK_HIP_ERR_ARG, "batch_desc_set: null destination");
+  if (!ctx->B.counters || !ctx->last_has_desc || ctx->last_nframes <= 0 || !ctx->D.desc)
+    return fail(ctx, BRISK_HIP_ERR_ARG, "batch_desc_set: the context's last call described no batch");
+  const int pitch = ctx->last_desc_pitch ? ctx->last_desc_pitch : ctx->D.desc_pitch;
+  set->d_desc = ctx->D.desc;
+  set->d_counts = &ctx->B.counters[0].ndesc;
+  set->count_stride = (int)(sizeof(BriskFrameCounters) / sizeof(int));
+  set->frame_pitch = (long)ctx->B.kp_cap * pitch;
+  set->row_pitch = pitch;
+  set->frames = ctx->last_nframes;
+  if (dim_bytes) *dim_bytes = ctx->last_strings;
+  return BRISK_HIP_OK;
+}
+
+static const char* match_pairs_check_set(const brisk_hip_desc_set* s, int dim_bytes) {
+  if (!s->d_desc || !s->d_counts) return "match_pairs: a descriptor set without rows or counts";
+  if (s->frames <= 0 || s->count_stride <= 0 || s->frame_pitch < 0) return "match_pairs: bad descriptor set geometry";
+  if (s->row_pitch < dim_bytes) return "match_pairs: pitch smaller than the descriptor";
+  return nullptr;
+}
+
+int brisk_hip_match_knn_pairs_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                     const brisk_hip_pair_spec* pairs, int dim_bytes, int k, int cross_check, int rows_cap,
+                                     brisk_hip_dmatch* d_out, int* d_out_count, int* d_pair_rows, void* stream) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (!query || !train || !pairs || pairs->npairs < 0) return fail(ctx, BRISK_HIP_ERR_ARG, "match_pairs: bad argument");
+  if (k < 1 || k > 2) return fail(ctx, BRISK_HIP_ERR_ARG, "match_pairs: k must be 1 or 2 (brisk_hip_match_knn for more)");
+  if (cross_check && k != 1) return fail(ctx, BRISK_HIP_ERR_ARG, "match_pairs: the cross check needs k == 1");
+  if (dim_bytes != 16 && dim_bytes != 32 && dim_bytes != 48 && dim_bytes != 64)
+    return fail(ctx, BRISK_HIP_ERR_UNSUPPORTED, "match_pairs: descriptor size must be 16, 32, 48 or 64 bytes (brisk_hip_match_knn_device for others)");
+  for (const brisk_hip_desc_set* s : {query, train})
+    if (const char* msg = match_pairs_check_set(s, dim_bytes)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
+  const int np = pairs->npairs;
+  if (np == 0) return BRISK_HIP_OK;
+  if (rows_cap <= 0 || !d_out || !d_out_count || !d_pair_rows) return fail(ctx, BRISK_HIP_ERR_ARG, "match_pairs: bad output argument");
+  if (!pairs->d_pairs) {  // (a list on the device is checked there: d_pair_rows = -1)
+    const long q0 = pairs->query_first, q1 = q0 + (long)(np - 1) * pairs->query_step;
+    const long t0 = pairs->train_first, t1 = t0 + (long)(np - 1) * pairs->train_step;
+    if (q0 < 0 || q0 >= query->frames || q1 < 0 || q1 >= query->frames || t0 < 0 || t0 >= train->frames || t1 < 0 || t1 >= train->frames)
+      return fail(ctx, BRISK_HIP_ERR_ARG, "match_pairs: a pair names a frame outside its set");
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  // no workspace of the context is written, but the sets usually ARE the last batch's result buffers: the stream is ordered
+  // behind that batch, and the next batch (which overwrites them) behind this call
+  if (workspace_acquire(ctx, st)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
+  WorkspaceGuard guard(ctx, st);
+  const BriskDescSet Q{query->d_desc, query->d_counts, query->count_stride, query->frame_pitch, query->row_pitch, query->frames};
+  const BriskDescSet T{train->d_desc, train->d_counts, train->count_stride, train->frame_pitch, train->row_pitch, train->frames};
+  const BriskPairSpec P{np, pairs->query_first, pairs->query_step, pairs->train_first, pairs->train_step, pairs->d_pairs};
+  if (!brisk_launch_match_knn_pairs(Q, T, P, dim_bytes / 4, k, cross_check != 0, rows_cap, reinterpret_cast<BriskDMatch*>(d_out),
+                                    d_out_count, d_pair_rows, st))
+    return fail(ctx, BRISK_HIP_ERR_UNSUPPORTED, "match_pairs: descriptor size not covered");
+  HIPCHK(ctx, hipGetLastError());
+  if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
+  return BRISK_HIP_OK;
+}
+
 int brisk_hip_set_uniformity(brisk_hip_ctx* ctx, double radius, int max_keypoints) {
   if (!ctx) return BRISK_HIP_ERR_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);

@@ -148,6 +148,23 @@ void brisk_launch_match_radius(const uint16_t* dist, long dist_pitch, int q0, in
 bool brisk_launch_match_knn_fused(const uint8_t* query, int q_pitch, int nq, const uint8_t* train, int t_pitch, int nt,
                                   int words32, int k, BriskDMatch* out, int* out_count, hipStream_t s);
 
+// the frame pairs of a batch in one launch (k <= 2, no masks, descriptors of 16 / 32 / 48 / 64 bytes); the structs mirror
+// brisk_hip_desc_set / brisk_hip_pair_spec
+struct BriskDescSet {
+  const uint8_t* desc;
+  const int* counts;
+  int count_stride;  // ints
+  long frame_pitch;  // bytes
+  int row_pitch;     // bytes
+  int frames;
+};
+struct BriskPairSpec {
+  int npairs, query_first, query_step, train_first, train_step;
+  const int* pairs;  // device: npairs x {query frame, train frame}, or null
+};
+bool brisk_launch_match_knn_pairs(const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, int words32, int k, bool cross,
+                                  int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s);
+
 // ---- uniformity enforcement / keypoint bucketing (brisk_uniformity.hip): optional post-filters of the detector's keypoints ----
 void brisk_launch_bucketing(BriskKeyPoint* kp, BriskFrameCounters* counters, int* order, BriskKeyPoint* tmp, int kp_cap, int rows,
                             int cols, int nbu, int nbv, int max_keypoints, int nframes, hipStream_t s);

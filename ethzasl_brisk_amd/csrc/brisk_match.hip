@@ -300,6 +300,193 @@ bool brisk_launch_match_knn_fused(const uint8_t* query, int q_pitch, int nq, con
   return true;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The frame pairs of a batch in one launch (brisk_hip_match_knn_pairs_device): k_match_knn_fused's scheme - 64 queries per
+// workgroup, one per lane with the descriptor in registers, MP_WAVES (8) waves each scanning a slice of the train rows through
+// wave-uniform loads, packed keys, merge through LDS - with everything a pair needs resolved on the device: grid
+// (ceil(rows_cap / 64), pairs); the workgroup finds its pair (arithmetic form or the caller's list), reads the two row
+// counts from the sets' count arrays and leaves at once when its 64 rows lie beyond min(n_a, rows_cap).
+// CROSS (k == 1): the forward match t of row q is kept only if the best match of row t of frame b among ALL rows of frame
+// a is q.  Fused: once the forward keys are merged, lane q takes row t of frame b into its registers and the waves scan
+// frame a the same way (top-1) - the same work as a role-swapped launch, without a scratch buffer of backward keys and
+// without any hand-off between workgroups.
+// ------------------------------------------------------------------------------------------------
+#ifndef MP_WAVES
+// waves of a workgroup = slices of the train rows.  8, not k_match_knn_fused's 16: a CU holds ONE workgroup of 16 waves (71 VGPRs
+// with the 32-key merge unrolled: 7 waves per SIMD) but four of 8 (39 VGPRs), and with several resident the prologue (pair and
+// count look-ups, the query row) and the LDS merge of one are covered by the scans of the others (measured both)
+#define MP_WAVES 8
+#endif
+template <int W32>
+__device__ __forceinline__ void mp_load_row(const uint8_t* p, bool aligned, unsigned (&v)[W32]) {
+  if (aligned) {
+    const unsigned* p32 = reinterpret_cast<const unsigned*>(p);
+#pragma unroll
+    for (int w = 0; w < W32; ++w) v[w] = p32[w];
+  } else {
+#pragma unroll
+    for (int w = 0; w < W32; ++w)
+      v[w] = (unsigned)p[4 * w] | ((unsigned)p[4 * w + 1] << 8) | ((unsigned)p[4 * w + 2] << 16) | ((unsigned)p[4 * w + 3] << 24);
+  }
+}
+// rows [t0, t1) of one frame (wave-uniform addresses) against the lane's descriptor: the two smallest keys
+template <int W32>
+__device__ __forceinline__ void mp_scan(const unsigned (&qv)[W32], const uint8_t* rows, int pitch, bool aligned, int t0, int t1,
+                                        unsigned& b1, unsigned& b2) {
+  if (aligned) {  // (batch results: 4-byte aligned rows at pitch 64)
+    for (int t = t0; t < t1; ++t) {
+      const unsigned* tp = reinterpret_cast<const unsigned*>(rows + (long)t * pitch);
+      unsigned d = 0;
+#pragma unroll
+      for (int w = 0; w < W32; ++w) d += __popc(qv[w] ^ tp[w]);
+      const unsigned key = (d << MF_IDX_BITS) | (unsigned)t;
+      b2 = min(b2, max(b1, key));
+      b1 = min(b1, key);
+    }
+  } else {  // (a caller's set whose base, frame pitch or row pitch is not)
+    for (int t = t0; t < t1; ++t) {
+      const uint8_t* tp = rows + (long)t * pitch;
+      unsigned d = 0;
+#pragma unroll
+      for (int w = 0; w < W32; ++w) {
+        const unsigned tv = (unsigned)tp[4 * w] | ((unsigned)tp[4 * w + 1] << 8) | ((unsigned)tp[4 * w + 2] << 16) | ((unsigned)tp[4 * w + 3] << 24);
+        d += __popc(qv[w] ^ tv);
+      }
+      const unsigned key = (d << MF_IDX_BITS) | (unsigned)t;
+      b2 = min(b2, max(b1, key));
+      b1 = min(b1, key);
+    }
+  }
+}
+
+template <int W32, bool CROSS>
+__global__ void __launch_bounds__(MP_WAVES * 64) k_match_knn_pairs(const BriskDescSet Q, const BriskDescSet T, const BriskPairSpec P,
+                                                                    int pair0, int k, int rows_cap, BriskDMatch* __restrict__ out,
+                                                                    int* __restrict__ out_count, int* __restrict__ pair_rows) {
+  __shared__ unsigned part[MP_WAVES][2][64];
+  __shared__ unsigned fwd[64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int p = pair0 + blockIdx.y;
+  int a, b;
+  if (P.pairs) {
+    a = P.pairs[2 * (long)p];
+    b = P.pairs[2 * (long)p + 1];
+  } else {
+    a = P.query_first + p * P.query_step;
+    b = P.train_first + p * P.train_step;
+  }
+  const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+  if (a < 0 || a >= Q.frames || b < 0 || b >= T.frames) {  // (a bad entry of the caller's list; the arithmetic form is checked on the host)
+    if (first) pair_rows[p] = -1;
+    return;
+  }
+  const int n_a = max(0, Q.counts[(long)a * Q.count_stride]), n_b = max(0, T.counts[(long)b * T.count_stride]);
+  if (n_b >= (1 << MF_IDX_BITS) || (CROSS && n_a >= (1 << MF_IDX_BITS))) {  // (the keys hold 22 index bits)
+    if (first) pair_rows[p] = -1;
+    return;
+  }
+  if (first) pair_rows[p] = n_a;
+  const int rows = min(n_a, rows_cap);
+  if ((int)blockIdx.x * 64 >= rows) return;
+  const int q = blockIdx.x * 64 + lane;
+  BriskDMatch* orow = out + ((long)p * rows_cap + q) * k;
+  int* ocnt = out_count + (long)p * rows_cap + q;
+  if (n_b == 0) {  // nothing to match against: empty rows (the reference tops up only when some train image has rows)
+    if (wave == 0 && q < rows) *ocnt = 0;
+    return;
+  }
+  const uint8_t* qrows = Q.desc + (long)a * Q.frame_pitch;
+  const uint8_t* trows = T.desc + (long)b * T.frame_pitch;
+  const bool q_aligned = (((uintptr_t)Q.desc | (unsigned long)Q.frame_pitch | (unsigned)Q.row_pitch) & 3) == 0;
+  const bool t_aligned = (((uintptr_t)T.desc | (unsigned long)T.frame_pitch | (unsigned)T.row_pitch) & 3) == 0;
+  unsigned qv[W32];
+  mp_load_row<W32>(qrows + (long)min(q, rows - 1) * Q.row_pitch, q_aligned, qv);
+  unsigned b1 = 0xFFFFFFFFu, b2 = 0xFFFFFFFFu;
+  {
+    const int per = (n_b + MP_WAVES - 1) / MP_WAVES;
+    const int t0 = __builtin_amdgcn_readfirstlane(wave * per), t1 = min(n_b, t0 + per);
+    mp_scan<W32>(qv, trows, T.row_pitch, t_aligned, t0, t1, b1, b2);
+  }
+  part[wave][0][lane] = b1;
+  part[wave][1][lane] = b2;
+  __syncthreads();
+  unsigned m1 = 0xFFFFFFFFu, m2 = 0xFFFFFFFFu;
+  if (wave == 0) {
+#pragma unroll
+    for (int w = 0; w < MP_WAVES; ++w)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const unsigned key = part[w][i][lane];
+        m2 = min(m2, max(m1, key));
+        m1 = min(m1, key);
+      }
+  }
+  bool keep = true;
+  if (CROSS) {
+    if (wave == 0) fwd[lane] = m1;
+    __syncthreads();  // (also: wave 0 has read part[] before anybody writes it again)
+    const int t = (int)(fwd[lane] & ((1u << MF_IDX_BITS) - 1));  // (n_b >= 1: every lane has a real forward match)
+    unsigned tv[W32];
+    mp_load_row<W32>(trows + (long)t * T.row_pitch, t_aligned, tv);
+    unsigned c1 = 0xFFFFFFFFu, c2 = 0xFFFFFFFFu;
+    const int per = (n_a + MP_WAVES - 1) / MP_WAVES;
+    const int r0 = __builtin_amdgcn_readfirstlane(wave * per), r1 = min(n_a, r0 + per);
+    mp_scan<W32>(tv, qrows, Q.row_pitch, q_aligned, r0, r1, c1, c2);  // ALL rows of frame a, also those beyond rows_cap
+    part[wave][0][lane] = c1;
+    __syncthreads();
+    if (wave == 0) {
+      unsigned best = 0xFFFFFFFFu;
+#pragma unroll
+      for (int w = 0; w < MP_WAVES; ++w) best = min(best, part[w][0][lane]);
+      keep = (int)(best & ((1u << MF_IDX_BITS) - 1)) == q;
+    }
+  }
+  if (wave == 0 && q < rows) {
+    if (!keep) {
+      *ocnt = 0;
+      return;
+    }
+    BriskDMatch m;
+    m.queryIdx = q; m.imgIdx = b;
+    m.trainIdx = (int)(m1 & ((1u << MF_IDX_BITS) - 1)); m.distance = (float)(m1 >> MF_IDX_BITS);
+    orow[0] = m;
+    if (k > 1) {
+      if (m2 != 0xFFFFFFFFu) {
+        m.trainIdx = (int)(m2 & ((1u << MF_IDX_BITS) - 1)); m.distance = (float)(m2 >> MF_IDX_BITS);
+      } else {  // n_b < k: the reference's top-up entry (k_match_knn above; brute-force-matcher.cc:139-153)
+        m.trainIdx = 0; m.distance = 2147483648.0f;
+      }
+      orow[1] = m;
+    }
+    *ocnt = k;
+  }
+}
+
+template <int W32>
+static void mp_launch(const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, int k, bool cross, int rows_cap,
+                      BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s) {
+  const dim3 block(MP_WAVES * 64);
+  for (int p0 = 0; p0 < P.npairs; p0 += 65535) {  // (grid.y holds 65535)
+    const dim3 grid((rows_cap + 63) / 64, min(65535, P.npairs - p0));
+    if (cross)
+      hipLaunchKernelGGL((k_match_knn_pairs<W32, true>), grid, block, 0, s, Q, T, P, p0, k, rows_cap, out, out_count, pair_rows);
+    else
+      hipLaunchKernelGGL((k_match_knn_pairs<W32, false>), grid, block, 0, s, Q, T, P, p0, k, rows_cap, out, out_count, pair_rows);
+  }
+}
+// false: descriptor size not covered (16, 32, 48, 64 bytes are)
+bool brisk_launch_match_knn_pairs(const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, int words32, int k, bool cross,
+                                  int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s) {
+  switch (words32) {
+    case 4: mp_launch<4>(Q, T, P, k, cross, rows_cap, out, out_count, pair_rows, s); break;
+    case 8: mp_launch<8>(Q, T, P, k, cross, rows_cap, out, out_count, pair_rows, s); break;
+    case 12: mp_launch<12>(Q, T, P, k, cross, rows_cap, out, out_count, pair_rows, s); break;
+    case 16: mp_launch<16>(Q, T, P, k, cross, rows_cap, out, out_count, pair_rows, s); break;
+    default: return false;
+  }
+  return true;
+}
+
 void brisk_launch_match_dist(const uint8_t* query, int q_pitch, int q0, int nqb, const uint8_t* train, int t_pitch, int nt,
                              int words, const uint8_t* mask, long mask_pitch, uint16_t* dist, long dist_pitch,
                              hipStream_t s) {

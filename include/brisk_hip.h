@@ -383,6 +383,51 @@ int brisk_hip_match_knn_device(brisk_hip_ctx* ctx, const uint8_t* d_query, int n
                                int nt, int t_pitch, int dim_bytes, int k, brisk_hip_dmatch* d_out, int* d_out_count,
                                void* stream);
 
+/* ---- all frame pairs of a batch in one call ----------------------------------------------------------------------------
+ * The step a stream runs after detect + describe - match every frame against the previous one, left against right - with
+ * the row counts read on the device: no synchronisation, no download and no launch per pair in between.
+ * A descriptor set: `frames` frames of rows in DEVICE memory; the two sides of a pair may come from one batch, from two
+ * contexts (stereo) or from a caller's own device copy of earlier frames. */
+typedef struct brisk_hip_desc_set {
+  const uint8_t* d_desc; /* frame f's rows at d_desc + f * frame_pitch, row r at + r * row_pitch */
+  const int* d_counts;   /* rows of frame f = d_counts[f * count_stride] (device memory); fewer than 2^22 */
+  int count_stride;      /* in ints */
+  long frame_pitch;      /* bytes */
+  int row_pitch;         /* bytes, >= dim_bytes */
+  int frames;
+} brisk_hip_desc_set;
+/* Fills *set with the DESCRIBED results of the context's last batch (the rows and counts brisk_hip_batch_results returns);
+ * *dim_bytes (may be NULL) = the descriptor size of the pattern that batch used.  BRISK_HIP_ERR_ARG if the context's last
+ * call described no batch.  LIFETIME: the result buffers are overwritten by the context's next batch (and may move when a
+ * later call grows them), so the set is valid until then; on one stream, match-then-next-batch is safe by stream order.
+ * To match across batches keep a device copy of the frames wanted and describe it with a set of your own. */
+int brisk_hip_batch_desc_set(brisk_hip_ctx* ctx, brisk_hip_desc_set* set, int* dim_bytes);
+/* The pairs: pair p = (query frame query_first + p * query_step, train frame train_first + p * train_step) - frame to
+ * previous frame (1, 1, 0, 1), interleaved stereo (0, 2, 1, 2), two sets side by side (0, 1, 0, 1), all against a
+ * keyframe (train_step = 0) - unless d_pairs is non-NULL: a DEVICE array of npairs x {query frame, train frame}. */
+typedef struct brisk_hip_pair_spec {
+  int npairs;
+  int query_first, query_step;
+  int train_first, train_step;
+  const int* d_pairs;
+} brisk_hip_pair_spec;
+/* Pair p = (a, b): rows [p][q] of d_out / d_out_count are what brisk_hip_match_knn returns for query = the n_a rows of
+ * frame a, one train image = the n_b rows of frame b, no masks, the same k: order (distance, train index), including the
+ * reference's top-up when 0 < n_b < k and count 0 when n_b == 0; queryIdx = row within frame a, trainIdx = row within
+ * frame b, imgIdx = b.  d_pair_rows[p] = n_a, the TRUE count: only rows q < min(n_a, rows_cap) are written, everything else
+ * of d_out [npairs][rows_cap][k] and d_out_count [npairs][rows_cap] is left untouched (a cut pair shows as
+ * d_pair_rows[p] > rows_cap; the entries of a row whose count is 0 are not written either).
+ * cross_check != 0 (k == 1 only): row q's match t is kept only if the best match of row t of frame b among ALL rows of
+ * frame a - same distance, same (distance, index) order - is q; otherwise d_out_count[p][q] = 0.
+ * A frame outside its set: BRISK_HIP_ERR_ARG for the arithmetic form (checked before anything is launched); for an entry
+ * of d_pairs, d_pair_rows[p] = -1 and no rows (also for a frame whose count is 2^22 or more).
+ * dim_bytes 16, 32, 48 or 64, else BRISK_HIP_ERR_UNSUPPORTED (brisk_hip_match_knn_device remains for other sizes, k > 2
+ * is brisk_hip_match_knn's); npairs == 0 is BRISK_HIP_OK.  Asynchronous on `stream` (hipStream_t, NULL = the context's
+ * stream): issued on the batch's stream right after brisk_hip_detect_describe_batch it needs no synchronisation in between. */
+int brisk_hip_match_knn_pairs_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                     const brisk_hip_pair_spec* pairs, int dim_bytes, int k, int cross_check, int rows_cap,
+                                     brisk_hip_dmatch* d_out, int* d_out_count, int* d_pair_rows, void* stream);
+
 /* ---- per-stage timing: HIP events recorded on the launch stream around every kernel of the batch path ---- */
 int brisk_hip_profile_enable(brisk_hip_ctx* ctx, int enable);       /* resets the accumulated calls */
 int brisk_hip_profile_stages(void);                                 /* number of stages */

@@ -1,0 +1,167 @@
+#!/usr/bin/env python3
+"""What matching adds to the bench line's stream: bench.py's workload (1080p App.-C frames, threshold 80, 4 octaves, 512 frames
+per batch, frames resident in HBM), every frame matched against the previous one, k = 2.  In ONE process, after warm-up,
+alternating windows that each end in a synchronise:
+  A  detect_describe_batch alone
+  B  detect_describe_batch + match_knn_pairs on the same stream (brisk_hip_match_knn_pairs_device: one launch, counts read on
+     the device)
+  C  detect_describe_batch, synchronise, download the counts, one brisk_hip_match_knn_device call per pair - the only way
+     there was before the pair call (that entry point is unchanged)
+and writes profiles/match_pairs.json: frames/s of A, B, C, the matching cost per batch (B - A, C - A), the spread over the
+repeats, the kernel revision and whether B's and C's rows are identical.
+Usage: python tools/bench_match_pairs.py [--repeats 5] [--window 0.4] [--rows-cap 2048] [--out FILE]
+       --stats-pass: warm-up + a few B iterations only, nothing written (the run a `rocprofv3 --kernel-trace --stats` pass wraps;
+       its kernel statistics are kept as profiles/match_pairs_kernel_stats.csv)"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+import torch
+import ethzasl_brisk_amd as B
+from bench import gen_frames, W, H, OCTAVES, THRESHOLD   # the bench line's frame generator and workload constants
+import synth
+
+
+class DeviceInts:
+    """a device pointer as a flat int32 array torch can wrap (the counters of the last batch)"""
+
+    def __init__(self, ptr, n):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": "<i4", "data": (ptr, False), "version": 2}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=512)
+    ap.add_argument("--distinct", type=int, default=64)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--window", type=float, default=0.4, help="seconds per window (repeats x window >= 1 s per variant)")
+    ap.add_argument("--rows-cap", type=int, default=2048, help="rows per pair in the match buffers (the stream has ~1k keypoints per frame)")
+    ap.add_argument("--k", type=int, default=2)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "match_pairs.json"))
+    ap.add_argument("--stats-pass", action="store_true")
+    a = ap.parse_args()
+
+    n, k, cap = a.batch, a.k, a.rows_cap
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    nd = min(a.distinct, n)
+    ring = torch.from_numpy(np.stack(gen_frames(synth.frame_1080p, list(range(nd))))).to(dev)
+    frames = ring[torch.arange(n, device=dev) % nd].contiguous()
+    del ring
+    ctx = B.Context(0)
+    ext = B.BriskDescriptorExtractor(context=ctx)
+    work = torch.cuda.Stream(device=dev)
+    torch.cuda.set_stream(work)
+    st = work.cuda_stream
+    spec = B.PairSpec(n - 1, 1, 1, 0, 1, None)   # frame to previous frame
+    outs = {v: (torch.zeros((n - 1, cap, k, 4), dtype=torch.int32, device=dev), torch.zeros((n - 1, cap), dtype=torch.int32, device=dev),
+                torch.zeros(n - 1, dtype=torch.int32, device=dev)) for v in "BC"}
+
+    def batch():
+        ctx.detect_describe_batch(ext, frames.data_ptr(), n, W, H, W * H, W, THRESHOLD, OCTAVES, st)
+
+    def run_a():
+        batch()
+
+    def run_b():
+        batch()
+        dset, dim = ctx.batch_desc_set()
+        ctx.match_knn_pairs(dset, dset, spec, k, rows_cap=cap, stream=st, dim_bytes=dim, out=outs["B"])
+
+    vp = C.c_void_p
+
+    def run_c():
+        batch()
+        torch.cuda.synchronize()
+        d_n, d_desc, cstride, kcap, pitch = vp(), vp(), C.c_int(), C.c_int(), C.c_int()
+        ctx.check(ctx._L.brisk_hip_batch_results(ctx._h, None, C.byref(d_n), C.byref(cstride), None, None, C.byref(d_desc), C.byref(kcap),
+                                                 C.byref(pitch)))
+        ints = cstride.value // 4
+        counts = torch.as_tensor(DeviceInts(d_n.value, (n - 1) * ints + 1), device=dev)[::ints].cpu().numpy()
+        m, cnt, rows = outs["C"]
+        fp = kcap.value * pitch.value
+        L, h, fn = ctx._L, ctx._h, ctx._L.brisk_hip_match_knn_device
+        for p in range(n - 1):
+            nq, nt = min(int(counts[p + 1]), cap), int(counts[p])
+            ctx.check(fn(h, d_desc.value + (p + 1) * fp, nq, pitch.value, d_desc.value + p * fp, nt, pitch.value, 48, k,
+                         m.data_ptr() + p * cap * k * 16, cnt.data_ptr() + p * cap * 4, st))
+        rows.copy_(torch.from_numpy(counts[1:].copy()), non_blocking=False)
+
+    runs = {"A": run_a, "B": run_b, "C": run_c}
+    for v in "ABCAB":                       # warm-up: buffers sized, the integral format settled on the stream's density
+        runs[v]()
+        torch.cuda.synchronize()
+    if a.stats_pass:
+        for _ in range(8):
+            run_b()
+        torch.cuda.synchronize()
+        return
+
+    # B's rows against C's: the same matches, row for row (imgIdx aside: the pair call writes the train frame's index, the
+    # one-pair call knows of one train image only and writes 0)
+    for v in "BC":
+        for t in outs[v]:
+            t.zero_()
+        runs[v]()
+        torch.cuda.synchronize()
+    (mb, cb, rb), (mc, cc, rc) = outs["B"], outs["C"]
+    valid = torch.arange(cap, device=dev)[None, :] < rb[:, None]
+    sel = valid[:, :, None] & (torch.arange(k, device=dev)[None, None, :] < cb[:, :, None])   # the entries a row's count covers
+    pidx = torch.arange(n - 1, device=dev, dtype=torch.int32)[:, None, None].expand(-1, cap, k)
+    identical = bool(torch.equal(rb, rc) and torch.equal(cb[valid], cc[valid]) and
+                     torch.equal(mb[sel][:, [0, 1, 3]], mc[sel][:, [0, 1, 3]]) and torch.equal(mb[..., 2][sel], pidx[sel]))
+    rows_host = rb.cpu().numpy()
+
+    fps = {v: [] for v in "ABC"}
+    for _ in range(a.repeats):
+        for v in "ABC":
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            calls = 0
+            while True:
+                runs[v]()
+                calls += 1
+                if time.perf_counter() - t0 >= a.window:
+                    break
+            torch.cuda.synchronize()
+            fps[v].append(calls * n / (time.perf_counter() - t0))
+
+    med = {v: float(np.median(fps[v])) for v in "ABC"}
+    ms = {v: 1e3 * n / med[v] for v in "ABC"}            # per batch
+    spread = {v: (max(fps[v]) - min(fps[v])) / med[v] for v in "ABC"}
+    res = {
+        "workload": "bench.py's stream: %dx%d, threshold %d, %d octaves, %d frames per batch (%d distinct) in HBM; frame-to-previous-frame, "
+                    "k = %d, rows_cap %d" % (W, H, THRESHOLD, OCTAVES, n, nd, k, cap),
+        "kernel_revision": ctx.kernel_revision(),
+        "device": torch.cuda.get_device_name(0),
+        "windows": {"repeats": a.repeats, "seconds_each": a.window, "order": "A, B, C alternating; every window ends in a synchronise"},
+        "frames_per_s": {v: round(med[v], 1) for v in "ABC"},
+        "frames_per_s_all": {v: [round(x, 1) for x in fps[v]] for v in "ABC"},
+        "spread_rel": {v: round(spread[v], 4) for v in "ABC"},
+        "ms_per_batch": {v: round(ms[v], 4) for v in "ABC"},
+        "matching_ms_per_batch": {"B_minus_A": round(ms["B"] - ms["A"], 4), "C_minus_A": round(ms["C"] - ms["A"], 4)},
+        "B_over_C_frames_per_s": round(med["B"] / med["C"], 4),
+        "matching_share_of_chunk_B": round((ms["B"] - ms["A"]) / ms["A"], 4),
+        "rows_identical_B_C": identical,
+        "rows_per_pair": {"mean": round(float(rows_host.mean()), 1), "max": int(rows_host.max()), "cut_pairs": int((rows_host > cap).sum())},
+        "legend": {"A": "detect_describe_batch", "B": "A + brisk_hip_match_knn_pairs_device on the same stream",
+                   "C": "A, synchronise, counts to the host, one brisk_hip_match_knn_device call per pair"},
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+    ext.close()
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
