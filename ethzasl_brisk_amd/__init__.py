@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "brisk_hip_pool_create", "brisk_hip_pool_destroy", "brisk_hip_pool_last_error", "brisk_hip_pool_detect", "brisk_hip_pool_describe", "brisk_hip_pool_stats",
     "brisk_hip_batch_download_all", "brisk_hip_batch_download_wait", "brisk_hip_detect_describe_batch_host_results",
     "brisk_hip_batch_desc_set", "brisk_hip_match_knn_pairs_device",
+    "brisk_hip_match_radius_pairs_device", "brisk_hip_match_radius_device",
 ]
 # every symbol include/brisk_hip_debug.h declares: test / tuning builds (BRISK_HIP_TUNING) only
 DEBUG_SYMBOLS = [
@@ -195,6 +196,9 @@ def load_library():
     L.brisk_hip_batch_desc_set.argtypes = [vp, C.POINTER(DescSet), ip]
     L.brisk_hip_match_knn_pairs_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(PairSpec), C.c_int, C.c_int,
                                                    C.c_int, C.c_int, vp, vp, vp, vp]
+    L.brisk_hip_match_radius_pairs_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(PairSpec), C.c_int, C.c_float,
+                                                      C.c_int, C.c_int, vp, vp, vp, vp]
+    L.brisk_hip_match_radius_device.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp]
     L.brisk_hip_reserve.argtypes = [vp, C.c_int, C.c_int]
     L.brisk_hip_detect_uniform.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
                                            C.c_double, C.c_int, vp, C.c_int, ip]
@@ -501,6 +505,46 @@ class Context:
         hm = m.cpu().numpy().view(DMATCH).reshape(n, rows_cap, max(k, 1))
         hc, hr = cnt.cpu().numpy(), rows.cpu().numpy()
         return [[hm[p, q, :hc[p, q]].copy() for q in range(min(max(int(hr[p]), 0), rows_cap))] for p in range(n)]
+
+    def match_radius_pairs(self, query, train, pairs, max_distance, cap_per_query, rows_cap=None, stream=None, dim_bytes=None, out=None,
+                           download=False):
+        """brisk_hip_match_radius_pairs_device; the conventions of match_knn_pairs.  Returns the device tensors (matches
+        [npairs, rows_cap, cap_per_query, 4] int32 - DMATCH records -, counts [npairs, rows_cap] = matches FOUND, pair_rows
+        [npairs]) or writes the triple `out`.  Asynchronous unless download=True: that synchronises and returns (rows, counts):
+        per pair the list of per-query DMATCH arrays cut to min(count, cap_per_query), and per pair the counts of those rows."""
+        import torch
+        if dim_bytes is None:
+            dim_bytes = self.batch_desc_set()[1]
+        if rows_cap is None:
+            cap = C.c_int()
+            self.check(self._L.brisk_hip_batch_results(self._h, None, None, None, None, None, None, C.byref(cap), None))
+            rows_cap = cap.value
+        n, cpq = pairs.npairs, int(cap_per_query)
+        if out is None:
+            dev = "cuda:%d" % self.device
+            out = (torch.empty((max(n, 0), max(rows_cap, 0), max(cpq, 1), 4), dtype=torch.int32, device=dev),
+                   torch.empty((max(n, 0), max(rows_cap, 0)), dtype=torch.int32, device=dev),
+                   torch.empty(max(n, 0), dtype=torch.int32, device=dev))
+        m, cnt, rows = out
+        self.check(self._L.brisk_hip_match_radius_pairs_device(self._h, C.byref(query), C.byref(train), C.byref(pairs), int(dim_bytes),
+                                                               float(max_distance), cpq, int(rows_cap), m.data_ptr(), cnt.data_ptr(),
+                                                               rows.data_ptr(), C.c_void_p(stream) if stream else None))
+        if not download:
+            return out
+        torch.cuda.synchronize(self.device)
+        hm = m.cpu().numpy().view(DMATCH).reshape(n, rows_cap, cpq)
+        hc, hr = cnt.cpu().numpy(), rows.cpu().numpy()
+        nrows = [min(max(int(hr[p]), 0), rows_cap) for p in range(n)]
+        return ([[hm[p, q, :min(int(hc[p, q]), cpq)].copy() for q in range(nrows[p])] for p in range(n)],
+                [hc[p, :nrows[p]].copy() for p in range(n)])
+
+    def match_radius_device(self, d_query, nq, q_pitch, d_train, nt, t_pitch, dim_bytes, max_distance, cap_per_query, d_out, d_out_count,
+                            stream=None):
+        """brisk_hip_match_radius_device: device pointers (ints), host counts; d_out [nq][cap_per_query] DMATCH records, d_out_count
+        [nq] = matches found.  Asynchronous on `stream` (None = the context's)."""
+        self.check(self._L.brisk_hip_match_radius_device(self._h, d_query, int(nq), int(q_pitch), d_train, int(nt), int(t_pitch), int(dim_bytes),
+                                                         float(max_distance), int(cap_per_query), d_out, d_out_count,
+                                                         C.c_void_p(stream) if stream else None))
 
 
 class Pool:

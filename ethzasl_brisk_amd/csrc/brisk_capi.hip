@@ -94,7 +94,7 @@ struct brisk_hip_ctx {
   int spec_nkp = 1024;        // keypoints the next detect call is expected to return (sizes the publishing kernel's grid)
   double density_mpx = 0.0;  // megapixels per frame of the batch the word belongs to
   DeviceBuf d_img16[3];  // scratch of the 16-bit image functions (source, destination, row sums)
-  DeviceBuf d_match;     // workspace of brisk_hip_match_knn_device
+  DeviceBuf d_match;     // workspace of brisk_hip_match_knn_device / brisk_hip_match_radius_device
   // Calls share one workspace but may be issued on different streams: every call that uses the workspace first makes
   // its stream wait for the end of the previous one (event recorded at the end of each call).
   hipEvent_t done_ev = nullptr;
@@ -2025,6 +2025,77 @@ int brisk_hip_match_knn_pairs_device(brisk_hip_ctx* ctx, const brisk_hip_desc_se
     return fail(ctx, BRISK_HIP_ERR_UNSUPPORTED, "match_pairs: descriptor size not covered");
   HIPCHK(ctx, hipGetLastError());
   if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
+  return BRISK_HIP_OK;
+}
+
+int brisk_hip_match_radius_pairs_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                        const brisk_hip_pair_spec* pairs, int dim_bytes, float max_distance, int cap_per_query,
+                                        int rows_cap, brisk_hip_dmatch* d_out, int* d_out_count, int* d_pair_rows, void* stream) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (!pairs || pairs->npairs < 0) return fail(ctx, BRISK_HIP_ERR_ARG, "match_radius_pairs: bad argument");
+  if (cap_per_query < 1) return fail(ctx, BRISK_HIP_ERR_ARG, "match_radius_pairs: cap_per_query must be at least 1");
+  if (dim_bytes != 16 && dim_bytes != 32 && dim_bytes != 48 && dim_bytes != 64)
+    return fail(ctx, BRISK_HIP_ERR_UNSUPPORTED, "match_radius_pairs: descriptor size must be 16, 32, 48 or 64 bytes (brisk_hip_match_radius_device for others)");
+  const int np = pairs->npairs;
+  if (np == 0) return BRISK_HIP_OK;
+  if (!query || !train) return fail(ctx, BRISK_HIP_ERR_ARG, "match_radius_pairs: null descriptor set");
+  for (const brisk_hip_desc_set* s : {query, train})
+    if (const char* msg = match_pairs_check_set(s, dim_bytes)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
+  if (rows_cap < 1 || !d_out || !d_out_count || !d_pair_rows) return fail(ctx, BRISK_HIP_ERR_ARG, "match_radius_pairs: bad output argument");
+  if (!pairs->d_pairs) {  // (a list on the device is checked there: d_pair_rows = -1)
+    const long q0 = pairs->query_first, q1 = q0 + (long)(np - 1) * pairs->query_step;
+    const long t0 = pairs->train_first, t1 = t0 + (long)(np - 1) * pairs->train_step;
+    if (q0 < 0 || q0 >= query->frames || q1 < 0 || q1 >= query->frames || t0 < 0 || t0 >= train->frames || t1 < 0 || t1 >= train->frames)
+      return fail(ctx, BRISK_HIP_ERR_ARG, "match_radius_pairs: a pair names a frame outside its set");
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  // (ordered behind the batch that wrote the sets and before the next one, as brisk_hip_match_knn_pairs_device)
+  if (workspace_acquire(ctx, st)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
+  WorkspaceGuard guard(ctx, st);
+  const BriskDescSet Q{query->d_desc, query->d_counts, query->count_stride, query->frame_pitch, query->row_pitch, query->frames};
+  const BriskDescSet T{train->d_desc, train->d_counts, train->count_stride, train->frame_pitch, train->row_pitch, train->frames};
+  const BriskPairSpec P{np, pairs->query_first, pairs->query_step, pairs->train_first, pairs->train_step, pairs->d_pairs};
+  if (!brisk_launch_match_radius_pairs(Q, T, P, dim_bytes / 4, max_distance, cap_per_query, rows_cap, reinterpret_cast<BriskDMatch*>(d_out),
+                                       d_out_count, d_pair_rows, st))
+    return fail(ctx, BRISK_HIP_ERR_UNSUPPORTED, "match_radius_pairs: descriptor size not covered");
+  HIPCHK(ctx, hipGetLastError());
+  if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
+  return BRISK_HIP_OK;
+}
+
+int brisk_hip_match_radius_device(brisk_hip_ctx* ctx, const uint8_t* d_query, int nq, int q_pitch, const uint8_t* d_train, int nt,
+                                  int t_pitch, int dim_bytes, float max_distance, int cap_per_query, brisk_hip_dmatch* d_out,
+                                  int* d_out_count, void* stream) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (nq < 0 || nt < 0 || cap_per_query < 1 || !d_out_count || (nq > 0 && (!d_query || !d_out)) || (nt > 0 && !d_train))
+    return fail(ctx, BRISK_HIP_ERR_ARG, "match: bad argument");
+  if (dim_bytes < 16 || dim_bytes > 224) return fail(ctx, BRISK_HIP_ERR_UNSUPPORTED, "match: descriptor size must be 16..224 bytes");
+  if (q_pitch < dim_bytes || (nt > 0 && t_pitch < dim_bytes)) return fail(ctx, BRISK_HIP_ERR_ARG, "match: pitch smaller than the descriptor");
+  if (nq == 0) return BRISK_HIP_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const int dim16 = (dim_bytes / 16) * 16;
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  if (dim16 <= 64 && brisk_launch_match_radius_fused(d_query, q_pitch, nq, d_train, t_pitch, nt, dim16 / 4, max_distance, cap_per_query,
+                                                     reinterpret_cast<BriskDMatch*>(d_out), d_out_count, st)) {
+    HIPCHK(ctx, hipGetLastError());
+    return BRISK_HIP_OK;
+  }
+  const long dist_pitch = ((long)nt + 63) / 64 * 64 + 64;
+  const size_t need = (size_t)nq * dist_pitch * 2;
+  if (workspace_acquire(ctx, st)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
+  if (ctx->d_match.cap < need) {  // workspace kept by the context (the call is asynchronous)
+    HIPCHK(ctx, hipDeviceSynchronize());
+    HIPCHK(ctx, ctx->d_match.grow(need));
+  }
+  uint16_t* d_dist = ctx->d_match.as<uint16_t>();
+  brisk_launch_match_dist(d_query, q_pitch, 0, nq, d_train, t_pitch, nt, dim16 / 8, nullptr, 0, d_dist, dist_pitch, st);
+  brisk_launch_match_radius(d_dist, dist_pitch, 0, nq, nt, nullptr, 1, nullptr, max_distance, cap_per_query,
+                            reinterpret_cast<BriskDMatch*>(d_out), d_out_count, dim16, st);
+  HIPCHK(ctx, hipGetLastError());
+  if (workspace_release(ctx, st)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
   return BRISK_HIP_OK;
 }
 

@@ -165,6 +165,13 @@ struct BriskPairSpec {
 bool brisk_launch_match_knn_pairs(const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, int words32, int k, bool cross,
                                   int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s);
 
+// radius matching in the same forms (cap_per_query entries per row, the count = matches found): the pairs of a batch, and one
+// query set against one train set with host counts (false = not covered, use brisk_launch_match_dist + brisk_launch_match_radius)
+bool brisk_launch_match_radius_pairs(const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, int words32, float max_distance,
+                                     int cap, int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s);
+bool brisk_launch_match_radius_fused(const uint8_t* query, int q_pitch, int nq, const uint8_t* train, int t_pitch, int nt, int words32,
+                                     float max_distance, int cap, BriskDMatch* out, int* out_count, hipStream_t s);
+
 // ---- uniformity enforcement / keypoint bucketing (brisk_uniformity.hip): optional post-filters of the detector's keypoints ----
 void brisk_launch_bucketing(BriskKeyPoint* kp, BriskFrameCounters* counters, int* order, BriskKeyPoint* tmp, int kp_cap, int rows,
                             int cols, int nbu, int nbv, int max_keypoints, int nframes, hipStream_t s);

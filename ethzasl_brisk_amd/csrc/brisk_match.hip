@@ -487,6 +487,260 @@ bool brisk_launch_match_knn_pairs(const BriskDescSet& Q, const BriskDescSet& T, 
   return true;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Radius matching in k_match_knn_pairs' shape (brisk_hip_match_radius_pairs_device / brisk_hip_match_radius_device): 64 queries
+// per workgroup, one per lane with the descriptor in registers, MP_WAVES waves each scanning a slice of the train rows through
+// wave-uniform loads.  No distance matrix: a hit ((float)d < max_distance, brute-force-matcher.cc:203-207) bumps its query's
+// counter in LDS and, while the query's short LDS list has room, drops its packed key (d << 22 | t) there.  Keys are unique per
+// train row, so the order of collection does not matter:
+//   sparse rows (count <= MRP_LIST): MP_WAVES threads per query rank the keys of the list against each other and store those
+//       of rank < cap at their rank - (distance, trainIdx) order;
+//   dense rows (the list overflowed): one wave per such query runs k_match_radius' algorithm with the distances recomputed on
+//       the fly (lane = train row, the query wave-uniform): histogram over the distances below the threshold, exclusive prefix,
+//       stable placement in train order.  Second phase of the same workgroup: nothing between the phases leaves the CU.
+// The counter holds the number FOUND in both cases.
+// ------------------------------------------------------------------------------------------------
+#ifndef MRP_LIST
+#define MRP_LIST 32  // keys per query held in LDS (8 KiB per workgroup); a row with more hits takes the dense path
+#endif
+#define MRP_BINS 513                    // distances 0 ... 512 (descriptors of at most 64 bytes)
+#define MRP_PER ((MRP_BINS + 63) / 64)  // bins per lane in the prefix
+
+template <int W32, bool ALIGNED>
+__device__ __forceinline__ unsigned mrp_dist(const unsigned (&qv)[W32], const uint8_t* tp) {
+  unsigned d = 0;
+  if (ALIGNED) {
+    const unsigned* tp32 = reinterpret_cast<const unsigned*>(tp);
+#pragma unroll
+    for (int w = 0; w < W32; ++w) d += __popc(qv[w] ^ tp32[w]);
+  } else {
+#pragma unroll
+    for (int w = 0; w < W32; ++w) {
+      const unsigned tv = (unsigned)tp[4 * w] | ((unsigned)tp[4 * w + 1] << 8) | ((unsigned)tp[4 * w + 2] << 16) | ((unsigned)tp[4 * w + 3] << 24);
+      d += __popc(qv[w] ^ tv);
+    }
+  }
+  return d;
+}
+// rows [t0, t1) of one frame (wave-uniform addresses) against the lane's descriptor: hits (d < thr) into the lane's counter and list
+template <int W32, bool ALIGNED>
+__device__ __forceinline__ void mrp_scan(const unsigned (&qv)[W32], const uint8_t* rows, int pitch, int t0, int t1, unsigned thr,
+                                         int* cnt, unsigned (*list)[64], int lane) {
+  for (int t = t0; t < t1; ++t) {
+    const unsigned d = mrp_dist<W32, ALIGNED>(qv, rows + (long)t * pitch);
+    if (d < thr) {
+      const int slot = atomicAdd(&cnt[lane], 1);
+      if (slot < MRP_LIST) list[slot][lane] = (d << MF_IDX_BITS) | (unsigned)t;
+    }
+  }
+}
+// one wave, one query with more than MRP_LIST hits.  bins: thr + 1 ints of this wave's own
+template <int W32, bool ALIGNED>
+__device__ __forceinline__ void mrp_dense(int* bins, const unsigned (&uq)[W32], const uint8_t* trows, int t_pitch, int n_b, unsigned thr,
+                                          int cap, int lane, int q, int img, BriskDMatch* __restrict__ orow) {
+  for (int b = lane; b <= (int)thr; b += 64) bins[b] = 0;
+  __builtin_amdgcn_s_waitcnt(0);
+  __builtin_amdgcn_wave_barrier();
+  for (int t = lane; t < n_b; t += 64) {
+    const unsigned d = mrp_dist<W32, ALIGNED>(uq, trows + (long)t * t_pitch);
+    if (d < thr) atomicAdd(&bins[d], 1);
+  }
+  __builtin_amdgcn_s_waitcnt(0);
+  __builtin_amdgcn_wave_barrier();
+  {  // exclusive prefix over the thr (<= 513) bins: MRP_PER consecutive bins per lane, a scan of the lane sums in between
+    int loc[MRP_PER], sum = 0;
+#pragma unroll
+    for (int i = 0; i < MRP_PER; ++i) {
+      const int b = lane * MRP_PER + i;
+      loc[i] = b < (int)thr ? bins[b] : 0;
+      sum += loc[i];
+    }
+    int incl = sum;
+    for (int off = 1; off < 64; off <<= 1) {
+      const int o = __shfl_up(incl, off, 64);
+      if (lane >= off) incl += o;
+    }
+    int acc = incl - sum;
+#pragma unroll
+    for (int i = 0; i < MRP_PER; ++i) {
+      const int b = lane * MRP_PER + i;
+      if (b < (int)thr) bins[b] = acc;
+      acc += loc[i];
+    }
+  }
+  __builtin_amdgcn_s_waitcnt(0);
+  __builtin_amdgcn_wave_barrier();
+  // stable placement (k_match_radius): chunks of 64 train rows in order; inside a chunk equal distances keep lane order.  A bin's
+  // base only grows: a hit whose bin has reached cap is never stored and takes no part
+  for (int t0 = 0; t0 < n_b; t0 += 64) {
+    const int t = t0 + lane;
+    unsigned d = thr;
+    if (t < n_b) d = mrp_dist<W32, ALIGNED>(uq, trows + (long)t * t_pitch);
+    const bool hit = d < thr && bins[d] < cap;
+    unsigned long long todo = __ballot(hit);
+    while (todo) {
+      const int leader = __ffsll((long long)todo) - 1;
+      const unsigned dsel = __shfl(d, leader, 64);
+      const unsigned long long same = __ballot(hit && d == dsel);
+      const int base = bins[dsel];
+      if (hit && d == dsel) {
+        const int pos = base + __popcll(same & ((1ull << lane) - 1ull));
+        if (pos < cap) {
+          BriskDMatch m;
+          m.queryIdx = q; m.trainIdx = t; m.imgIdx = img; m.distance = (float)d;
+          orow[pos] = m;
+        }
+      }
+      __builtin_amdgcn_wave_barrier();
+      if (lane == leader) bins[dsel] = base + __popcll(same);
+      __builtin_amdgcn_s_waitcnt(0);
+      __builtin_amdgcn_wave_barrier();
+      todo &= ~same;
+    }
+  }
+}
+
+// the workgroup's 64 query rows [blockIdx.x * 64, ...) of `rows` against the n_b train rows; out / out_count: row 0 of this query set
+template <int W32>
+__device__ __forceinline__ void mrp_body(const uint8_t* qrows, int q_pitch, bool q_aligned, int rows, const uint8_t* trows, int t_pitch,
+                                         bool t_aligned, int n_b, float max_distance, int cap, int img, BriskDMatch* __restrict__ out,
+                                         int* __restrict__ out_count) {
+  __shared__ int cnt[64];
+  __shared__ unsigned list[MRP_LIST][64];
+  __shared__ int bins[MP_WAVES][MRP_BINS + 3];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int q = blockIdx.x * 64 + lane;
+  // d is an integer: (float)d < max_distance <=> d < ceil(max_distance); nothing hits for max_distance <= 0 or NaN, and no
+  // distance exceeds 32 * W32
+  const unsigned thr = max_distance > 0.f ? (unsigned)fminf(ceilf(max_distance), (float)(32 * W32 + 1)) : 0u;
+  if (n_b == 0 || thr == 0) {  // (radius matching has no top-up entry)
+    if (wave == 0 && q < rows) out_count[q] = 0;
+    return;
+  }
+  if (wave == 0) cnt[lane] = 0;
+  __syncthreads();
+  {
+    unsigned qv[W32];
+    mp_load_row<W32>(qrows + (long)min(q, rows - 1) * q_pitch, q_aligned, qv);
+    const unsigned thr_lane = q < rows ? thr : 0u;  // (the lanes behind the last row collect nothing)
+    const int per = (n_b + MP_WAVES - 1) / MP_WAVES;
+    const int t0 = wave * per, t1 = min(n_b, t0 + per);
+    if (t_aligned) mrp_scan<W32, true>(qv, trows, t_pitch, t0, t1, thr_lane, cnt, list, lane);
+    else mrp_scan<W32, false>(qv, trows, t_pitch, t0, t1, thr_lane, cnt, list, lane);
+  }
+  __syncthreads();
+  {  // counts of all rows; sparse rows: MP_WAVES threads per query, each ranks every MP_WAVES-th key of the list
+    const int ql = threadIdx.x / MP_WAVES, sub = threadIdx.x % MP_WAVES;
+    const int qq = blockIdx.x * 64 + ql;
+    if (qq < rows) {
+      const int c = cnt[ql];
+      if (sub == 0) out_count[qq] = c;
+      if (c <= MRP_LIST) {
+        BriskDMatch* orow = out + (long)qq * cap;
+        for (int j = sub; j < c; j += MP_WAVES) {
+          const unsigned key = list[j][ql];
+          int rank = 0;
+          for (int i = 0; i < c; ++i) rank += list[i][ql] < key ? 1 : 0;
+          if (rank < cap) {
+            BriskDMatch m;
+            m.queryIdx = qq; m.trainIdx = (int)(key & ((1u << MF_IDX_BITS) - 1)); m.imgIdx = img; m.distance = (float)(key >> MF_IDX_BITS);
+            orow[rank] = m;
+          }
+        }
+      }
+    }
+  }
+  for (int ql = wave; ql < 64; ql += MP_WAVES) {  // dense rows: one wave each
+    const int qq = blockIdx.x * 64 + ql;
+    if (qq >= rows) break;
+    if (cnt[ql] <= MRP_LIST) continue;
+    unsigned uq[W32];
+    mp_load_row<W32>(qrows + (long)qq * q_pitch, q_aligned, uq);
+    if (t_aligned) mrp_dense<W32, true>(bins[wave], uq, trows, t_pitch, n_b, thr, cap, lane, qq, img, out + (long)qq * cap);
+    else mrp_dense<W32, false>(bins[wave], uq, trows, t_pitch, n_b, thr, cap, lane, qq, img, out + (long)qq * cap);
+  }
+}
+
+// grid (ceil(rows_cap / 64), pairs): pair and counts resolved as k_match_knn_pairs does
+template <int W32>
+__global__ void __launch_bounds__(MP_WAVES * 64) k_match_radius_pairs(const BriskDescSet Q, const BriskDescSet T, const BriskPairSpec P,
+                                                                       int pair0, float max_distance, int cap, int rows_cap,
+                                                                       BriskDMatch* __restrict__ out, int* __restrict__ out_count,
+                                                                       int* __restrict__ pair_rows) {
+  const int p = pair0 + blockIdx.y;
+  int a, b;
+  if (P.pairs) {
+    a = P.pairs[2 * (long)p];
+    b = P.pairs[2 * (long)p + 1];
+  } else {
+    a = P.query_first + p * P.query_step;
+    b = P.train_first + p * P.train_step;
+  }
+  const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+  if (a < 0 || a >= Q.frames || b < 0 || b >= T.frames) {  // (a bad entry of the caller's list; the arithmetic form is checked on the host)
+    if (first) pair_rows[p] = -1;
+    return;
+  }
+  const int n_a = max(0, Q.counts[(long)a * Q.count_stride]), n_b = max(0, T.counts[(long)b * T.count_stride]);
+  if (n_b >= (1 << MF_IDX_BITS)) {  // (the keys hold 22 index bits)
+    if (first) pair_rows[p] = -1;
+    return;
+  }
+  if (first) pair_rows[p] = n_a;
+  const int rows = min(n_a, rows_cap);
+  if ((int)blockIdx.x * 64 >= rows) return;
+  const bool q_aligned = (((uintptr_t)Q.desc | (unsigned long)Q.frame_pitch | (unsigned)Q.row_pitch) & 3) == 0;
+  const bool t_aligned = (((uintptr_t)T.desc | (unsigned long)T.frame_pitch | (unsigned)T.row_pitch) & 3) == 0;
+  mrp_body<W32>(Q.desc + (long)a * Q.frame_pitch, Q.row_pitch, q_aligned, rows, T.desc + (long)b * T.frame_pitch, T.row_pitch, t_aligned,
+                n_b, max_distance, cap, b, out + (long)p * rows_cap * cap, out_count + (long)p * rows_cap);
+}
+
+// one query set against one train set, counts from the host (brisk_hip_match_radius_device); grid ceil(nq / 64)
+template <int W32>
+__global__ void __launch_bounds__(MP_WAVES * 64) k_match_radius_pairs_one(const uint8_t* __restrict__ query, int q_pitch, int nq,
+                                                                           const uint8_t* __restrict__ train, int t_pitch, int nt,
+                                                                           float max_distance, int cap, BriskDMatch* __restrict__ out,
+                                                                           int* __restrict__ out_count) {
+  const bool q_aligned = (((uintptr_t)query | (unsigned)q_pitch) & 3) == 0, t_aligned = (((uintptr_t)train | (unsigned)t_pitch) & 3) == 0;
+  mrp_body<W32>(query, q_pitch, q_aligned, nq, train, t_pitch, t_aligned, nt, max_distance, cap, 0, out, out_count);
+}
+
+template <int W32>
+static void mrp_launch(const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, float max_distance, int cap, int rows_cap,
+                       BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s) {
+  const dim3 block(MP_WAVES * 64);
+  for (int p0 = 0; p0 < P.npairs; p0 += 65535) {  // (grid.y holds 65535)
+    const dim3 grid((rows_cap + 63) / 64, min(65535, P.npairs - p0));
+    hipLaunchKernelGGL(k_match_radius_pairs<W32>, grid, block, 0, s, Q, T, P, p0, max_distance, cap, rows_cap, out, out_count, pair_rows);
+  }
+}
+// false: descriptor size not covered (16, 32, 48, 64 bytes are)
+bool brisk_launch_match_radius_pairs(const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, int words32, float max_distance,
+                                     int cap, int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s) {
+  switch (words32) {
+    case 4: mrp_launch<4>(Q, T, P, max_distance, cap, rows_cap, out, out_count, pair_rows, s); break;
+    case 8: mrp_launch<8>(Q, T, P, max_distance, cap, rows_cap, out, out_count, pair_rows, s); break;
+    case 12: mrp_launch<12>(Q, T, P, max_distance, cap, rows_cap, out, out_count, pair_rows, s); break;
+    case 16: mrp_launch<16>(Q, T, P, max_distance, cap, rows_cap, out, out_count, pair_rows, s); break;
+    default: return false;
+  }
+  return true;
+}
+// false: not covered (descriptor size, nt >= 2^22): the caller uses the distance-matrix path
+bool brisk_launch_match_radius_fused(const uint8_t* query, int q_pitch, int nq, const uint8_t* train, int t_pitch, int nt, int words32,
+                                     float max_distance, int cap, BriskDMatch* out, int* out_count, hipStream_t s) {
+  if (nq <= 0 || nt < 0 || nt >= (1 << MF_IDX_BITS) || cap < 1) return false;
+  const dim3 grid((nq + 63) / 64), block(MP_WAVES * 64);
+  switch (words32) {
+    case 4: hipLaunchKernelGGL(k_match_radius_pairs_one<4>, grid, block, 0, s, query, q_pitch, nq, train, t_pitch, nt, max_distance, cap, out, out_count); break;
+    case 8: hipLaunchKernelGGL(k_match_radius_pairs_one<8>, grid, block, 0, s, query, q_pitch, nq, train, t_pitch, nt, max_distance, cap, out, out_count); break;
+    case 12: hipLaunchKernelGGL(k_match_radius_pairs_one<12>, grid, block, 0, s, query, q_pitch, nq, train, t_pitch, nt, max_distance, cap, out, out_count); break;
+    case 16: hipLaunchKernelGGL(k_match_radius_pairs_one<16>, grid, block, 0, s, query, q_pitch, nq, train, t_pitch, nt, max_distance, cap, out, out_count); break;
+    default: return false;
+  }
+  return true;
+}
+
 void brisk_launch_match_dist(const uint8_t* query, int q_pitch, int q0, int nqb, const uint8_t* train, int t_pitch, int nt,
                              int words, const uint8_t* mask, long mask_pitch, uint16_t* dist, long dist_pitch,
                              hipStream_t s) {

@@ -167,7 +167,7 @@ class BruteForceMatcher {
     for (size_t i = 0; i < knn.size(); ++i)
       if (!knn[i].empty()) matches.push_back(knn[i][0]);
   }
-  // two-set convenience forms (cv::DescriptorMatcher::match / knnMatch with explicit train descriptors)
+  // two-set convenience forms (cv::DescriptorMatcher::match / knnMatch / radiusMatch with explicit train descriptors)
   void match(const agast::Mat& queryDescriptors, const agast::Mat& trainDescriptors, std::vector<DMatch>& matches) {
     BruteForceMatcher tmp(distance_);
     tmp.add(trainDescriptors);
@@ -178,6 +178,12 @@ class BruteForceMatcher {
     BruteForceMatcher tmp(distance_);
     tmp.add(trainDescriptors);
     tmp.knnMatch(queryDescriptors, matches, k);
+  }
+  void radiusMatch(const agast::Mat& queryDescriptors, const agast::Mat& trainDescriptors,
+                   std::vector<std::vector<DMatch> >& matches, float maxDistance) {
+    BruteForceMatcher tmp(distance_);
+    tmp.add(trainDescriptors);
+    tmp.radiusMatch(queryDescriptors, matches, maxDistance);
   }
 
  protected:

@@ -428,6 +428,32 @@ int brisk_hip_match_knn_pairs_device(brisk_hip_ctx* ctx, const brisk_hip_desc_se
                                      const brisk_hip_pair_spec* pairs, int dim_bytes, int k, int cross_check, int rows_cap,
                                      brisk_hip_dmatch* d_out, int* d_out_count, int* d_pair_rows, void* stream);
 
+/* Radius matching in the same form - what the reference's callers use (radiusMatch in its live demo and camera test).
+ * Pair p = (a, b): row [p][q] of d_out [npairs][rows_cap][cap_per_query] / d_out_count [npairs][rows_cap] is what
+ * brisk_hip_match_radius returns for query = the n_a rows of frame a, one train image = the n_b rows of frame b, no masks, the
+ * same max_distance and cap_per_query: every train row with (float)distance < max_distance (strict), in (distance, trainIdx)
+ * order; queryIdx = row within frame a, trainIdx = row within frame b, imgIdx = b, distance = the bit count as a float.
+ * d_out_count[p][q] = matches FOUND (it may exceed cap_per_query; only the first cap_per_query are stored).
+ * d_pair_rows[p] = n_a, the TRUE count: only rows q < min(n_a, rows_cap) are written; the entries behind
+ * min(count, cap_per_query) of a written row and all other rows are left untouched.  n_b == 0: counts of 0 (radius matching
+ * has no top-up entry).  max_distance <= 0 or NaN: all counts 0, not an error.
+ * BRISK_HIP_ERR_ARG, before anything is launched: an arithmetic-form frame outside its set, npairs < 0, rows_cap < 1,
+ * cap_per_query < 1, row_pitch < dim_bytes, NULL sets or outputs with npairs > 0; npairs == 0 is BRISK_HIP_OK.  An entry of
+ * d_pairs outside its set, or a train count of 2^22 or more: d_pair_rows[p] = -1 and no rows, for that pair only.
+ * dim_bytes 16, 32, 48 or 64, else BRISK_HIP_ERR_UNSUPPORTED.  Asynchronous on `stream` like
+ * brisk_hip_match_knn_pairs_device: issued on the batch's stream after brisk_hip_detect_describe_batch it needs no
+ * synchronisation.  Rows with more hits than the kernel's per-query list holds (32) take an exact, slower path inside the
+ * same launch. */
+int brisk_hip_match_radius_pairs_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                        const brisk_hip_pair_spec* pairs, int dim_bytes, float max_distance, int cap_per_query,
+                                        int rows_cap, brisk_hip_dmatch* d_out, int* d_out_count, int* d_pair_rows, void* stream);
+/* The radius sibling of brisk_hip_match_knn_device: one train set, no masks, device pointers, host counts, asynchronous on
+ * `stream`; d_out [nq][cap_per_query], d_out_count [nq], as brisk_hip_match_radius writes them (imgIdx 0).  dim_bytes as
+ * brisk_hip_match_radius (16 ... 224); cap_per_query >= 1. */
+int brisk_hip_match_radius_device(brisk_hip_ctx* ctx, const uint8_t* d_query, int nq, int q_pitch, const uint8_t* d_train, int nt,
+                                  int t_pitch, int dim_bytes, float max_distance, int cap_per_query, brisk_hip_dmatch* d_out,
+                                  int* d_out_count, void* stream);
+
 /* ---- per-stage timing: HIP events recorded on the launch stream around every kernel of the batch path ---- */
 int brisk_hip_profile_enable(brisk_hip_ctx* ctx, int enable);       /* resets the accumulated calls */
 int brisk_hip_profile_stages(void);                                 /* number of stages */

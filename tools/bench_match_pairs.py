@@ -9,7 +9,12 @@ alternating windows that each end in a synchronise:
      there was before the pair call (that entry point is unchanged)
 and writes profiles/match_pairs.json: frames/s of A, B, C, the matching cost per batch (B - A, C - A), the spread over the
 repeats, the kernel revision and whether B's and C's rows are identical.
-Usage: python tools/bench_match_pairs.py [--repeats 5] [--window 0.4] [--rows-cap 2048] [--out FILE]
+With --radius R [--cap N] the same three windows for radius matching (profiles/match_radius_pairs.json):
+  B  detect_describe_batch + match_radius_pairs on the same stream (brisk_hip_match_radius_pairs_device)
+  C  detect_describe_batch, synchronise, download every frame's rows, one brisk_hip_match_radius call per pair (host pointers:
+     each call uploads its rows again) - the only way there was before the radius pair call
+plus the threshold, the cap, the hits per query row (mean, max) and the share of rows that took the kernel's dense path.
+Usage: python tools/bench_match_pairs.py [--repeats 5] [--window 0.4] [--rows-cap 2048] [--radius R [--cap N]] [--out FILE]
        --stats-pass: warm-up + a few B iterations only, nothing written (the run a `rocprofv3 --kernel-trace --stats` pass wraps;
        its kernel statistics are kept as profiles/match_pairs_kernel_stats.csv)"""
 import argparse
@@ -29,6 +34,13 @@ from bench import gen_frames, W, H, OCTAVES, THRESHOLD   # the bench line's fram
 import synth
 
 
+class DeviceBytes:
+    """a device pointer as a flat uint8 array torch can wrap (the descriptor rows of the last batch)"""
+
+    def __init__(self, ptr, n):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": "|u1", "data": (ptr, False), "version": 2}
+
+
 class DeviceInts:
     """a device pointer as a flat int32 array torch can wrap (the counters of the last batch)"""
 
@@ -44,11 +56,17 @@ def main():
     ap.add_argument("--window", type=float, default=0.4, help="seconds per window (repeats x window >= 1 s per variant)")
     ap.add_argument("--rows-cap", type=int, default=2048, help="rows per pair in the match buffers (the stream has ~1k keypoints per frame)")
     ap.add_argument("--k", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "match_pairs.json"))
+    ap.add_argument("--radius", type=float, default=None, help="radius matching with this max_distance instead of k-NN")
+    ap.add_argument("--cap", type=int, default=8, help="cap_per_query of the radius calls")
+    ap.add_argument("--out", default=None, help="default: profiles/match_pairs.json, with --radius profiles/match_radius_pairs.json")
     ap.add_argument("--stats-pass", action="store_true")
     a = ap.parse_args()
 
-    n, k, cap = a.batch, a.k, a.rows_cap
+    radius = a.radius
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "match_radius_pairs.json" if radius is not None else "match_pairs.json")
+    n, k, cap = a.batch, (a.cap if radius is not None else a.k), a.rows_cap   # (k: entries per row of the match buffers)
+    LIST = 32                                  # MRP_LIST of brisk_match.hip: rows with more hits take the dense path
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     nd = min(a.distinct, n)
@@ -73,7 +91,10 @@ def main():
     def run_b():
         batch()
         dset, dim = ctx.batch_desc_set()
-        ctx.match_knn_pairs(dset, dset, spec, k, rows_cap=cap, stream=st, dim_bytes=dim, out=outs["B"])
+        if radius is not None:
+            ctx.match_radius_pairs(dset, dset, spec, radius, k, rows_cap=cap, stream=st, dim_bytes=dim, out=outs["B"])
+        else:
+            ctx.match_knn_pairs(dset, dset, spec, k, rows_cap=cap, stream=st, dim_bytes=dim, out=outs["B"])
 
     vp = C.c_void_p
 
@@ -94,7 +115,31 @@ def main():
                          m.data_ptr() + p * cap * k * 16, cnt.data_ptr() + p * cap * 4, st))
         rows.copy_(torch.from_numpy(counts[1:].copy()), non_blocking=False)
 
-    runs = {"A": run_a, "B": run_b, "C": run_c}
+    host_c = {"m": np.zeros((n - 1, cap, k), B.DMATCH), "cnt": np.zeros((n - 1, cap), np.int32)}
+
+    def run_c_radius():
+        batch()
+        torch.cuda.synchronize()
+        d_n, d_desc, cstride, kcap, pitch = vp(), vp(), C.c_int(), C.c_int(), C.c_int()
+        ctx.check(ctx._L.brisk_hip_batch_results(ctx._h, None, C.byref(d_n), C.byref(cstride), None, None, C.byref(d_desc), C.byref(kcap),
+                                                 C.byref(pitch)))
+        ints = cstride.value // 4
+        counts = torch.as_tensor(DeviceInts(d_n.value, (n - 1) * ints + 1), device=dev)[::ints].cpu().numpy()
+        fp = kcap.value * pitch.value
+        rows_dev = torch.as_tensor(DeviceBytes(d_desc.value, n * fp), device=dev).view(n, fp)
+        desc = [rows_dev[f, :int(counts[f]) * pitch.value].cpu().numpy().reshape(-1, pitch.value) for f in range(n)]   # the rows of every frame
+        L, h, fn = ctx._L, ctx._h, ctx._L.brisk_hip_match_radius
+        one, pt = np.zeros(1, np.int32), np.array([pitch.value], np.int32)
+        for p in range(n - 1):
+            q, t = desc[p + 1], desc[p]
+            nq = min(len(q), cap)
+            one[0] = len(t)
+            tptr = (C.c_void_p * 1)(t.ctypes.data if len(t) else None)
+            ctx.check(fn(h, q.ctypes.data if nq else None, nq, pitch.value, 48, 1, tptr, one.ctypes.data, pt.ctypes.data, None, None,
+                         float(radius), k, host_c["m"][p].ctypes.data, host_c["cnt"][p].ctypes.data))
+        host_c["rows"] = counts[1:].copy()
+
+    runs = {"A": run_a, "B": run_b, "C": run_c_radius if radius is not None else run_c}
     for v in "ABCAB":                       # warm-up: buffers sized, the integral format settled on the stream's density
         runs[v]()
         torch.cuda.synchronize()
@@ -111,6 +156,10 @@ def main():
             t.zero_()
         runs[v]()
         torch.cuda.synchronize()
+    if radius is not None:   # variant C wrote host arrays: into the device triple the comparison below reads
+        outs["C"][0].copy_(torch.from_numpy(host_c["m"].view(np.int32).reshape(n - 1, cap, k, 4)))
+        outs["C"][1].copy_(torch.from_numpy(host_c["cnt"]))
+        outs["C"][2].copy_(torch.from_numpy(host_c["rows"]))
     (mb, cb, rb), (mc, cc, rc) = outs["B"], outs["C"]
     valid = torch.arange(cap, device=dev)[None, :] < rb[:, None]
     sel = valid[:, :, None] & (torch.arange(k, device=dev)[None, None, :] < cb[:, :, None])   # the entries a row's count covers
@@ -118,6 +167,7 @@ def main():
     identical = bool(torch.equal(rb, rc) and torch.equal(cb[valid], cc[valid]) and
                      torch.equal(mb[sel][:, [0, 1, 3]], mc[sel][:, [0, 1, 3]]) and torch.equal(mb[..., 2][sel], pidx[sel]))
     rows_host = rb.cpu().numpy()
+    hits = cb[valid].cpu().numpy()             # per query row: k-NN entries, or radius matches FOUND
 
     fps = {v: [] for v in "ABC"}
     for _ in range(a.repeats):
@@ -138,7 +188,8 @@ def main():
     spread = {v: (max(fps[v]) - min(fps[v])) / med[v] for v in "ABC"}
     res = {
         "workload": "bench.py's stream: %dx%d, threshold %d, %d octaves, %d frames per batch (%d distinct) in HBM; frame-to-previous-frame, "
-                    "k = %d, rows_cap %d" % (W, H, THRESHOLD, OCTAVES, n, nd, k, cap),
+                    "%s, rows_cap %d" % (W, H, THRESHOLD, OCTAVES, n, nd,
+                                         ("max_distance %g, cap_per_query %d" % (radius, k)) if radius is not None else "k = %d" % k, cap),
         "kernel_revision": ctx.kernel_revision(),
         "device": torch.cuda.get_device_name(0),
         "windows": {"repeats": a.repeats, "seconds_each": a.window, "order": "A, B, C alternating; every window ends in a synchronise"},
@@ -154,6 +205,14 @@ def main():
         "legend": {"A": "detect_describe_batch", "B": "A + brisk_hip_match_knn_pairs_device on the same stream",
                    "C": "A, synchronise, counts to the host, one brisk_hip_match_knn_device call per pair"},
     }
+    if radius is not None:
+        res["legend"].update({"B": "A + brisk_hip_match_radius_pairs_device on the same stream",
+                              "C": "A, synchronise, every frame's rows to the host, one brisk_hip_match_radius call per pair"})
+        res.update({"max_distance": radius, "cap_per_query": k,
+                    "hits_per_query": {"mean": round(float(hits.mean()), 4), "max": int(hits.max()), "rows": int(hits.size),
+                                       "rows_without_a_hit": round(float((hits == 0).mean()), 4),
+                                       "rows_over_the_cap": round(float((hits > k).mean()), 6)},
+                    "dense_path_share_of_rows": round(float((hits > LIST).mean()), 6), "dense_path_list_keys": LIST})
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
