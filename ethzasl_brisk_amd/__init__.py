@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "brisk_hip_batch_download_all", "brisk_hip_batch_download_wait", "brisk_hip_detect_describe_batch_host_results",
     "brisk_hip_batch_desc_set", "brisk_hip_match_knn_pairs_device",
     "brisk_hip_match_radius_pairs_device", "brisk_hip_match_radius_device",
+    "brisk_hip_batch_kp_set", "brisk_hip_match_knn_pairs_gated_device", "brisk_hip_match_radius_pairs_gated_device",
 ]
 # every symbol include/brisk_hip_debug.h declares: test / tuning builds (BRISK_HIP_TUNING) only
 DEBUG_SYMBOLS = [
@@ -77,6 +78,21 @@ class PairSpec(C.Structure):
     device array of npairs x {query frame, train frame}"""
     _fields_ = [("npairs", C.c_int), ("query_first", C.c_int), ("query_step", C.c_int), ("train_first", C.c_int),
                 ("train_step", C.c_int), ("d_pairs", C.c_void_p)]
+
+
+class KpSet(C.Structure):
+    """brisk_hip_kp_set: the keypoint records (28 bytes each, device memory) that belong to the rows of a DescSet"""
+    _fields_ = [("d_kps", C.c_void_p), ("frame_pitch", C.c_long)]
+
+
+class MatchGate(C.Structure):
+    """brisk_hip_match_gate: rows q, t may match iff dx_min <= T.x - Q.x <= dx_max, dy_min <= T.y - Q.y <= dy_max and
+    (max_octave_diff < 0 or |T.octave - Q.octave| <= max_octave_diff); -inf / +inf switch a bound off"""
+    _fields_ = [("dx_min", C.c_float), ("dx_max", C.c_float), ("dy_min", C.c_float), ("dy_max", C.c_float), ("max_octave_diff", C.c_int)]
+
+    @classmethod
+    def all_pass(cls):
+        return cls(-float("inf"), float("inf"), -float("inf"), float("inf"), -1)
 
 
 class HostResults:
@@ -199,6 +215,13 @@ def load_library():
     L.brisk_hip_match_radius_pairs_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(PairSpec), C.c_int, C.c_float,
                                                       C.c_int, C.c_int, vp, vp, vp, vp]
     L.brisk_hip_match_radius_device.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp]
+    L.brisk_hip_batch_kp_set.argtypes = [vp, C.POINTER(KpSet)]
+    L.brisk_hip_match_knn_pairs_gated_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
+                                                         C.POINTER(MatchGate), C.POINTER(PairSpec), C.c_int, C.c_int, C.c_int, C.c_int,
+                                                         vp, vp, vp, vp]
+    L.brisk_hip_match_radius_pairs_gated_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
+                                                            C.POINTER(MatchGate), C.POINTER(PairSpec), C.c_int, C.c_float, C.c_int, C.c_int,
+                                                            vp, vp, vp, vp]
     L.brisk_hip_reserve.argtypes = [vp, C.c_int, C.c_int]
     L.brisk_hip_detect_uniform.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
                                            C.c_double, C.c_int, vp, C.c_int, ip]
@@ -475,13 +498,29 @@ class Context:
         self.check(self._L.brisk_hip_batch_desc_set(self._h, C.byref(st), C.byref(dim)))
         return st, dim.value
 
+    def batch_kp_set(self):
+        """KpSet of the last batch's described keypoints, row for row with batch_desc_set()'s rows; valid as long as that set"""
+        kps = KpSet()
+        self.check(self._L.brisk_hip_batch_kp_set(self._h, C.byref(kps)))
+        return kps
+
+    def _gate_args(self, gate, query_kps, train_kps):
+        """the three extra arguments of the gated calls; keypoint sets left out = the last batch's"""
+        if query_kps is None or train_kps is None:
+            own = self.batch_kp_set()
+            query_kps = own if query_kps is None else query_kps
+            train_kps = own if train_kps is None else train_kps
+        return C.byref(query_kps), C.byref(train_kps), C.byref(gate)
+
     def match_knn_pairs(self, query, train, pairs, k, cross_check=False, rows_cap=None, stream=None, dim_bytes=None, out=None,
-                        download=False):
+                        download=False, gate=None, query_kps=None, train_kps=None):
         """brisk_hip_match_knn_pairs_device.  query / train: DescSet; pairs: PairSpec.  rows_cap None = the context's keypoint
         capacity, dim_bytes None = the last batch's descriptor size.  Returns the device tensors (matches [npairs, rows_cap, k, 4]
         int32 - DMATCH records -, counts [npairs, rows_cap], pair_rows [npairs]); `out` = such a triple to be written instead of
         new (uninitialised) tensors.  Asynchronous unless download=True: that synchronises and returns, per pair, the list of
-        per-query DMATCH arrays BruteForceMatcher.knnMatch returns (a pair with pair_rows -1: an empty list)."""
+        per-query DMATCH arrays BruteForceMatcher.knnMatch returns (a pair with pair_rows -1: an empty list).
+        gate (a MatchGate): brisk_hip_match_knn_pairs_gated_device - only rows whose keypoints (query_kps / train_kps: KpSet, None =
+        the last batch's) pass the gate are matched, and a row holds real matches only (no top-up entry)."""
         import torch
         if dim_bytes is None:
             dim_bytes = self.batch_desc_set()[1]
@@ -496,9 +535,16 @@ class Context:
                    torch.empty((max(n, 0), max(rows_cap, 0)), dtype=torch.int32, device=dev),
                    torch.empty(max(n, 0), dtype=torch.int32, device=dev))
         m, cnt, rows = out
-        self.check(self._L.brisk_hip_match_knn_pairs_device(self._h, C.byref(query), C.byref(train), C.byref(pairs), int(dim_bytes), int(k),
-                                                            int(bool(cross_check)), int(rows_cap), m.data_ptr(), cnt.data_ptr(),
-                                                            rows.data_ptr(), C.c_void_p(stream) if stream else None))
+        if gate is not None:
+            self.check(self._L.brisk_hip_match_knn_pairs_gated_device(self._h, C.byref(query), C.byref(train),
+                                                                      *self._gate_args(gate, query_kps, train_kps), C.byref(pairs),
+                                                                      int(dim_bytes), int(k), int(bool(cross_check)), int(rows_cap),
+                                                                      m.data_ptr(), cnt.data_ptr(), rows.data_ptr(),
+                                                                      C.c_void_p(stream) if stream else None))
+        else:
+            self.check(self._L.brisk_hip_match_knn_pairs_device(self._h, C.byref(query), C.byref(train), C.byref(pairs), int(dim_bytes), int(k),
+                                                                int(bool(cross_check)), int(rows_cap), m.data_ptr(), cnt.data_ptr(),
+                                                                rows.data_ptr(), C.c_void_p(stream) if stream else None))
         if not download:
             return out
         torch.cuda.synchronize(self.device)
@@ -507,11 +553,12 @@ class Context:
         return [[hm[p, q, :hc[p, q]].copy() for q in range(min(max(int(hr[p]), 0), rows_cap))] for p in range(n)]
 
     def match_radius_pairs(self, query, train, pairs, max_distance, cap_per_query, rows_cap=None, stream=None, dim_bytes=None, out=None,
-                           download=False):
+                           download=False, gate=None, query_kps=None, train_kps=None):
         """brisk_hip_match_radius_pairs_device; the conventions of match_knn_pairs.  Returns the device tensors (matches
         [npairs, rows_cap, cap_per_query, 4] int32 - DMATCH records -, counts [npairs, rows_cap] = matches FOUND, pair_rows
         [npairs]) or writes the triple `out`.  Asynchronous unless download=True: that synchronises and returns (rows, counts):
-        per pair the list of per-query DMATCH arrays cut to min(count, cap_per_query), and per pair the counts of those rows."""
+        per pair the list of per-query DMATCH arrays cut to min(count, cap_per_query), and per pair the counts of those rows.
+        gate / query_kps / train_kps as in match_knn_pairs: brisk_hip_match_radius_pairs_gated_device."""
         import torch
         if dim_bytes is None:
             dim_bytes = self.batch_desc_set()[1]
@@ -526,9 +573,16 @@ class Context:
                    torch.empty((max(n, 0), max(rows_cap, 0)), dtype=torch.int32, device=dev),
                    torch.empty(max(n, 0), dtype=torch.int32, device=dev))
         m, cnt, rows = out
-        self.check(self._L.brisk_hip_match_radius_pairs_device(self._h, C.byref(query), C.byref(train), C.byref(pairs), int(dim_bytes),
-                                                               float(max_distance), cpq, int(rows_cap), m.data_ptr(), cnt.data_ptr(),
-                                                               rows.data_ptr(), C.c_void_p(stream) if stream else None))
+        if gate is not None:
+            self.check(self._L.brisk_hip_match_radius_pairs_gated_device(self._h, C.byref(query), C.byref(train),
+                                                                         *self._gate_args(gate, query_kps, train_kps), C.byref(pairs),
+                                                                         int(dim_bytes), float(max_distance), cpq, int(rows_cap),
+                                                                         m.data_ptr(), cnt.data_ptr(), rows.data_ptr(),
+                                                                         C.c_void_p(stream) if stream else None))
+        else:
+            self.check(self._L.brisk_hip_match_radius_pairs_device(self._h, C.byref(query), C.byref(train), C.byref(pairs), int(dim_bytes),
+                                                                   float(max_distance), cpq, int(rows_cap), m.data_ptr(), cnt.data_ptr(),
+                                                                   rows.data_ptr(), C.c_void_p(stream) if stream else None))
         if not download:
             return out
         torch.cuda.synchronize(self.device)

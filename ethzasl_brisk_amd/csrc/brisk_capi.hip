@@ -2065,6 +2065,114 @@ int brisk_hip_match_radius_pairs_device(brisk_hip_ctx* ctx, const brisk_hip_desc
   return BRISK_HIP_OK;
 }
 
+int brisk_hip_batch_kp_set(brisk_hip_ctx* ctx, brisk_hip_kp_set* kps) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!kps) return fail(ctx, BRISK_HIP_ERR_ARG, "batch_kp_set: null destination");
+  if (!ctx->B.counters || !ctx->last_has_desc || ctx->last_nframes <= 0 || !ctx->D.dkp)
+    return fail(ctx, BRISK_HIP_ERR_ARG, "batch_kp_set: the context's last call described no batch");
+  kps->d_kps = reinterpret_cast<const brisk_hip_keypoint*>(ctx->D.dkp);
+  kps->frame_pitch = (long)ctx->B.kp_cap * (long)sizeof(BriskKeyPoint);
+  return BRISK_HIP_OK;
+}
+
+// the gated calls' own arguments (npairs > 0); the kernels read the records with 4-byte loads
+static const char* match_gated_check(const brisk_hip_kp_set* qk, const brisk_hip_kp_set* tk, const brisk_hip_match_gate* gate) {
+  if (!qk || !tk || !gate) return "match_pairs_gated: null keypoint set or gate";
+  for (const brisk_hip_kp_set* s : {qk, tk}) {
+    if (!s->d_kps) return "match_pairs_gated: a keypoint set without records";
+    if (s->frame_pitch < 0 || (((uintptr_t)s->d_kps | (unsigned long)s->frame_pitch) & 3)) return "match_pairs_gated: bad keypoint set geometry";
+  }
+  return nullptr;
+}
+
+int brisk_hip_match_knn_pairs_gated_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                           const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                           const brisk_hip_match_gate* gate, const brisk_hip_pair_spec* pairs, int dim_bytes, int k,
+                                           int cross_check, int rows_cap, brisk_hip_dmatch* d_out, int* d_out_count, int* d_pair_rows,
+                                           void* stream) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  // (the checks of brisk_hip_match_knn_pairs_device in its order, the gate's own behind npairs == 0)
+  if (!query || !train || !pairs || pairs->npairs < 0) return fail(ctx, BRISK_HIP_ERR_ARG, "match_pairs: bad argument");
+  if (k < 1 || k > 2) return fail(ctx, BRISK_HIP_ERR_ARG, "match_pairs: k must be 1 or 2 (brisk_hip_match_knn for more)");
+  if (cross_check && k != 1) return fail(ctx, BRISK_HIP_ERR_ARG, "match_pairs: the cross check needs k == 1");
+  if (dim_bytes != 16 && dim_bytes != 32 && dim_bytes != 48 && dim_bytes != 64)
+    return fail(ctx, BRISK_HIP_ERR_UNSUPPORTED, "match_pairs: descriptor size must be 16, 32, 48 or 64 bytes");
+  for (const brisk_hip_desc_set* s : {query, train})
+    if (const char* msg = match_pairs_check_set(s, dim_bytes)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
+  const int np = pairs->npairs;
+  if (np == 0) return BRISK_HIP_OK;
+  if (const char* msg = match_gated_check(query_kps, train_kps, gate)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
+  if (rows_cap <= 0 || !d_out || !d_out_count || !d_pair_rows) return fail(ctx, BRISK_HIP_ERR_ARG, "match_pairs: bad output argument");
+  if (!pairs->d_pairs) {  // (a list on the device is checked there: d_pair_rows = -1)
+    const long q0 = pairs->query_first, q1 = q0 + (long)(np - 1) * pairs->query_step;
+    const long t0 = pairs->train_first, t1 = t0 + (long)(np - 1) * pairs->train_step;
+    if (q0 < 0 || q0 >= query->frames || q1 < 0 || q1 >= query->frames || t0 < 0 || t0 >= train->frames || t1 < 0 || t1 >= train->frames)
+      return fail(ctx, BRISK_HIP_ERR_ARG, "match_pairs: a pair names a frame outside its set");
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  // (ordered behind the batch that wrote the sets and before the next one, as brisk_hip_match_knn_pairs_device)
+  if (workspace_acquire(ctx, st)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
+  WorkspaceGuard guard(ctx, st);
+  const BriskDescSet Q{query->d_desc, query->d_counts, query->count_stride, query->frame_pitch, query->row_pitch, query->frames};
+  const BriskDescSet T{train->d_desc, train->d_counts, train->count_stride, train->frame_pitch, train->row_pitch, train->frames};
+  const BriskKpSet QK{reinterpret_cast<const char*>(query_kps->d_kps), query_kps->frame_pitch};
+  const BriskKpSet TK{reinterpret_cast<const char*>(train_kps->d_kps), train_kps->frame_pitch};
+  const BriskMatchGate G{gate->dx_min, gate->dx_max, gate->dy_min, gate->dy_max, gate->max_octave_diff};
+  const BriskPairSpec P{np, pairs->query_first, pairs->query_step, pairs->train_first, pairs->train_step, pairs->d_pairs};
+  if (!brisk_launch_match_knn_pairs_gated(Q, T, QK, TK, G, P, dim_bytes / 4, k, cross_check != 0, rows_cap,
+                                          reinterpret_cast<BriskDMatch*>(d_out), d_out_count, d_pair_rows, st))
+    return fail(ctx, BRISK_HIP_ERR_UNSUPPORTED, "match_pairs: descriptor size not covered");
+  HIPCHK(ctx, hipGetLastError());
+  if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
+  return BRISK_HIP_OK;
+}
+
+int brisk_hip_match_radius_pairs_gated_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                              const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                              const brisk_hip_match_gate* gate, const brisk_hip_pair_spec* pairs, int dim_bytes,
+                                              float max_distance, int cap_per_query, int rows_cap, brisk_hip_dmatch* d_out,
+                                              int* d_out_count, int* d_pair_rows, void* stream) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  // (the checks of brisk_hip_match_radius_pairs_device in its order, the gate's own behind npairs == 0)
+  if (!pairs || pairs->npairs < 0) return fail(ctx, BRISK_HIP_ERR_ARG, "match_radius_pairs: bad argument");
+  if (cap_per_query < 1) return fail(ctx, BRISK_HIP_ERR_ARG, "match_radius_pairs: cap_per_query must be at least 1");
+  if (dim_bytes != 16 && dim_bytes != 32 && dim_bytes != 48 && dim_bytes != 64)
+    return fail(ctx, BRISK_HIP_ERR_UNSUPPORTED, "match_radius_pairs: descriptor size must be 16, 32, 48 or 64 bytes");
+  const int np = pairs->npairs;
+  if (np == 0) return BRISK_HIP_OK;
+  if (!query || !train) return fail(ctx, BRISK_HIP_ERR_ARG, "match_radius_pairs: null descriptor set");
+  for (const brisk_hip_desc_set* s : {query, train})
+    if (const char* msg = match_pairs_check_set(s, dim_bytes)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
+  if (const char* msg = match_gated_check(query_kps, train_kps, gate)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
+  if (rows_cap < 1 || !d_out || !d_out_count || !d_pair_rows) return fail(ctx, BRISK_HIP_ERR_ARG, "match_radius_pairs: bad output argument");
+  if (!pairs->d_pairs) {  // (a list on the device is checked there: d_pair_rows = -1)
+    const long q0 = pairs->query_first, q1 = q0 + (long)(np - 1) * pairs->query_step;
+    const long t0 = pairs->train_first, t1 = t0 + (long)(np - 1) * pairs->train_step;
+    if (q0 < 0 || q0 >= query->frames || q1 < 0 || q1 >= query->frames || t0 < 0 || t0 >= train->frames || t1 < 0 || t1 >= train->frames)
+      return fail(ctx, BRISK_HIP_ERR_ARG, "match_radius_pairs: a pair names a frame outside its set");
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  if (workspace_acquire(ctx, st)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
+  WorkspaceGuard guard(ctx, st);
+  const BriskDescSet Q{query->d_desc, query->d_counts, query->count_stride, query->frame_pitch, query->row_pitch, query->frames};
+  const BriskDescSet T{train->d_desc, train->d_counts, train->count_stride, train->frame_pitch, train->row_pitch, train->frames};
+  const BriskKpSet QK{reinterpret_cast<const char*>(query_kps->d_kps), query_kps->frame_pitch};
+  const BriskKpSet TK{reinterpret_cast<const char*>(train_kps->d_kps), train_kps->frame_pitch};
+  const BriskMatchGate G{gate->dx_min, gate->dx_max, gate->dy_min, gate->dy_max, gate->max_octave_diff};
+  const BriskPairSpec P{np, pairs->query_first, pairs->query_step, pairs->train_first, pairs->train_step, pairs->d_pairs};
+  if (!brisk_launch_match_radius_pairs_gated(Q, T, QK, TK, G, P, dim_bytes / 4, max_distance, cap_per_query, rows_cap,
+                                             reinterpret_cast<BriskDMatch*>(d_out), d_out_count, d_pair_rows, st))
+    return fail(ctx, BRISK_HIP_ERR_UNSUPPORTED, "match_radius_pairs: descriptor size not covered");
+  HIPCHK(ctx, hipGetLastError());
+  if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
+  return BRISK_HIP_OK;
+}
+
 int brisk_hip_match_radius_device(brisk_hip_ctx* ctx, const uint8_t* d_query, int nq, int q_pitch, const uint8_t* d_train, int nt,
                                   int t_pitch, int dim_bytes, float max_distance, int cap_per_query, brisk_hip_dmatch* d_out,
                                   int* d_out_count, void* stream) {

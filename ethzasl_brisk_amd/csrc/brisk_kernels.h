@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "brisk_common.h"
+#include "brisk_match_gate.h"
 
 #define BRISK_DETECT_TILE_W 64
 #ifndef BRISK_DETECT_ROWS_PER_THREAD
@@ -171,6 +172,19 @@ bool brisk_launch_match_radius_pairs(const BriskDescSet& Q, const BriskDescSet& 
                                      int cap, int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s);
 bool brisk_launch_match_radius_fused(const uint8_t* query, int q_pitch, int nq, const uint8_t* train, int t_pitch, int nt, int words32,
                                      float max_distance, int cap, BriskDMatch* out, int* out_count, hipStream_t s);
+
+// the same two pair matchers behind a position gate (brisk_match_gate.h) evaluated on the keypoints that belong to the rows; a gated
+// k-NN row holds real matches only (min(k, allowed rows) entries, no top-up).  BriskKpSet mirrors brisk_hip_kp_set
+struct BriskKpSet {
+  const char* kps;   // frame f's record r (BriskKeyPoint, 4-byte aligned) at kps + f * frame_pitch + r * sizeof(BriskKeyPoint)
+  long frame_pitch;  // bytes
+};
+bool brisk_launch_match_knn_pairs_gated(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
+                                        const BriskMatchGate& gate, const BriskPairSpec& P, int words32, int k, bool cross, int rows_cap,
+                                        BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s);
+bool brisk_launch_match_radius_pairs_gated(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
+                                           const BriskMatchGate& gate, const BriskPairSpec& P, int words32, float max_distance, int cap,
+                                           int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s);
 
 // ---- uniformity enforcement / keypoint bucketing (brisk_uniformity.hip): optional post-filters of the detector's keypoints ----
 void brisk_launch_bucketing(BriskKeyPoint* kp, BriskFrameCounters* counters, int* order, BriskKeyPoint* tmp, int kp_cap, int rows,

@@ -534,15 +534,35 @@ __device__ __forceinline__ void mrp_scan(const unsigned (&qv)[W32], const uint8_
     }
   }
 }
+// the gated kernels' view of a pair: the gate and the keypoint records of the two frames, row for row with the descriptors
+struct MpGate {
+  BriskMatchGate g;
+  const char* qk;
+  const char* tk;
+};
+__device__ __forceinline__ const BriskKeyPoint* mp_kp(const char* kps, int r) {
+  return reinterpret_cast<const BriskKeyPoint*>(kps + (long)r * (long)sizeof(BriskKeyPoint));
+}
+// the dense path's distance of train row t (one per lane) to the wave's query; GATE: a row the gate forbids is no hit (thr)
+template <int W32, bool ALIGNED, bool GATE>
+__device__ __forceinline__ unsigned mrp_dense_dist(const unsigned (&uq)[W32], const uint8_t* trows, int t_pitch, int t, unsigned thr,
+                                                   const MpGate& G, const BriskGateLane& QL) {
+  if (GATE) {
+    const BriskKeyPoint* kp = mp_kp(G.tk, t);
+    if (!brisk_gate_query_lane(G.g, QL, kp->x, kp->y, kp->octave)) return thr;
+  }
+  return mrp_dist<W32, ALIGNED>(uq, trows + (long)t * t_pitch);
+}
 // one wave, one query with more than MRP_LIST hits.  bins: thr + 1 ints of this wave's own
-template <int W32, bool ALIGNED>
+template <int W32, bool ALIGNED, bool GATE>
 __device__ __forceinline__ void mrp_dense(int* bins, const unsigned (&uq)[W32], const uint8_t* trows, int t_pitch, int n_b, unsigned thr,
-                                          int cap, int lane, int q, int img, BriskDMatch* __restrict__ orow) {
+                                          int cap, int lane, int q, int img, BriskDMatch* __restrict__ orow, const MpGate& G,
+                                          const BriskGateLane& QL) {
   for (int b = lane; b <= (int)thr; b += 64) bins[b] = 0;
   __builtin_amdgcn_s_waitcnt(0);
   __builtin_amdgcn_wave_barrier();
   for (int t = lane; t < n_b; t += 64) {
-    const unsigned d = mrp_dist<W32, ALIGNED>(uq, trows + (long)t * t_pitch);
+    const unsigned d = mrp_dense_dist<W32, ALIGNED, GATE>(uq, trows, t_pitch, t, thr, G, QL);
     if (d < thr) atomicAdd(&bins[d], 1);
   }
   __builtin_amdgcn_s_waitcnt(0);
@@ -575,7 +595,7 @@ __device__ __forceinline__ void mrp_dense(int* bins, const unsigned (&uq)[W32], 
   for (int t0 = 0; t0 < n_b; t0 += 64) {
     const int t = t0 + lane;
     unsigned d = thr;
-    if (t < n_b) d = mrp_dist<W32, ALIGNED>(uq, trows + (long)t * t_pitch);
+    if (t < n_b) d = mrp_dense_dist<W32, ALIGNED, GATE>(uq, trows, t_pitch, t, thr, G, QL);
     const bool hit = d < thr && bins[d] < cap;
     unsigned long long todo = __ballot(hit);
     while (todo) {
@@ -600,11 +620,52 @@ __device__ __forceinline__ void mrp_dense(int* bins, const unsigned (&uq)[W32], 
   }
 }
 
+// The gated scans (k_match_knn_pairs_gated / k_match_radius_pairs_gated).  The keypoint of the wave-uniform row comes through the same
+// scalar loads as the row itself, MPG_CHUNK records ahead of the rows they belong to (one wait for the chunk, not one per row); the
+// predicate is a handful of VALU compares whose result lives in a lane mask.  A row that NO lane of the wave may match is left
+// without its descriptor loads and popcounts: a uniform branch on the mask.  `on`: the lane takes part at all.
+// ok[i]: this lane may match row tc + i; live[i]: the lanes of the wave that may.  The ballots are taken for the whole chunk BEFORE
+// the first branch (a ballot is not moved below a branch), so the chunk's keypoint loads and compares stay together in front of
+// its rows instead of one load and wait in front of each.  (No scheduling barrier between the loads and the compares: with one
+// the compiler no longer takes the loop's loads - the descriptor rows included - for scalar loads.)
+#define MPG_CHUNK 4
+template <bool SWAP>
+__device__ __forceinline__ void mpg_allowed(const BriskMatchGate& g, const BriskGateLane& L, bool on, const char* kps, int tc, int t1,
+                                            bool (&ok)[MPG_CHUNK], unsigned long long (&live)[MPG_CHUNK]) {
+#pragma unroll
+  for (int i = 0; i < MPG_CHUNK; ++i) {
+    const BriskKeyPoint* kp = mp_kp(kps, min(tc + i, t1 - 1));
+    const bool pass = SWAP ? brisk_gate_train_lane(g, L, kp->x, kp->y, kp->octave) : brisk_gate_query_lane(g, L, kp->x, kp->y, kp->octave);
+    ok[i] = on && tc + i < t1 && pass;
+    live[i] = __ballot(ok[i]);
+  }
+}
+template <int W32, bool ALIGNED>
+__device__ __forceinline__ void mrpg_scan(const unsigned (&qv)[W32], const uint8_t* rows, int pitch, int t0, int t1, unsigned thr,
+                                          const BriskMatchGate& g, const BriskGateLane& L, bool on, const char* kps, int* cnt,
+                                          unsigned (*list)[64], int lane) {
+  for (int tc = t0; tc < t1; tc += MPG_CHUNK) {
+    bool ok[MPG_CHUNK];
+    unsigned long long live[MPG_CHUNK];
+    mpg_allowed<false>(g, L, on, kps, tc, t1, ok, live);
+#pragma unroll
+    for (int i = 0; i < MPG_CHUNK; ++i) {
+      if (live[i] == 0) continue;  // wave-uniform
+      const int t = tc + i;
+      const unsigned d = mrp_dist<W32, ALIGNED>(qv, rows + (long)t * pitch);
+      if (ok[i] && d < thr) {
+        const int slot = atomicAdd(&cnt[lane], 1);
+        if (slot < MRP_LIST) list[slot][lane] = (d << MF_IDX_BITS) | (unsigned)t;
+      }
+    }
+  }
+}
+
 // the workgroup's 64 query rows [blockIdx.x * 64, ...) of `rows` against the n_b train rows; out / out_count: row 0 of this query set
-template <int W32>
+template <int W32, bool GATE = false>
 __device__ __forceinline__ void mrp_body(const uint8_t* qrows, int q_pitch, bool q_aligned, int rows, const uint8_t* trows, int t_pitch,
                                          bool t_aligned, int n_b, float max_distance, int cap, int img, BriskDMatch* __restrict__ out,
-                                         int* __restrict__ out_count) {
+                                         int* __restrict__ out_count, const MpGate& G = MpGate()) {
   __shared__ int cnt[64];
   __shared__ unsigned list[MRP_LIST][64];
   __shared__ int bins[MP_WAVES][MRP_BINS + 3];
@@ -625,8 +686,15 @@ __device__ __forceinline__ void mrp_body(const uint8_t* qrows, int q_pitch, bool
     const unsigned thr_lane = q < rows ? thr : 0u;  // (the lanes behind the last row collect nothing)
     const int per = (n_b + MP_WAVES - 1) / MP_WAVES;
     const int t0 = wave * per, t1 = min(n_b, t0 + per);
-    if (t_aligned) mrp_scan<W32, true>(qv, trows, t_pitch, t0, t1, thr_lane, cnt, list, lane);
-    else mrp_scan<W32, false>(qv, trows, t_pitch, t0, t1, thr_lane, cnt, list, lane);
+    if (GATE) {
+      const BriskKeyPoint* kp = mp_kp(G.qk, min(q, rows - 1));
+      const BriskGateLane L = brisk_gate_lane(G.g, kp->x, kp->y, kp->octave);
+      if (t_aligned) mrpg_scan<W32, true>(qv, trows, t_pitch, t0, t1, thr, G.g, L, q < rows, G.tk, cnt, list, lane);
+      else mrpg_scan<W32, false>(qv, trows, t_pitch, t0, t1, thr, G.g, L, q < rows, G.tk, cnt, list, lane);
+    } else {
+      if (t_aligned) mrp_scan<W32, true>(qv, trows, t_pitch, t0, t1, thr_lane, cnt, list, lane);
+      else mrp_scan<W32, false>(qv, trows, t_pitch, t0, t1, thr_lane, cnt, list, lane);
+    }
   }
   __syncthreads();
   {  // counts of all rows; sparse rows: MP_WAVES threads per query, each ranks every MP_WAVES-th key of the list
@@ -656,8 +724,13 @@ __device__ __forceinline__ void mrp_body(const uint8_t* qrows, int q_pitch, bool
     if (cnt[ql] <= MRP_LIST) continue;
     unsigned uq[W32];
     mp_load_row<W32>(qrows + (long)qq * q_pitch, q_aligned, uq);
-    if (t_aligned) mrp_dense<W32, true>(bins[wave], uq, trows, t_pitch, n_b, thr, cap, lane, qq, img, out + (long)qq * cap);
-    else mrp_dense<W32, false>(bins[wave], uq, trows, t_pitch, n_b, thr, cap, lane, qq, img, out + (long)qq * cap);
+    BriskGateLane QL = {};
+    if (GATE) {
+      const BriskKeyPoint* kp = mp_kp(G.qk, qq);  // (wave-uniform)
+      QL = brisk_gate_lane(G.g, kp->x, kp->y, kp->octave);
+    }
+    if (t_aligned) mrp_dense<W32, true, GATE>(bins[wave], uq, trows, t_pitch, n_b, thr, cap, lane, qq, img, out + (long)qq * cap, G, QL);
+    else mrp_dense<W32, false, GATE>(bins[wave], uq, trows, t_pitch, n_b, thr, cap, lane, qq, img, out + (long)qq * cap, G, QL);
   }
 }
 
@@ -736,6 +809,223 @@ bool brisk_launch_match_radius_fused(const uint8_t* query, int q_pitch, int nq, 
     case 8: hipLaunchKernelGGL(k_match_radius_pairs_one<8>, grid, block, 0, s, query, q_pitch, nq, train, t_pitch, nt, max_distance, cap, out, out_count); break;
     case 12: hipLaunchKernelGGL(k_match_radius_pairs_one<12>, grid, block, 0, s, query, q_pitch, nq, train, t_pitch, nt, max_distance, cap, out, out_count); break;
     case 16: hipLaunchKernelGGL(k_match_radius_pairs_one<16>, grid, block, 0, s, query, q_pitch, nq, train, t_pitch, nt, max_distance, cap, out, out_count); break;
+    default: return false;
+  }
+  return true;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The two pair matchers behind a position gate (brisk_hip_match_knn_pairs_gated_device / brisk_hip_match_radius_pairs_gated_device):
+// the mask of a pair is the predicate of brisk_match_gate.h on the two rows' keypoints, evaluated inside the scan (mpg_allowed
+// above).  Same grid, same 8-wave workgroups, same LDS, no scratch, no workspace.  k-NN: a lane the gate forbids keeps its key
+// 0xFFFFFFFF, so a row holds min(k, allowed rows) REAL matches and is never topped up.  CROSS: the roles swap - the lane holds
+// keypoint T of its forward match (a lane without one takes no part), the row passing by is q'.
+// ------------------------------------------------------------------------------------------------
+// pair, counts and d_pair_rows as k_match_knn_pairs / k_match_radius_pairs resolve them; false: nothing to do for this workgroup
+__device__ __forceinline__ bool mpg_resolve(const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, int p, bool back_keys,
+                                            int rows_cap, int* __restrict__ pair_rows, int& a, int& b, int& n_a, int& n_b, int& rows) {
+  if (P.pairs) {
+    a = P.pairs[2 * (long)p];
+    b = P.pairs[2 * (long)p + 1];
+  } else {
+    a = P.query_first + p * P.query_step;
+    b = P.train_first + p * P.train_step;
+  }
+  const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+  if (a < 0 || a >= Q.frames || b < 0 || b >= T.frames) {  // (a bad entry of the caller's list; the arithmetic form is checked on the host)
+    if (first) pair_rows[p] = -1;
+    return false;
+  }
+  n_a = max(0, Q.counts[(long)a * Q.count_stride]);
+  n_b = max(0, T.counts[(long)b * T.count_stride]);
+  if (n_b >= (1 << MF_IDX_BITS) || (back_keys && n_a >= (1 << MF_IDX_BITS))) {  // (the keys hold 22 index bits)
+    if (first) pair_rows[p] = -1;
+    return false;
+  }
+  if (first) pair_rows[p] = n_a;
+  rows = min(n_a, rows_cap);
+  return (int)blockIdx.x * 64 < rows;
+}
+
+// rows [t0, t1) of one frame against the lane's descriptor, behind the gate: the two smallest keys among the allowed rows
+template <int W32, bool ALIGNED, bool SWAP>
+__device__ __forceinline__ void mpg_scan(const unsigned (&qv)[W32], const uint8_t* rows, int pitch, int t0, int t1, const BriskMatchGate& g,
+                                         const BriskGateLane& L, bool on, const char* kps, unsigned& b1, unsigned& b2) {
+  for (int tc = t0; tc < t1; tc += MPG_CHUNK) {
+    bool ok[MPG_CHUNK];
+    unsigned long long live[MPG_CHUNK];
+    mpg_allowed<SWAP>(g, L, on, kps, tc, t1, ok, live);
+#pragma unroll
+    for (int i = 0; i < MPG_CHUNK; ++i) {
+      if (live[i] == 0) continue;  // wave-uniform
+      const int t = tc + i;
+      const unsigned d = mrp_dist<W32, ALIGNED>(qv, rows + (long)t * pitch);
+      const unsigned key = ok[i] ? (d << MF_IDX_BITS) | (unsigned)t : 0xFFFFFFFFu;
+      b2 = min(b2, max(b1, key));
+      b1 = min(b1, key);
+    }
+  }
+}
+
+template <int W32, bool CROSS>
+__global__ void __launch_bounds__(MP_WAVES * 64) k_match_knn_pairs_gated(const BriskDescSet Q, const BriskDescSet T, const BriskKpSet QK,
+                                                                          const BriskKpSet TK, const BriskMatchGate gate,
+                                                                          const BriskPairSpec P, int pair0, int k, int rows_cap,
+                                                                          BriskDMatch* __restrict__ out, int* __restrict__ out_count,
+                                                                          int* __restrict__ pair_rows) {
+  __shared__ unsigned part[MP_WAVES][2][64];
+  __shared__ unsigned fwd[64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int p = pair0 + blockIdx.y;
+  int a, b, n_a, n_b, rows;
+  if (!mpg_resolve(Q, T, P, p, CROSS, rows_cap, pair_rows, a, b, n_a, n_b, rows)) return;
+  const int q = blockIdx.x * 64 + lane;
+  BriskDMatch* orow = out + ((long)p * rows_cap + q) * k;
+  int* ocnt = out_count + (long)p * rows_cap + q;
+  if (n_b == 0) {
+    if (wave == 0 && q < rows) *ocnt = 0;
+    return;
+  }
+  const uint8_t* qrows = Q.desc + (long)a * Q.frame_pitch;
+  const uint8_t* trows = T.desc + (long)b * T.frame_pitch;
+  const char* qk = QK.kps + (long)a * QK.frame_pitch;
+  const char* tk = TK.kps + (long)b * TK.frame_pitch;
+  const bool q_aligned = (((uintptr_t)Q.desc | (unsigned long)Q.frame_pitch | (unsigned)Q.row_pitch) & 3) == 0;
+  const bool t_aligned = (((uintptr_t)T.desc | (unsigned long)T.frame_pitch | (unsigned)T.row_pitch) & 3) == 0;
+  unsigned b1 = 0xFFFFFFFFu, b2 = 0xFFFFFFFFu;
+  {
+    unsigned qv[W32];
+    mp_load_row<W32>(qrows + (long)min(q, rows - 1) * Q.row_pitch, q_aligned, qv);
+    const BriskKeyPoint* kp = mp_kp(qk, min(q, rows - 1));
+    const BriskGateLane L = brisk_gate_lane(gate, kp->x, kp->y, kp->octave);
+    const int per = (n_b + MP_WAVES - 1) / MP_WAVES;
+    const int t0 = __builtin_amdgcn_readfirstlane(wave * per), t1 = min(n_b, t0 + per);
+    if (t_aligned) mpg_scan<W32, true, false>(qv, trows, T.row_pitch, t0, t1, gate, L, q < rows, tk, b1, b2);
+    else mpg_scan<W32, false, false>(qv, trows, T.row_pitch, t0, t1, gate, L, q < rows, tk, b1, b2);
+  }
+  part[wave][0][lane] = b1;
+  part[wave][1][lane] = b2;
+  __syncthreads();
+  unsigned m1 = 0xFFFFFFFFu, m2 = 0xFFFFFFFFu;
+  if (wave == 0) {
+#pragma unroll
+    for (int w = 0; w < MP_WAVES; ++w)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const unsigned key = part[w][i][lane];
+        m2 = min(m2, max(m1, key));
+        m1 = min(m1, key);
+      }
+  }
+  bool keep = true;
+  if (CROSS) {
+    if (wave == 0) fwd[lane] = m1;
+    __syncthreads();  // (also: wave 0 has read part[] before anybody writes it again)
+    const unsigned f = fwd[lane];
+    const bool has = f != 0xFFFFFFFFu;  // (the gate may have left the row without a forward match)
+    const int t = has ? (int)(f & ((1u << MF_IDX_BITS) - 1)) : 0;
+    unsigned tv[W32];
+    mp_load_row<W32>(trows + (long)t * T.row_pitch, t_aligned, tv);
+    const BriskKeyPoint* kp = mp_kp(tk, t);
+    const BriskGateLane L = brisk_gate_lane(gate, kp->x, kp->y, kp->octave);
+    unsigned c1 = 0xFFFFFFFFu, c2 = 0xFFFFFFFFu;
+    const int per = (n_a + MP_WAVES - 1) / MP_WAVES;
+    const int r0 = __builtin_amdgcn_readfirstlane(wave * per), r1 = min(n_a, r0 + per);
+    // ALL rows q' of frame a, also those beyond rows_cap: M[q'][t]
+    if (q_aligned) mpg_scan<W32, true, true>(tv, qrows, Q.row_pitch, r0, r1, gate, L, has, qk, c1, c2);
+    else mpg_scan<W32, false, true>(tv, qrows, Q.row_pitch, r0, r1, gate, L, has, qk, c1, c2);
+    part[wave][0][lane] = c1;
+    __syncthreads();
+    if (wave == 0) {
+      unsigned best = 0xFFFFFFFFu;
+#pragma unroll
+      for (int w = 0; w < MP_WAVES; ++w) best = min(best, part[w][0][lane]);
+      keep = has && (int)(best & ((1u << MF_IDX_BITS) - 1)) == q;
+    }
+  }
+  if (wave == 0 && q < rows) {
+    int n = 0;
+    if (keep && m1 != 0xFFFFFFFFu) {
+      BriskDMatch m;
+      m.queryIdx = q; m.imgIdx = b;
+      m.trainIdx = (int)(m1 & ((1u << MF_IDX_BITS) - 1)); m.distance = (float)(m1 >> MF_IDX_BITS);
+      orow[0] = m;
+      n = 1;
+      if (k > 1 && m2 != 0xFFFFFFFFu) {  // (no top-up: a second entry only where a second row is allowed)
+        m.trainIdx = (int)(m2 & ((1u << MF_IDX_BITS) - 1)); m.distance = (float)(m2 >> MF_IDX_BITS);
+        orow[1] = m;
+        n = 2;
+      }
+    }
+    *ocnt = n;
+  }
+}
+
+template <int W32>
+__global__ void __launch_bounds__(MP_WAVES * 64) k_match_radius_pairs_gated(const BriskDescSet Q, const BriskDescSet T, const BriskKpSet QK,
+                                                                             const BriskKpSet TK, const BriskMatchGate gate,
+                                                                             const BriskPairSpec P, int pair0, float max_distance, int cap,
+                                                                             int rows_cap, BriskDMatch* __restrict__ out,
+                                                                             int* __restrict__ out_count, int* __restrict__ pair_rows) {
+  const int p = pair0 + blockIdx.y;
+  int a, b, n_a, n_b, rows;
+  if (!mpg_resolve(Q, T, P, p, false, rows_cap, pair_rows, a, b, n_a, n_b, rows)) return;
+  const bool q_aligned = (((uintptr_t)Q.desc | (unsigned long)Q.frame_pitch | (unsigned)Q.row_pitch) & 3) == 0;
+  const bool t_aligned = (((uintptr_t)T.desc | (unsigned long)T.frame_pitch | (unsigned)T.row_pitch) & 3) == 0;
+  const MpGate G{gate, QK.kps + (long)a * QK.frame_pitch, TK.kps + (long)b * TK.frame_pitch};
+  mrp_body<W32, true>(Q.desc + (long)a * Q.frame_pitch, Q.row_pitch, q_aligned, rows, T.desc + (long)b * T.frame_pitch, T.row_pitch,
+                      t_aligned, n_b, max_distance, cap, b, out + (long)p * rows_cap * cap, out_count + (long)p * rows_cap, G);
+}
+
+template <int W32>
+static void mpg_launch(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK, const BriskMatchGate& gate,
+                       const BriskPairSpec& P, int k, bool cross, int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows,
+                       hipStream_t s) {
+  const dim3 block(MP_WAVES * 64);
+  for (int p0 = 0; p0 < P.npairs; p0 += 65535) {  // (grid.y holds 65535)
+    const dim3 grid((rows_cap + 63) / 64, min(65535, P.npairs - p0));
+    if (cross)
+      hipLaunchKernelGGL((k_match_knn_pairs_gated<W32, true>), grid, block, 0, s, Q, T, QK, TK, gate, P, p0, k, rows_cap, out, out_count,
+                         pair_rows);
+    else
+      hipLaunchKernelGGL((k_match_knn_pairs_gated<W32, false>), grid, block, 0, s, Q, T, QK, TK, gate, P, p0, k, rows_cap, out, out_count,
+                         pair_rows);
+  }
+}
+// false: descriptor size not covered (16, 32, 48, 64 bytes are)
+bool brisk_launch_match_knn_pairs_gated(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
+                                        const BriskMatchGate& gate, const BriskPairSpec& P, int words32, int k, bool cross, int rows_cap,
+                                        BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s) {
+  switch (words32) {
+    case 4: mpg_launch<4>(Q, T, QK, TK, gate, P, k, cross, rows_cap, out, out_count, pair_rows, s); break;
+    case 8: mpg_launch<8>(Q, T, QK, TK, gate, P, k, cross, rows_cap, out, out_count, pair_rows, s); break;
+    case 12: mpg_launch<12>(Q, T, QK, TK, gate, P, k, cross, rows_cap, out, out_count, pair_rows, s); break;
+    case 16: mpg_launch<16>(Q, T, QK, TK, gate, P, k, cross, rows_cap, out, out_count, pair_rows, s); break;
+    default: return false;
+  }
+  return true;
+}
+
+template <int W32>
+static void mrpg_launch(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK, const BriskMatchGate& gate,
+                        const BriskPairSpec& P, float max_distance, int cap, int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows,
+                        hipStream_t s) {
+  const dim3 block(MP_WAVES * 64);
+  for (int p0 = 0; p0 < P.npairs; p0 += 65535) {  // (grid.y holds 65535)
+    const dim3 grid((rows_cap + 63) / 64, min(65535, P.npairs - p0));
+    hipLaunchKernelGGL(k_match_radius_pairs_gated<W32>, grid, block, 0, s, Q, T, QK, TK, gate, P, p0, max_distance, cap, rows_cap, out,
+                       out_count, pair_rows);
+  }
+}
+// false: descriptor size not covered (16, 32, 48, 64 bytes are)
+bool brisk_launch_match_radius_pairs_gated(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
+                                           const BriskMatchGate& gate, const BriskPairSpec& P, int words32, float max_distance, int cap,
+                                           int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s) {
+  switch (words32) {
+    case 4: mrpg_launch<4>(Q, T, QK, TK, gate, P, max_distance, cap, rows_cap, out, out_count, pair_rows, s); break;
+    case 8: mrpg_launch<8>(Q, T, QK, TK, gate, P, max_distance, cap, rows_cap, out, out_count, pair_rows, s); break;
+    case 12: mrpg_launch<12>(Q, T, QK, TK, gate, P, max_distance, cap, rows_cap, out, out_count, pair_rows, s); break;
+    case 16: mrpg_launch<16>(Q, T, QK, TK, gate, P, max_distance, cap, rows_cap, out, out_count, pair_rows, s); break;
     default: return false;
   }
   return true;

@@ -454,6 +454,59 @@ int brisk_hip_match_radius_device(brisk_hip_ctx* ctx, const uint8_t* d_query, in
                                   int t_pitch, int dim_bytes, float max_distance, int cap_per_query, brisk_hip_dmatch* d_out,
                                   int* d_out_count, void* stream);
 
+/* ---- the same two pair matchers behind a position gate -----------------------------------------------------------------
+ * How the two pair forms are matched in practice: left against right inside an epipolar band (a few rows of dy, a disparity
+ * range of dx), a frame against the previous one inside a search window around each keypoint, often with a limit on the
+ * distance between pyramid layers.  The reference's matcher expresses this as a u8 mask per train image
+ * (brisk_hip_match_knn / _radius); for the pairs of a batch the mask is a PREDICATE on the two rows' keypoints, evaluated
+ * inside the kernels - and a train row that none of a wavefront's 64 neighbouring query rows may match costs neither its
+ * descriptor loads nor its bit counts.
+ * The keypoints that belong to the rows of a brisk_hip_desc_set: frame f's record r (28 bytes, brisk_hip_keypoint) at
+ * (const char*)d_kps + f * frame_pitch + r * sizeof(brisk_hip_keypoint); DEVICE memory, d_kps and frame_pitch multiples of 4.
+ * Only x, y and octave are read. */
+typedef struct brisk_hip_kp_set {
+  const brisk_hip_keypoint* d_kps;
+  long frame_pitch; /* bytes */
+} brisk_hip_kp_set;
+/* query row q (keypoint Q) and train row t (keypoint T) may match iff
+ *   dx_min <= T.x - Q.x <= dx_max  and  dy_min <= T.y - Q.y <= dy_max      (one IEEE fp32 subtraction each, then
+ *   and (max_octave_diff < 0  or  |T.octave - Q.octave| <= max_octave_diff)   fp32 compares; no contraction)
+ * -INFINITY / +INFINITY switch a bound off.  A NaN coordinate or bound makes the compare false: not allowed.
+ * A stereo band: {-64, 0, -2, 2, -1}; a tracking window: {-40, 40, -40, 40, 1}; everything: {-INF, +INF, -INF, +INF, -1}. */
+typedef struct brisk_hip_match_gate {
+  float dx_min, dx_max, dy_min, dy_max;
+  int max_octave_diff;
+} brisk_hip_match_gate;
+/* The DESCRIBED keypoints of the context's last batch, row for row with brisk_hip_batch_desc_set's descriptors; lifetime
+ * and errors as brisk_hip_batch_desc_set. */
+int brisk_hip_batch_kp_set(brisk_hip_ctx* ctx, brisk_hip_kp_set* kps);
+/* brisk_hip_match_knn_pairs_device / brisk_hip_match_radius_pairs_device with the mask M[q][t] = gate(Qkp[a][q], Tkp[b][t])
+ * per pair (a, b).  Everything not named here is exactly as in the ungated call of the same name: pair forms, d_pair_rows,
+ * rows_cap, untouched memory, bad entries of d_pairs, descriptor sizes, error codes (all checked before anything is
+ * launched), asynchronous on `stream`, no workspace.  Additional BRISK_HIP_ERR_ARG with npairs > 0: NULL query_kps /
+ * train_kps / gate, a NULL or misaligned d_kps, a frame_pitch that is negative or no multiple of 4.
+ * Radius: row [p][q] and its count are what brisk_hip_match_radius returns for frame a's rows, frame b's rows as the one
+ *   train image and mask M: the allowed train rows with (float)d < max_distance in (distance, trainIdx) order, count =
+ *   matches found.
+ * k-NN (k = 1, 2): the min(k, allowed(q)) smallest (distance, trainIdx) keys among the allowed train rows;
+ *   d_out_count[p][q] = that number (0: nothing allowed; entries behind the count are not written).
+ *   DEVIATION FROM THE REFERENCE, on purpose: a gated row is NEVER topped up.  With a mask the reference's top-up entry
+ *   (distance 2147483648.f, brute-force-matcher.cc:139-153) names the first train row that is masked or already taken - an
+ *   accident nobody can use.  The gated row is brisk_hip_match_knn's row for mask M without the entries of that distance;
+ *   so an all-pass gate gives the ungated call's rows except the top-up entry of 0 < n_b < k.
+ * cross_check (k == 1): row q's match t is kept iff the best ALLOWED match of row t among all rows q' of frame a (M[q'][t],
+ *   same (distance, index) order) is q. */
+int brisk_hip_match_knn_pairs_gated_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                           const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                           const brisk_hip_match_gate* gate, const brisk_hip_pair_spec* pairs, int dim_bytes, int k,
+                                           int cross_check, int rows_cap, brisk_hip_dmatch* d_out, int* d_out_count, int* d_pair_rows,
+                                           void* stream);
+int brisk_hip_match_radius_pairs_gated_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                              const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                              const brisk_hip_match_gate* gate, const brisk_hip_pair_spec* pairs, int dim_bytes,
+                                              float max_distance, int cap_per_query, int rows_cap, brisk_hip_dmatch* d_out,
+                                              int* d_out_count, int* d_pair_rows, void* stream);
+
 /* ---- per-stage timing: HIP events recorded on the launch stream around every kernel of the batch path ---- */
 int brisk_hip_profile_enable(brisk_hip_ctx* ctx, int enable);       /* resets the accumulated calls */
 int brisk_hip_profile_stages(void);                                 /* number of stages */

@@ -14,9 +14,20 @@ With --radius R [--cap N] the same three windows for radius matching (profiles/m
   C  detect_describe_batch, synchronise, download every frame's rows, one brisk_hip_match_radius call per pair (host pointers:
      each call uploads its rows again) - the only way there was before the radius pair call
 plus the threshold, the cap, the hits per query row (mean, max) and the share of rows that took the kernel's dense path.
-Usage: python tools/bench_match_pairs.py [--repeats 5] [--window 0.4] [--rows-cap 2048] [--radius R [--cap N]] [--out FILE]
-       --stats-pass: warm-up + a few B iterations only, nothing written (the run a `rocprofv3 --kernel-trace --stats` pass wraps;
-       its kernel statistics are kept as profiles/match_pairs_kernel_stats.csv)"""
+With --gate dx_min,dx_max,dy_min,dy_max[,octaves] (with and without --radius) five windows instead of three
+(profiles/match_pairs_gated.json / profiles/match_radius_pairs_gated.json):
+  B  as above - the UNGATED pair call
+  G  detect_describe_batch + the gated pair call with the given gate (brisk_hip_match_knn_pairs_gated_device /
+     brisk_hip_match_radius_pairs_gated_device, keypoints from brisk_hip_batch_kp_set)
+  I  the same with the all-pass gate (-inf, +inf, -inf, +inf, -1): what the predicate costs when it rejects nothing
+  C  what a caller had to do before: synchronise, download every frame's keypoints and rows, build the mask of every pair on
+     the host, one brisk_hip_match_knn / brisk_hip_match_radius call with that mask per pair
+plus, computed on the host from the downloaded keypoints: the share of (64-query wave, train row) steps in which no lane is
+allowed (the steps the gated kernels skip), the share of query rows with no allowed row, the mask density, and whether G's rows
+equal C's (k-NN: C's rows without the reference's top-up entries of distance 2147483648, which the gated call never writes).
+Usage: python tools/bench_match_pairs.py [--repeats 5] [--window 0.4] [--rows-cap 2048] [--radius R [--cap N]] [--gate ...] [--out FILE]
+       --stats-pass: warm-up + a few B iterations (with --gate: B, G and I) only, nothing written (the run a
+       `rocprofv3 --kernel-trace --stats` pass wraps; its kernel statistics are kept as profiles/match_pairs_kernel_stats.csv)"""
 import argparse
 import ctypes as C
 import json
@@ -58,13 +69,20 @@ def main():
     ap.add_argument("--k", type=int, default=2)
     ap.add_argument("--radius", type=float, default=None, help="radius matching with this max_distance instead of k-NN")
     ap.add_argument("--cap", type=int, default=8, help="cap_per_query of the radius calls")
-    ap.add_argument("--out", default=None, help="default: profiles/match_pairs.json, with --radius profiles/match_radius_pairs.json")
+    ap.add_argument("--gate", default=None, help="dx_min,dx_max,dy_min,dy_max[,max_octave_diff]: adds the gated windows G, I and the masked C")
+    ap.add_argument("--out", default=None, help="default: profiles/match_pairs.json, with --radius profiles/match_radius_pairs.json, "
+                                                "with --gate the same names ending in _gated.json")
     ap.add_argument("--stats-pass", action="store_true")
     a = ap.parse_args()
 
     radius = a.radius
+    gate = None
+    if a.gate is not None:
+        g = [float(v) for v in a.gate.split(",")]
+        gate = (g[0], g[1], g[2], g[3], int(g[4]) if len(g) > 4 else -1)
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "match_radius_pairs.json" if radius is not None else "match_pairs.json")
+        a.out = os.path.join(ROOT, "profiles", ("match_radius_pairs" if radius is not None else "match_pairs") +
+                             ("_gated" if gate else "") + ".json")
     n, k, cap = a.batch, (a.cap if radius is not None else a.k), a.rows_cap   # (k: entries per row of the match buffers)
     LIST = 32                                  # MRP_LIST of brisk_match.hip: rows with more hits take the dense path
     dev = torch.device("cuda", 0)
@@ -80,7 +98,7 @@ def main():
     st = work.cuda_stream
     spec = B.PairSpec(n - 1, 1, 1, 0, 1, None)   # frame to previous frame
     outs = {v: (torch.zeros((n - 1, cap, k, 4), dtype=torch.int32, device=dev), torch.zeros((n - 1, cap), dtype=torch.int32, device=dev),
-                torch.zeros(n - 1, dtype=torch.int32, device=dev)) for v in "BC"}
+                torch.zeros(n - 1, dtype=torch.int32, device=dev)) for v in "BCGI"}
 
     def batch():
         ctx.detect_describe_batch(ext, frames.data_ptr(), n, W, H, W * H, W, THRESHOLD, OCTAVES, st)
@@ -95,6 +113,17 @@ def main():
             ctx.match_radius_pairs(dset, dset, spec, radius, k, rows_cap=cap, stream=st, dim_bytes=dim, out=outs["B"])
         else:
             ctx.match_knn_pairs(dset, dset, spec, k, rows_cap=cap, stream=st, dim_bytes=dim, out=outs["B"])
+
+    def run_gated(which, g):
+        batch()
+        dset, dim = ctx.batch_desc_set()
+        kps = ctx.batch_kp_set()
+        if radius is not None:
+            ctx.match_radius_pairs(dset, dset, spec, radius, k, rows_cap=cap, stream=st, dim_bytes=dim, out=outs[which], gate=g, query_kps=kps,
+                                   train_kps=kps)
+        else:
+            ctx.match_knn_pairs(dset, dset, spec, k, rows_cap=cap, stream=st, dim_bytes=dim, out=outs[which], gate=g, query_kps=kps,
+                                train_kps=kps)
 
     vp = C.c_void_p
 
@@ -139,28 +168,95 @@ def main():
                          float(radius), k, host_c["m"][p].ctypes.data, host_c["cnt"][p].ctypes.data))
         host_c["rows"] = counts[1:].copy()
 
+    def gate_mask(kq, kt):
+        """the mask the gate defines, in float32 as the header states it"""
+        with np.errstate(invalid="ignore"):
+            dx, dy = kt["x"][None, :] - kq["x"][:, None], kt["y"][None, :] - kq["y"][:, None]
+            m = (dx >= np.float32(gate[0])) & (dx <= np.float32(gate[1])) & (dy >= np.float32(gate[2])) & (dy <= np.float32(gate[3]))
+        if gate[4] >= 0:
+            m &= np.abs(kt["octave"][None, :].astype(np.int64) - kq["octave"][:, None]) <= gate[4]
+        return m
+
+    gate_stats = {"steps": 0, "skipped": 0, "rows": 0, "rows_nothing_allowed": 0, "allowed": 0, "cells": 0}
+
+    def run_c_gated(stats=False):
+        batch()
+        torch.cuda.synchronize()
+        d_n, d_kps, d_desc, cstride, kcap, pitch = vp(), vp(), vp(), C.c_int(), C.c_int(), C.c_int()
+        ctx.check(ctx._L.brisk_hip_batch_results(ctx._h, None, C.byref(d_n), C.byref(cstride), None, C.byref(d_kps), C.byref(d_desc),
+                                                 C.byref(kcap), C.byref(pitch)))
+        ints = cstride.value // 4
+        counts = torch.as_tensor(DeviceInts(d_n.value, (n - 1) * ints + 1), device=dev)[::ints].cpu().numpy()
+        fp, kfp = kcap.value * pitch.value, kcap.value * B.KEYPOINT.itemsize
+        rows_dev = torch.as_tensor(DeviceBytes(d_desc.value, n * fp), device=dev).view(n, fp)
+        kps_dev = torch.as_tensor(DeviceBytes(d_kps.value, n * kfp), device=dev).view(n, kfp)
+        desc = [rows_dev[f, :int(counts[f]) * pitch.value].cpu().numpy().reshape(-1, pitch.value) for f in range(n)]
+        kps = [kps_dev[f, :int(counts[f]) * B.KEYPOINT.itemsize].cpu().numpy().view(B.KEYPOINT) for f in range(n)]
+        L, h = ctx._L, ctx._h
+        one, pt, mp = np.zeros(1, np.int32), np.array([pitch.value], np.int32), np.zeros(1, np.int32)
+        for p in range(n - 1):
+            q, t = desc[p + 1], desc[p]
+            nq = min(len(q), cap)
+            one[0] = len(t)
+            m = np.ascontiguousarray(gate_mask(kps[p + 1][:nq], kps[p]).astype(np.uint8))
+            if stats and m.size:
+                for w0 in range(0, nq, 64):
+                    live = m[w0:w0 + 64].any(axis=0)
+                    gate_stats["steps"] += live.size
+                    gate_stats["skipped"] += int((~live).sum())
+                gate_stats["rows"] += nq
+                gate_stats["rows_nothing_allowed"] += int((m.sum(axis=1) == 0).sum())
+                gate_stats["allowed"] += int(m.sum())
+                gate_stats["cells"] += m.size
+            mp[0] = m.strides[0] if m.size else 0
+            tptr = (C.c_void_p * 1)(t.ctypes.data if len(t) else None)
+            mptr = (C.c_void_p * 1)(m.ctypes.data if m.size else None)
+            if radius is not None:
+                ctx.check(L.brisk_hip_match_radius(h, q.ctypes.data if nq else None, nq, pitch.value, 48, 1, tptr, one.ctypes.data,
+                                                   pt.ctypes.data, mptr, mp.ctypes.data, float(radius), k, host_c["m"][p].ctypes.data,
+                                                   host_c["cnt"][p].ctypes.data))
+            else:
+                ctx.check(L.brisk_hip_match_knn(h, q.ctypes.data if nq else None, nq, pitch.value, 48, 1, tptr, one.ctypes.data,
+                                                pt.ctypes.data, mptr, mp.ctypes.data, k, host_c["m"][p].ctypes.data,
+                                                host_c["cnt"][p].ctypes.data))
+        host_c["rows"] = counts[1:].copy()
+
     runs = {"A": run_a, "B": run_b, "C": run_c_radius if radius is not None else run_c}
-    for v in "ABCAB":                       # warm-up: buffers sized, the integral format settled on the stream's density
+    order = "ABC"
+    if gate:
+        g_given, g_all = B.MatchGate(*gate), B.MatchGate.all_pass()
+        runs.update({"G": lambda: run_gated("G", g_given), "I": lambda: run_gated("I", g_all), "C": run_c_gated})
+        order = "ABGIC"
+    for v in order + "AB":                  # warm-up: buffers sized, the integral format settled on the stream's density
         runs[v]()
         torch.cuda.synchronize()
     if a.stats_pass:
         for _ in range(8):
-            run_b()
+            for v in ("BGI" if gate else "B"):
+                runs[v]()
         torch.cuda.synchronize()
         return
 
-    # B's rows against C's: the same matches, row for row (imgIdx aside: the pair call writes the train frame's index, the
-    # one-pair call knows of one train image only and writes 0)
-    for v in "BC":
-        for t in outs[v]:
-            t.zero_()
-        runs[v]()
-        torch.cuda.synchronize()
-    if radius is not None:   # variant C wrote host arrays: into the device triple the comparison below reads
+    # B's rows against C's (with --gate: G's against the masked C's): the same matches, row for row (imgIdx aside: the pair call
+    # writes the train frame's index, the one-pair call knows of one train image only and writes 0)
+    dev_v = "G" if gate else "B"
+    for t in outs[dev_v] + outs["C"]:
+        t.zero_()
+    runs[dev_v]()
+    torch.cuda.synchronize()
+    if gate:
+        run_c_gated(stats=True)
+        if radius is None:   # the reference's top-up entries (distance 2147483648, sorted last) are not part of a gated row
+            real = (host_c["m"]["distance"] != np.float32(2147483648.0)) & (np.arange(k)[None, None, :] < host_c["cnt"][:, :, None])
+            host_c["cnt"] = real.sum(axis=2).astype(np.int32)
+    else:
+        runs["C"]()
+    torch.cuda.synchronize()
+    if radius is not None or gate:   # variant C wrote host arrays: into the device triple the comparison below reads
         outs["C"][0].copy_(torch.from_numpy(host_c["m"].view(np.int32).reshape(n - 1, cap, k, 4)))
         outs["C"][1].copy_(torch.from_numpy(host_c["cnt"]))
         outs["C"][2].copy_(torch.from_numpy(host_c["rows"]))
-    (mb, cb, rb), (mc, cc, rc) = outs["B"], outs["C"]
+    (mb, cb, rb), (mc, cc, rc) = outs[dev_v], outs["C"]
     valid = torch.arange(cap, device=dev)[None, :] < rb[:, None]
     sel = valid[:, :, None] & (torch.arange(k, device=dev)[None, None, :] < cb[:, :, None])   # the entries a row's count covers
     pidx = torch.arange(n - 1, device=dev, dtype=torch.int32)[:, None, None].expand(-1, cap, k)
@@ -169,9 +265,9 @@ def main():
     rows_host = rb.cpu().numpy()
     hits = cb[valid].cpu().numpy()             # per query row: k-NN entries, or radius matches FOUND
 
-    fps = {v: [] for v in "ABC"}
+    fps = {v: [] for v in order}
     for _ in range(a.repeats):
-        for v in "ABC":
+        for v in order:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             calls = 0
@@ -183,24 +279,25 @@ def main():
             torch.cuda.synchronize()
             fps[v].append(calls * n / (time.perf_counter() - t0))
 
-    med = {v: float(np.median(fps[v])) for v in "ABC"}
-    ms = {v: 1e3 * n / med[v] for v in "ABC"}            # per batch
-    spread = {v: (max(fps[v]) - min(fps[v])) / med[v] for v in "ABC"}
+    med = {v: float(np.median(fps[v])) for v in order}
+    ms = {v: 1e3 * n / med[v] for v in order}            # per batch
+    spread = {v: (max(fps[v]) - min(fps[v])) / med[v] for v in order}
     res = {
         "workload": "bench.py's stream: %dx%d, threshold %d, %d octaves, %d frames per batch (%d distinct) in HBM; frame-to-previous-frame, "
                     "%s, rows_cap %d" % (W, H, THRESHOLD, OCTAVES, n, nd,
                                          ("max_distance %g, cap_per_query %d" % (radius, k)) if radius is not None else "k = %d" % k, cap),
         "kernel_revision": ctx.kernel_revision(),
         "device": torch.cuda.get_device_name(0),
-        "windows": {"repeats": a.repeats, "seconds_each": a.window, "order": "A, B, C alternating; every window ends in a synchronise"},
-        "frames_per_s": {v: round(med[v], 1) for v in "ABC"},
-        "frames_per_s_all": {v: [round(x, 1) for x in fps[v]] for v in "ABC"},
-        "spread_rel": {v: round(spread[v], 4) for v in "ABC"},
-        "ms_per_batch": {v: round(ms[v], 4) for v in "ABC"},
+        "windows": {"repeats": a.repeats, "seconds_each": a.window,
+                    "order": ", ".join(order) + " alternating; every window ends in a synchronise"},
+        "frames_per_s": {v: round(med[v], 1) for v in order},
+        "frames_per_s_all": {v: [round(x, 1) for x in fps[v]] for v in order},
+        "spread_rel": {v: round(spread[v], 4) for v in order},
+        "ms_per_batch": {v: round(ms[v], 4) for v in order},
         "matching_ms_per_batch": {"B_minus_A": round(ms["B"] - ms["A"], 4), "C_minus_A": round(ms["C"] - ms["A"], 4)},
         "B_over_C_frames_per_s": round(med["B"] / med["C"], 4),
         "matching_share_of_chunk_B": round((ms["B"] - ms["A"]) / ms["A"], 4),
-        "rows_identical_B_C": identical,
+        ("rows_identical_G_C" if gate else "rows_identical_B_C"): identical,
         "rows_per_pair": {"mean": round(float(rows_host.mean()), 1), "max": int(rows_host.max()), "cut_pairs": int((rows_host > cap).sum())},
         "legend": {"A": "detect_describe_batch", "B": "A + brisk_hip_match_knn_pairs_device on the same stream",
                    "C": "A, synchronise, counts to the host, one brisk_hip_match_knn_device call per pair"},
@@ -213,6 +310,27 @@ def main():
                                        "rows_without_a_hit": round(float((hits == 0).mean()), 4),
                                        "rows_over_the_cap": round(float((hits > k).mean()), 6)},
                     "dense_path_share_of_rows": round(float((hits > LIST).mean()), 6), "dense_path_list_keys": LIST})
+    if gate:
+        ms_spread = {v: ms[v] * spread[v] for v in order}   # the spread of a window's frames/s as milliseconds per batch
+        res["legend"].update({"B": res["legend"]["B"] + " (the UNGATED call)",
+                              "G": "A + the gated pair call with the given gate on the same stream",
+                              "I": "A + the gated pair call with the all-pass gate",
+                              "C": "A, synchronise, every frame's keypoints and rows to the host, the pair's mask built there, one "
+                                   "brisk_hip_match_%s call with that mask per pair" % ("radius" if radius is not None else "knn")})
+        res["matching_ms_per_batch"].update({"G_minus_A": round(ms["G"] - ms["A"], 4), "I_minus_A": round(ms["I"] - ms["A"], 4)})
+        res.update({
+            "gate": {"dx_min": gate[0], "dx_max": gate[1], "dy_min": gate[2], "dy_max": gate[3], "max_octave_diff": gate[4]},
+            "gate_on_the_bench_frames": {
+                "mask_density": round(gate_stats["allowed"] / max(gate_stats["cells"], 1), 6),
+                "wave_row_steps_without_an_allowed_lane": round(gate_stats["skipped"] / max(gate_stats["steps"], 1), 4),
+                "query_rows_with_no_allowed_row": round(gate_stats["rows_nothing_allowed"] / max(gate_stats["rows"], 1), 4)},
+            "G_against_B": {"added_ms_G": round(ms["G"] - ms["A"], 4), "added_ms_B": round(ms["B"] - ms["A"], 4),
+                            "G_minus_B_ms": round(ms["G"] - ms["B"], 4),
+                            "spread_ms_B_plus_G": round(ms_spread["B"] + ms_spread["G"], 4),
+                            "bar_met": bool(ms["G"] - ms["B"] <= ms_spread["B"] + ms_spread["G"])},
+            "I_against_B": {"added_ms_I": round(ms["I"] - ms["A"], 4), "I_minus_B_ms": round(ms["I"] - ms["B"], 4),
+                            "added_ratio_I_over_B": round((ms["I"] - ms["A"]) / max(ms["B"] - ms["A"], 1e-9), 4)},
+            "G_over_C_frames_per_s": round(med["G"] / med["C"], 4)})
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
