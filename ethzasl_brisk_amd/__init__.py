@@ -512,6 +512,23 @@ class Context:
             train_kps = own if train_kps is None else train_kps
         return C.byref(query_kps), C.byref(train_kps), C.byref(gate)
 
+    def _pairs_prologue(self, pairs, dim_bytes, rows_cap, per_row, out):
+        """what the pair matchers share: dim_bytes None = the last batch's descriptor size, rows_cap None = the context's keypoint
+        capacity, out None = new (uninitialised) device tensors (matches [npairs, rows_cap, per_row, 4], counts, pair_rows)"""
+        import torch
+        if dim_bytes is None:
+            dim_bytes = self.batch_desc_set()[1]
+        if rows_cap is None:
+            cap = C.c_int()
+            self.check(self._L.brisk_hip_batch_results(self._h, None, None, None, None, None, None, C.byref(cap), None))
+            rows_cap = cap.value
+        if out is None:
+            n, dev = max(pairs.npairs, 0), "cuda:%d" % self.device
+            out = (torch.empty((n, max(rows_cap, 0), max(per_row, 1), 4), dtype=torch.int32, device=dev),
+                   torch.empty((n, max(rows_cap, 0)), dtype=torch.int32, device=dev),
+                   torch.empty(n, dtype=torch.int32, device=dev))
+        return dim_bytes, rows_cap, out
+
     def match_knn_pairs(self, query, train, pairs, k, cross_check=False, rows_cap=None, stream=None, dim_bytes=None, out=None,
                         download=False, gate=None, query_kps=None, train_kps=None):
         """brisk_hip_match_knn_pairs_device.  query / train: DescSet; pairs: PairSpec.  rows_cap None = the context's keypoint
@@ -522,18 +539,8 @@ class Context:
         gate (a MatchGate): brisk_hip_match_knn_pairs_gated_device - only rows whose keypoints (query_kps / train_kps: KpSet, None =
         the last batch's) pass the gate are matched, and a row holds real matches only (no top-up entry)."""
         import torch
-        if dim_bytes is None:
-            dim_bytes = self.batch_desc_set()[1]
-        if rows_cap is None:
-            cap = C.c_int()
-            self.check(self._L.brisk_hip_batch_results(self._h, None, None, None, None, None, None, C.byref(cap), None))
-            rows_cap = cap.value
         n = pairs.npairs
-        if out is None:
-            dev = "cuda:%d" % self.device
-            out = (torch.empty((max(n, 0), max(rows_cap, 0), max(k, 1), 4), dtype=torch.int32, device=dev),
-                   torch.empty((max(n, 0), max(rows_cap, 0)), dtype=torch.int32, device=dev),
-                   torch.empty(max(n, 0), dtype=torch.int32, device=dev))
+        dim_bytes, rows_cap, out = self._pairs_prologue(pairs, dim_bytes, rows_cap, k, out)
         m, cnt, rows = out
         if gate is not None:
             self.check(self._L.brisk_hip_match_knn_pairs_gated_device(self._h, C.byref(query), C.byref(train),
@@ -560,18 +567,8 @@ class Context:
         per pair the list of per-query DMATCH arrays cut to min(count, cap_per_query), and per pair the counts of those rows.
         gate / query_kps / train_kps as in match_knn_pairs: brisk_hip_match_radius_pairs_gated_device."""
         import torch
-        if dim_bytes is None:
-            dim_bytes = self.batch_desc_set()[1]
-        if rows_cap is None:
-            cap = C.c_int()
-            self.check(self._L.brisk_hip_batch_results(self._h, None, None, None, None, None, None, C.byref(cap), None))
-            rows_cap = cap.value
         n, cpq = pairs.npairs, int(cap_per_query)
-        if out is None:
-            dev = "cuda:%d" % self.device
-            out = (torch.empty((max(n, 0), max(rows_cap, 0), max(cpq, 1), 4), dtype=torch.int32, device=dev),
-                   torch.empty((max(n, 0), max(rows_cap, 0)), dtype=torch.int32, device=dev),
-                   torch.empty(max(n, 0), dtype=torch.int32, device=dev))
+        dim_bytes, rows_cap, out = self._pairs_prologue(pairs, dim_bytes, rows_cap, cpq, out)
         m, cnt, rows = out
         if gate is not None:
             self.check(self._L.brisk_hip_match_radius_pairs_gated_device(self._h, C.byref(query), C.byref(train),

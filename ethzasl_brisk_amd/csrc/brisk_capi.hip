@@ -1983,88 +1983,6 @@ int brisk_hip_batch_desc_set(brisk_hip_ctx* ctx, brisk_hip_desc_set* set, int* d
   return BRISK_HIP_OK;
 }
 
-static const char* match_pairs_check_set(const brisk_hip_desc_set* s, int dim_bytes) {
-  if (!s->d_desc || !s->d_counts) return "match_pairs: a descriptor set without rows or counts";
-  if (s->frames <= 0 || s->count_stride <= 0 || s->frame_pitch < 0) return "match_pairs: bad descriptor set geometry";
-  if (s->row_pitch < dim_bytes) return "match_pairs: pitch smaller than the descriptor";
-  return nullptr;
-}
-
-int brisk_hip_match_knn_pairs_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
-                                     const brisk_hip_pair_spec* pairs, int dim_bytes, int k, int cross_check, int rows_cap,
-                                     brisk_hip_dmatch* d_out, int* d_out_count, int* d_pair_rows, void* stream) {
-  if (!ctx) return BRISK_HIP_ERR_ARG;
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  if (!query || !train || !pairs || pairs->npairs < 0) return fail(ctx, BRISK_HIP_ERR_ARG, "match_pairs: bad argument");
-  if (k < 1 || k > 2) return fail(ctx, BRISK_HIP_ERR_ARG, "match_pairs: k must be 1 or 2 (brisk_hip_match_knn for more)");
-  if (cross_check && k != 1) return fail(ctx, BRISK_HIP_ERR_ARG, "match_pairs: the cross check needs k == 1");
-  if (dim_bytes != 16 && dim_bytes != 32 && dim_bytes != 48 && dim_bytes != 64)
-    return fail(ctx, BRISK_HIP_ERR_UNSUPPORTED, "match_pairs: descriptor size must be 16, 32, 48 or 64 bytes (brisk_hip_match_knn_device for others)");
-  for (const brisk_hip_desc_set* s : {query, train})
-    if (const char* msg = match_pairs_check_set(s, dim_bytes)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
-  const int np = pairs->npairs;
-  if (np == 0) return BRISK_HIP_OK;
-  if (rows_cap <= 0 || !d_out || !d_out_count || !d_pair_rows) return fail(ctx, BRISK_HIP_ERR_ARG, "match_pairs: bad output argument");
-  if (!pairs->d_pairs) {  // (a list on the device is checked there: d_pair_rows = -1)
-    const long q0 = pairs->query_first, q1 = q0 + (long)(np - 1) * pairs->query_step;
-    const long t0 = pairs->train_first, t1 = t0 + (long)(np - 1) * pairs->train_step;
-    if (q0 < 0 || q0 >= query->frames || q1 < 0 || q1 >= query->frames || t0 < 0 || t0 >= train->frames || t1 < 0 || t1 >= train->frames)
-      return fail(ctx, BRISK_HIP_ERR_ARG, "match_pairs: a pair names a frame outside its set");
-  }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  // no workspace of the context is written, but the sets usually ARE the last batch's result buffers: the stream is ordered
-  // behind that batch, and the next batch (which overwrites them) behind this call
-  if (workspace_acquire(ctx, st)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
-  WorkspaceGuard guard(ctx, st);
-  const BriskDescSet Q{query->d_desc, query->d_counts, query->count_stride, query->frame_pitch, query->row_pitch, query->frames};
-  const BriskDescSet T{train->d_desc, train->d_counts, train->count_stride, train->frame_pitch, train->row_pitch, train->frames};
-  const BriskPairSpec P{np, pairs->query_first, pairs->query_step, pairs->train_first, pairs->train_step, pairs->d_pairs};
-  if (!brisk_launch_match_knn_pairs(Q, T, P, dim_bytes / 4, k, cross_check != 0, rows_cap, reinterpret_cast<BriskDMatch*>(d_out),
-                                    d_out_count, d_pair_rows, st))
-    return fail(ctx, BRISK_HIP_ERR_UNSUPPORTED, "match_pairs: descriptor size not covered");
-  HIPCHK(ctx, hipGetLastError());
-  if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
-  return BRISK_HIP_OK;
-}
-
-int brisk_hip_match_radius_pairs_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
-                                        const brisk_hip_pair_spec* pairs, int dim_bytes, float max_distance, int cap_per_query,
-                                        int rows_cap, brisk_hip_dmatch* d_out, int* d_out_count, int* d_pair_rows, void* stream) {
-  if (!ctx) return BRISK_HIP_ERR_ARG;
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  if (!pairs || pairs->npairs < 0) return fail(ctx, BRISK_HIP_ERR_ARG, "match_radius_pairs: bad argument");
-  if (cap_per_query < 1) return fail(ctx, BRISK_HIP_ERR_ARG, "match_radius_pairs: cap_per_query must be at least 1");
-  if (dim_bytes != 16 && dim_bytes != 32 && dim_bytes != 48 && dim_bytes != 64)
-    return fail(ctx, BRISK_HIP_ERR_UNSUPPORTED, "match_radius_pairs: descriptor size must be 16, 32, 48 or 64 bytes (brisk_hip_match_radius_device for others)");
-  const int np = pairs->npairs;
-  if (np == 0) return BRISK_HIP_OK;
-  if (!query || !train) return fail(ctx, BRISK_HIP_ERR_ARG, "match_radius_pairs: null descriptor set");
-  for (const brisk_hip_desc_set* s : {query, train})
-    if (const char* msg = match_pairs_check_set(s, dim_bytes)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
-  if (rows_cap < 1 || !d_out || !d_out_count || !d_pair_rows) return fail(ctx, BRISK_HIP_ERR_ARG, "match_radius_pairs: bad output argument");
-  if (!pairs->d_pairs) {  // (a list on the device is checked there: d_pair_rows = -1)
-    const long q0 = pairs->query_first, q1 = q0 + (long)(np - 1) * pairs->query_step;
-    const long t0 = pairs->train_first, t1 = t0 + (long)(np - 1) * pairs->train_step;
-    if (q0 < 0 || q0 >= query->frames || q1 < 0 || q1 >= query->frames || t0 < 0 || t0 >= train->frames || t1 < 0 || t1 >= train->frames)
-      return fail(ctx, BRISK_HIP_ERR_ARG, "match_radius_pairs: a pair names a frame outside its set");
-  }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  // (ordered behind the batch that wrote the sets and before the next one, as brisk_hip_match_knn_pairs_device)
-  if (workspace_acquire(ctx, st)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
-  WorkspaceGuard guard(ctx, st);
-  const BriskDescSet Q{query->d_desc, query->d_counts, query->count_stride, query->frame_pitch, query->row_pitch, query->frames};
-  const BriskDescSet T{train->d_desc, train->d_counts, train->count_stride, train->frame_pitch, train->row_pitch, train->frames};
-  const BriskPairSpec P{np, pairs->query_first, pairs->query_step, pairs->train_first, pairs->train_step, pairs->d_pairs};
-  if (!brisk_launch_match_radius_pairs(Q, T, P, dim_bytes / 4, max_distance, cap_per_query, rows_cap, reinterpret_cast<BriskDMatch*>(d_out),
-                                       d_out_count, d_pair_rows, st))
-    return fail(ctx, BRISK_HIP_ERR_UNSUPPORTED, "match_radius_pairs: descriptor size not covered");
-  HIPCHK(ctx, hipGetLastError());
-  if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
-  return BRISK_HIP_OK;
-}
-
 int brisk_hip_batch_kp_set(brisk_hip_ctx* ctx, brisk_hip_kp_set* kps) {
   if (!ctx) return BRISK_HIP_ERR_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
@@ -2076,6 +1994,12 @@ int brisk_hip_batch_kp_set(brisk_hip_ctx* ctx, brisk_hip_kp_set* kps) {
   return BRISK_HIP_OK;
 }
 
+static const char* match_pairs_check_set(const brisk_hip_desc_set* s, int dim_bytes) {
+  if (!s->d_desc || !s->d_counts) return "match_pairs: a descriptor set without rows or counts";
+  if (s->frames <= 0 || s->count_stride <= 0 || s->frame_pitch < 0) return "match_pairs: bad descriptor set geometry";
+  if (s->row_pitch < dim_bytes) return "match_pairs: pitch smaller than the descriptor";
+  return nullptr;
+}
 // the gated calls' own arguments (npairs > 0); the kernels read the records with 4-byte loads
 static const char* match_gated_check(const brisk_hip_kp_set* qk, const brisk_hip_kp_set* tk, const brisk_hip_match_gate* gate) {
   if (!qk || !tk || !gate) return "match_pairs_gated: null keypoint set or gate";
@@ -2086,6 +2010,113 @@ static const char* match_gated_check(const brisk_hip_kp_set* qk, const brisk_hip
   return nullptr;
 }
 
+// What the four pair matchers (k-NN and radius, each plain and gated) share.  An entry point runs its own checks and the shared
+// ones in ITS order - the k-NN forms look at the sets before npairs == 0 returns OK, the radius forms behind it - and ends in run().
+// name: "match_pairs" or "match_radius_pairs", the head of the messages; the keypoint sets and the gate: the gated forms only.
+extern "C++" {  // (a member template)
+struct PairCall {
+  brisk_hip_ctx* ctx;
+  const char* name;
+  const brisk_hip_desc_set *query, *train;
+  const brisk_hip_pair_spec* pairs;
+  int dim_bytes;
+  bool gated;
+  const brisk_hip_kp_set *query_kps, *train_kps;
+  const brisk_hip_match_gate* gate;
+
+  int err(int code, const char* what) const { return fail(ctx, code, (std::string(name) + ": " + what).c_str()); }
+  // other: where the ungated forms send the caller for other sizes
+  int check_dim(const char* other) const {
+    if (dim_bytes == 16 || dim_bytes == 32 || dim_bytes == 48 || dim_bytes == 64) return BRISK_HIP_OK;
+    return err(BRISK_HIP_ERR_UNSUPPORTED, (std::string("descriptor size must be 16, 32, 48 or 64 bytes") + (gated ? "" : other)).c_str());
+  }
+  int check_sets() const {
+    for (const brisk_hip_desc_set* s : {query, train})
+      if (const char* msg = match_pairs_check_set(s, dim_bytes)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
+    return BRISK_HIP_OK;
+  }
+  // npairs > 0, the sets checked: the gate's and the output arguments, the range of the arithmetic pair form, then
+  // launch(Q, T, P, QK, TK, G, out, stream) on the caller's stream or the context's
+  template <class Launch>
+  int run(int rows_cap, brisk_hip_dmatch* d_out, int* d_out_count, int* d_pair_rows, void* stream, Launch launch) const {
+    if (gated)
+      if (const char* msg = match_gated_check(query_kps, train_kps, gate)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
+    if (rows_cap < 1 || !d_out || !d_out_count || !d_pair_rows) return err(BRISK_HIP_ERR_ARG, "bad output argument");
+    const int np = pairs->npairs;
+    if (!pairs->d_pairs) {  // (a list on the device is checked there: d_pair_rows = -1)
+      const long q0 = pairs->query_first, q1 = q0 + (long)(np - 1) * pairs->query_step;
+      const long t0 = pairs->train_first, t1 = t0 + (long)(np - 1) * pairs->train_step;
+      if (q0 < 0 || q0 >= query->frames || q1 < 0 || q1 >= query->frames || t0 < 0 || t0 >= train->frames || t1 < 0 || t1 >= train->frames)
+        return err(BRISK_HIP_ERR_ARG, "a pair names a frame outside its set");
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    // no workspace of the context is written, but the sets usually ARE the last batch's result buffers: the stream is ordered
+    // behind that batch, and the next batch (which overwrites them) behind this call
+    if (workspace_acquire(ctx, st)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
+    WorkspaceGuard guard(ctx, st);
+    const BriskDescSet Q{query->d_desc, query->d_counts, query->count_stride, query->frame_pitch, query->row_pitch, query->frames};
+    const BriskDescSet T{train->d_desc, train->d_counts, train->count_stride, train->frame_pitch, train->row_pitch, train->frames};
+    const BriskPairSpec P{np, pairs->query_first, pairs->query_step, pairs->train_first, pairs->train_step, pairs->d_pairs};
+    BriskKpSet QK{}, TK{};
+    BriskMatchGate G{};
+    if (gated) {
+      QK = BriskKpSet{reinterpret_cast<const char*>(query_kps->d_kps), query_kps->frame_pitch};
+      TK = BriskKpSet{reinterpret_cast<const char*>(train_kps->d_kps), train_kps->frame_pitch};
+      G = BriskMatchGate{gate->dx_min, gate->dx_max, gate->dy_min, gate->dy_max, gate->max_octave_diff};
+    }
+    if (!launch(Q, T, P, QK, TK, G, reinterpret_cast<BriskDMatch*>(d_out), st)) return err(BRISK_HIP_ERR_UNSUPPORTED, "descriptor size not covered");
+    HIPCHK(ctx, hipGetLastError());
+    if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
+    return BRISK_HIP_OK;
+  }
+};
+}
+
+// k-NN: a null set and the sets' geometry are rejected before npairs == 0 returns OK
+static int match_knn_pairs_call(const PairCall& C, int k, int cross_check, int rows_cap, brisk_hip_dmatch* d_out, int* d_out_count,
+                                int* d_pair_rows, void* stream) {
+  if (!C.query || !C.train || !C.pairs || C.pairs->npairs < 0) return C.err(BRISK_HIP_ERR_ARG, "bad argument");
+  if (k < 1 || k > 2) return C.err(BRISK_HIP_ERR_ARG, "k must be 1 or 2 (brisk_hip_match_knn for more)");
+  if (cross_check && k != 1) return C.err(BRISK_HIP_ERR_ARG, "the cross check needs k == 1");
+  if (int rc = C.check_dim(" (brisk_hip_match_knn_device for others)")) return rc;
+  if (int rc = C.check_sets()) return rc;
+  if (C.pairs->npairs == 0) return BRISK_HIP_OK;
+  return C.run(rows_cap, d_out, d_out_count, d_pair_rows, stream,
+               [&](const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, const BriskKpSet& QK, const BriskKpSet& TK,
+                   const BriskMatchGate& G, BriskDMatch* out, hipStream_t st) {
+                 const bool cross = cross_check != 0;
+                 return C.gated ? brisk_launch_match_knn_pairs_gated(Q, T, QK, TK, G, P, C.dim_bytes / 4, k, cross, rows_cap, out, d_out_count, d_pair_rows, st)
+                                : brisk_launch_match_knn_pairs(Q, T, P, C.dim_bytes / 4, k, cross, rows_cap, out, d_out_count, d_pair_rows, st);
+               });
+}
+// radius: npairs == 0 returns OK before the sets are looked at
+static int match_radius_pairs_call(const PairCall& C, float max_distance, int cap_per_query, int rows_cap, brisk_hip_dmatch* d_out,
+                                   int* d_out_count, int* d_pair_rows, void* stream) {
+  if (!C.pairs || C.pairs->npairs < 0) return C.err(BRISK_HIP_ERR_ARG, "bad argument");
+  if (cap_per_query < 1) return C.err(BRISK_HIP_ERR_ARG, "cap_per_query must be at least 1");
+  if (int rc = C.check_dim(" (brisk_hip_match_radius_device for others)")) return rc;
+  if (C.pairs->npairs == 0) return BRISK_HIP_OK;
+  if (!C.query || !C.train) return C.err(BRISK_HIP_ERR_ARG, "null descriptor set");
+  if (int rc = C.check_sets()) return rc;
+  return C.run(rows_cap, d_out, d_out_count, d_pair_rows, stream,
+               [&](const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, const BriskKpSet& QK, const BriskKpSet& TK,
+                   const BriskMatchGate& G, BriskDMatch* out, hipStream_t st) {
+                 return C.gated ? brisk_launch_match_radius_pairs_gated(Q, T, QK, TK, G, P, C.dim_bytes / 4, max_distance, cap_per_query, rows_cap, out,
+                                                                        d_out_count, d_pair_rows, st)
+                                : brisk_launch_match_radius_pairs(Q, T, P, C.dim_bytes / 4, max_distance, cap_per_query, rows_cap, out, d_out_count,
+                                                                  d_pair_rows, st);
+               });
+}
+
+int brisk_hip_match_knn_pairs_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                     const brisk_hip_pair_spec* pairs, int dim_bytes, int k, int cross_check, int rows_cap,
+                                     brisk_hip_dmatch* d_out, int* d_out_count, int* d_pair_rows, void* stream) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  return match_knn_pairs_call({ctx, "match_pairs", query, train, pairs, dim_bytes, false, nullptr, nullptr, nullptr}, k, cross_check, rows_cap,
+                              d_out, d_out_count, d_pair_rows, stream);
+}
 int brisk_hip_match_knn_pairs_gated_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
                                            const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
                                            const brisk_hip_match_gate* gate, const brisk_hip_pair_spec* pairs, int dim_bytes, int k,
@@ -2093,43 +2124,17 @@ int brisk_hip_match_knn_pairs_gated_device(brisk_hip_ctx* ctx, const brisk_hip_d
                                            void* stream) {
   if (!ctx) return BRISK_HIP_ERR_ARG;
   std::lock_guard<std::mutex> lock(ctx->mu);
-  // (the checks of brisk_hip_match_knn_pairs_device in its order, the gate's own behind npairs == 0)
-  if (!query || !train || !pairs || pairs->npairs < 0) return fail(ctx, BRISK_HIP_ERR_ARG, "match_pairs: bad argument");
-  if (k < 1 || k > 2) return fail(ctx, BRISK_HIP_ERR_ARG, "match_pairs: k must be 1 or 2 (brisk_hip_match_knn for more)");
-  if (cross_check && k != 1) return fail(ctx, BRISK_HIP_ERR_ARG, "match_pairs: the cross check needs k == 1");
-  if (dim_bytes != 16 && dim_bytes != 32 && dim_bytes != 48 && dim_bytes != 64)
-    return fail(ctx, BRISK_HIP_ERR_UNSUPPORTED, "match_pairs: descriptor size must be 16, 32, 48 or 64 bytes");
-  for (const brisk_hip_desc_set* s : {query, train})
-    if (const char* msg = match_pairs_check_set(s, dim_bytes)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
-  const int np = pairs->npairs;
-  if (np == 0) return BRISK_HIP_OK;
-  if (const char* msg = match_gated_check(query_kps, train_kps, gate)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
-  if (rows_cap <= 0 || !d_out || !d_out_count || !d_pair_rows) return fail(ctx, BRISK_HIP_ERR_ARG, "match_pairs: bad output argument");
-  if (!pairs->d_pairs) {  // (a list on the device is checked there: d_pair_rows = -1)
-    const long q0 = pairs->query_first, q1 = q0 + (long)(np - 1) * pairs->query_step;
-    const long t0 = pairs->train_first, t1 = t0 + (long)(np - 1) * pairs->train_step;
-    if (q0 < 0 || q0 >= query->frames || q1 < 0 || q1 >= query->frames || t0 < 0 || t0 >= train->frames || t1 < 0 || t1 >= train->frames)
-      return fail(ctx, BRISK_HIP_ERR_ARG, "match_pairs: a pair names a frame outside its set");
-  }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  // (ordered behind the batch that wrote the sets and before the next one, as brisk_hip_match_knn_pairs_device)
-  if (workspace_acquire(ctx, st)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
-  WorkspaceGuard guard(ctx, st);
-  const BriskDescSet Q{query->d_desc, query->d_counts, query->count_stride, query->frame_pitch, query->row_pitch, query->frames};
-  const BriskDescSet T{train->d_desc, train->d_counts, train->count_stride, train->frame_pitch, train->row_pitch, train->frames};
-  const BriskKpSet QK{reinterpret_cast<const char*>(query_kps->d_kps), query_kps->frame_pitch};
-  const BriskKpSet TK{reinterpret_cast<const char*>(train_kps->d_kps), train_kps->frame_pitch};
-  const BriskMatchGate G{gate->dx_min, gate->dx_max, gate->dy_min, gate->dy_max, gate->max_octave_diff};
-  const BriskPairSpec P{np, pairs->query_first, pairs->query_step, pairs->train_first, pairs->train_step, pairs->d_pairs};
-  if (!brisk_launch_match_knn_pairs_gated(Q, T, QK, TK, G, P, dim_bytes / 4, k, cross_check != 0, rows_cap,
-                                          reinterpret_cast<BriskDMatch*>(d_out), d_out_count, d_pair_rows, st))
-    return fail(ctx, BRISK_HIP_ERR_UNSUPPORTED, "match_pairs: descriptor size not covered");
-  HIPCHK(ctx, hipGetLastError());
-  if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
-  return BRISK_HIP_OK;
+  return match_knn_pairs_call({ctx, "match_pairs", query, train, pairs, dim_bytes, true, query_kps, train_kps, gate}, k, cross_check, rows_cap,
+                              d_out, d_out_count, d_pair_rows, stream);
 }
-
+int brisk_hip_match_radius_pairs_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                        const brisk_hip_pair_spec* pairs, int dim_bytes, float max_distance, int cap_per_query,
+                                        int rows_cap, brisk_hip_dmatch* d_out, int* d_out_count, int* d_pair_rows, void* stream) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  return match_radius_pairs_call({ctx, "match_radius_pairs", query, train, pairs, dim_bytes, false, nullptr, nullptr, nullptr}, max_distance,
+                                 cap_per_query, rows_cap, d_out, d_out_count, d_pair_rows, stream);
+}
 int brisk_hip_match_radius_pairs_gated_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
                                               const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
                                               const brisk_hip_match_gate* gate, const brisk_hip_pair_spec* pairs, int dim_bytes,
@@ -2137,40 +2142,8 @@ int brisk_hip_match_radius_pairs_gated_device(brisk_hip_ctx* ctx, const brisk_hi
                                               int* d_out_count, int* d_pair_rows, void* stream) {
   if (!ctx) return BRISK_HIP_ERR_ARG;
   std::lock_guard<std::mutex> lock(ctx->mu);
-  // (the checks of brisk_hip_match_radius_pairs_device in its order, the gate's own behind npairs == 0)
-  if (!pairs || pairs->npairs < 0) return fail(ctx, BRISK_HIP_ERR_ARG, "match_radius_pairs: bad argument");
-  if (cap_per_query < 1) return fail(ctx, BRISK_HIP_ERR_ARG, "match_radius_pairs: cap_per_query must be at least 1");
-  if (dim_bytes != 16 && dim_bytes != 32 && dim_bytes != 48 && dim_bytes != 64)
-    return fail(ctx, BRISK_HIP_ERR_UNSUPPORTED, "match_radius_pairs: descriptor size must be 16, 32, 48 or 64 bytes");
-  const int np = pairs->npairs;
-  if (np == 0) return BRISK_HIP_OK;
-  if (!query || !train) return fail(ctx, BRISK_HIP_ERR_ARG, "match_radius_pairs: null descriptor set");
-  for (const brisk_hip_desc_set* s : {query, train})
-    if (const char* msg = match_pairs_check_set(s, dim_bytes)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
-  if (const char* msg = match_gated_check(query_kps, train_kps, gate)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
-  if (rows_cap < 1 || !d_out || !d_out_count || !d_pair_rows) return fail(ctx, BRISK_HIP_ERR_ARG, "match_radius_pairs: bad output argument");
-  if (!pairs->d_pairs) {  // (a list on the device is checked there: d_pair_rows = -1)
-    const long q0 = pairs->query_first, q1 = q0 + (long)(np - 1) * pairs->query_step;
-    const long t0 = pairs->train_first, t1 = t0 + (long)(np - 1) * pairs->train_step;
-    if (q0 < 0 || q0 >= query->frames || q1 < 0 || q1 >= query->frames || t0 < 0 || t0 >= train->frames || t1 < 0 || t1 >= train->frames)
-      return fail(ctx, BRISK_HIP_ERR_ARG, "match_radius_pairs: a pair names a frame outside its set");
-  }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  if (workspace_acquire(ctx, st)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
-  WorkspaceGuard guard(ctx, st);
-  const BriskDescSet Q{query->d_desc, query->d_counts, query->count_stride, query->frame_pitch, query->row_pitch, query->frames};
-  const BriskDescSet T{train->d_desc, train->d_counts, train->count_stride, train->frame_pitch, train->row_pitch, train->frames};
-  const BriskKpSet QK{reinterpret_cast<const char*>(query_kps->d_kps), query_kps->frame_pitch};
-  const BriskKpSet TK{reinterpret_cast<const char*>(train_kps->d_kps), train_kps->frame_pitch};
-  const BriskMatchGate G{gate->dx_min, gate->dx_max, gate->dy_min, gate->dy_max, gate->max_octave_diff};
-  const BriskPairSpec P{np, pairs->query_first, pairs->query_step, pairs->train_first, pairs->train_step, pairs->d_pairs};
-  if (!brisk_launch_match_radius_pairs_gated(Q, T, QK, TK, G, P, dim_bytes / 4, max_distance, cap_per_query, rows_cap,
-                                             reinterpret_cast<BriskDMatch*>(d_out), d_out_count, d_pair_rows, st))
-    return fail(ctx, BRISK_HIP_ERR_UNSUPPORTED, "match_radius_pairs: descriptor size not covered");
-  HIPCHK(ctx, hipGetLastError());
-  if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
-  return BRISK_HIP_OK;
+  return match_radius_pairs_call({ctx, "match_radius_pairs", query, train, pairs, dim_bytes, true, query_kps, train_kps, gate}, max_distance,
+                                 cap_per_query, rows_cap, d_out, d_out_count, d_pair_rows, stream);
 }
 
 int brisk_hip_match_radius_device(brisk_hip_ctx* ctx, const uint8_t* d_query, int nq, int q_pitch, const uint8_t* d_train, int nt,

@@ -2,14 +2,34 @@
 //
 // Replaces brisk::BruteForceMatcher::commonKnnMatchImpl / commonRadiusMatchImpl
 // (brisk/src/brute-force-matcher.cc:80-213) with brisk::Hamming (brisk/include/brisk/internal/hamming.h:98-112)
-// as the distance: popcount of a ^ b over size / 16 128-bit words.  Integer work, HBM/L2-bound, no MFMA:
-//   k_match_dist    u16 distance matrix of a block of queries against all train descriptors (all train images
-//                   concatenated in image order); 0xFFFF = the reference's INT_MAX (masked pair)
-//   k_match_knn     one wave per query: k rounds of "first minimum" selection, as the reference does
-//   k_match_radius  one wave per query: distance histogram in LDS, then stable placement by (distance, image,
-//                   train index)
+// as the distance: popcount of a ^ b over size / 16 128-bit words.  Integer work, HBM/L2-bound, no MFMA.
+//
+// Matrix path (any descriptor size up to 224 bytes, several train images, masks):
+//   k_match_dist        u16 distance matrix of a block of queries against all train descriptors (all train images
+//                       concatenated in image order); 0xFFFF = the reference's INT_MAX (masked pair)
+//   k_match_masked_out  the queries that every image's mask forbids
+//   k_match_knn         one wave per query: k rounds of "first minimum" selection, as the reference does
+//   k_match_radius      one wave per query: distance histogram in LDS, then stable placement by (distance, image,
+//                       train index)
+//
+// Register-row path (descriptors of 16, 32, 48 or 64 bytes, one train set, no masks, no distance matrix): 64 queries per
+// workgroup, one per lane with its descriptor in registers; each wave walks a slice of the train rows through wave-uniform
+// (scalar) loads and XORs them against the lane's registers.  A candidate is one packed key, distance << 22 | train row.
+// The shared pieces, each written once: mp_resolve (a workgroup's pair, counts, frame pointers, alignment), mp_load_row and
+// m_dist (a row into registers, a register row against a memory row), the scans mp_scan / mrp_scan and their gated forms
+// mpg_scan / mrpg_scan (chosen once per slice by mp_scan_slice / mrp_body), m_top2 and m_merge (the two smallest keys, and
+// the per-wave lists of a workgroup merged through LDS), m_dispatch_words and mp_launch_pairs on the host.
+//   k_match_knn_fused           k <= 2, one query set against one train set, 16 waves per workgroup
+//   k_match_knn_pairs[_gated]   k <= 2 for the frame pairs of a batch in one launch (mp_body), with the cross check fused;
+//                               gated: only rows whose keypoints pass brisk_match_gate.h's predicate, no top-up entry
+//   k_match_radius_pairs[_gated], k_match_radius_pairs_one
+//                               radius matching in the same shape (mrp_body): hits collected in a short LDS list per
+//                               query and ranked; a query with more hits than the list holds is redone by one wave
+//                               with k_match_radius' histogram and placement (mrp_dense)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "brisk_kernels.h"
 
@@ -208,115 +228,23 @@ __global__ void __launch_bounds__(64) k_match_radius(const uint16_t* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------
-// Fused k-NN for k <= 2, one train set, no masks (the frame-to-frame / frame-to-map case): no distance matrix.
-// Workgroup = 64 queries (one per lane, descriptor in registers) x MF_WAVES waves; wave w scans the w-th slice of
-// the train set, whose descriptors are wave-uniform (scalar loads, XOR against SGPRs); per pair 2 x W32 VALU
-// (v_xor + v_bcnt with accumulate) and a 3-instruction top-2 update on packed keys (distance << 22 | train
-// index).  The MF_WAVES partial top-2 lists of a query are merged through LDS.
+// The register-row path: what its kernels share.
 // ------------------------------------------------------------------------------------------------
 #define MF_WAVES 16
 #define MF_IDX_BITS 22
-template <int W32>
-__global__ void __launch_bounds__(MF_WAVES * 64) k_match_knn_fused(const uint8_t* __restrict__ query, int q_pitch, int nq,
-                                                                    const uint8_t* __restrict__ train, int t_pitch, int nt,
-                                                                    int k, BriskDMatch* __restrict__ out,
-                                                                    int* __restrict__ out_count) {
-  __shared__ unsigned part[MF_WAVES][2][64];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int q = blockIdx.x * 64 + lane;
-  unsigned qv[W32];
-  {
-    const uint8_t* p = query + (long)min(q, nq - 1) * q_pitch;
-#pragma unroll
-    for (int w = 0; w < W32; ++w)  // (byte loads: no alignment assumption on caller rows)
-      qv[w] = (unsigned)p[4 * w] | ((unsigned)p[4 * w + 1] << 8) | ((unsigned)p[4 * w + 2] << 16) | ((unsigned)p[4 * w + 3] << 24);
-  }
-  const int per = (nt + MF_WAVES - 1) / MF_WAVES;
-  const int t0 = __builtin_amdgcn_readfirstlane(wave * per), t1 = min(nt, t0 + per);
-  unsigned b1 = 0xFFFFFFFFu, b2 = 0xFFFFFFFFu;
-  const bool aligned = (((uintptr_t)train | (unsigned)t_pitch) & 3) == 0;
-  if (aligned) {
-    for (int t = t0; t < t1; ++t) {
-      const unsigned* tp = reinterpret_cast<const unsigned*>(train + (long)t * t_pitch);  // wave-uniform address
-      unsigned d = 0;
-#pragma unroll
-      for (int w = 0; w < W32; ++w) d += __popc(qv[w] ^ tp[w]);
-      const unsigned key = (d << MF_IDX_BITS) | (unsigned)t;
-      b2 = min(b2, max(b1, key));
-      b1 = min(b1, key);
-    }
-  } else {
-    for (int t = t0; t < t1; ++t) {
-      const uint8_t* tp = train + (long)t * t_pitch;
-      unsigned d = 0;
-#pragma unroll
-      for (int w = 0; w < W32; ++w) {
-        const unsigned tv = (unsigned)tp[4 * w] | ((unsigned)tp[4 * w + 1] << 8) | ((unsigned)tp[4 * w + 2] << 16) | ((unsigned)tp[4 * w + 3] << 24);
-        d += __popc(qv[w] ^ tv);
-      }
-      const unsigned key = (d << MF_IDX_BITS) | (unsigned)t;
-      b2 = min(b2, max(b1, key));
-      b1 = min(b1, key);
-    }
-  }
-  part[wave][0][lane] = b1;
-  part[wave][1][lane] = b2;
-  __syncthreads();
-  if (wave == 0 && q < nq) {
-    unsigned m1 = 0xFFFFFFFFu, m2 = 0xFFFFFFFFu;
-#pragma unroll
-    for (int w = 0; w < MF_WAVES; ++w)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const unsigned key = part[w][i][lane];
-        m2 = min(m2, max(m1, key));
-        m1 = min(m1, key);
-      }
-    BriskDMatch* orow = out + (long)q * k;
-    BriskDMatch m;
-    m.queryIdx = q; m.imgIdx = 0;
-    m.trainIdx = (int)(m1 & ((1u << MF_IDX_BITS) - 1)); m.distance = (float)(m1 >> MF_IDX_BITS);
-    orow[0] = m;
-    if (k > 1) {
-      m.trainIdx = (int)(m2 & ((1u << MF_IDX_BITS) - 1)); m.distance = (float)(m2 >> MF_IDX_BITS);
-      orow[1] = m;
-    }
-    out_count[q] = k;
-  }
-}
-
-// returns false when the case is not covered (the caller uses the distance-matrix path)
-bool brisk_launch_match_knn_fused(const uint8_t* query, int q_pitch, int nq, const uint8_t* train, int t_pitch, int nt,
-                                  int words32, int k, BriskDMatch* out, int* out_count, hipStream_t s) {
-  if (k < 1 || k > 2 || nt < k || nt >= (1 << MF_IDX_BITS) || nq <= 0) return false;
-  const dim3 grid((nq + 63) / 64), block(MF_WAVES * 64);
-  switch (words32) {
-    case 4: hipLaunchKernelGGL(k_match_knn_fused<4>, grid, block, 0, s, query, q_pitch, nq, train, t_pitch, nt, k, out, out_count); break;
-    case 8: hipLaunchKernelGGL(k_match_knn_fused<8>, grid, block, 0, s, query, q_pitch, nq, train, t_pitch, nt, k, out, out_count); break;
-    case 12: hipLaunchKernelGGL(k_match_knn_fused<12>, grid, block, 0, s, query, q_pitch, nq, train, t_pitch, nt, k, out, out_count); break;
-    case 16: hipLaunchKernelGGL(k_match_knn_fused<16>, grid, block, 0, s, query, q_pitch, nq, train, t_pitch, nt, k, out, out_count); break;
-    default: return false;
-  }
-  return true;
-}
-
-// ------------------------------------------------------------------------------------------------
-// The frame pairs of a batch in one launch (brisk_hip_match_knn_pairs_device): k_match_knn_fused's scheme - 64 queries per
-// workgroup, one per lane with the descriptor in registers, MP_WAVES (8) waves each scanning a slice of the train rows through
-// wave-uniform loads, packed keys, merge through LDS - with everything a pair needs resolved on the device: grid
-// (ceil(rows_cap / 64), pairs); the workgroup finds its pair (arithmetic form or the caller's list), reads the two row
-// counts from the sets' count arrays and leaves at once when its 64 rows lie beyond min(n_a, rows_cap).
-// CROSS (k == 1): the forward match t of row q is kept only if the best match of row t of frame b among ALL rows of frame
-// a is q.  Fused: once the forward keys are merged, lane q takes row t of frame b into its registers and the waves scan
-// frame a the same way (top-1) - the same work as a role-swapped launch, without a scratch buffer of backward keys and
-// without any hand-off between workgroups.
-// ------------------------------------------------------------------------------------------------
+#define MF_IDX_MASK ((1u << MF_IDX_BITS) - 1)
+#define MF_NO_KEY 0xFFFFFFFFu
 #ifndef MP_WAVES
-// waves of a workgroup = slices of the train rows.  8, not k_match_knn_fused's 16: a CU holds ONE workgroup of 16 waves (71 VGPRs
+// waves of a pair workgroup = slices of the train rows.  8, not k_match_knn_fused's 16: a CU holds ONE workgroup of 16 waves (71 VGPRs
 // with the 32-key merge unrolled: 7 waves per SIMD) but four of 8 (39 VGPRs), and with several resident the prologue (pair and
 // count look-ups, the query row) and the LDS merge of one are covered by the scans of the others (measured both)
 #define MP_WAVES 8
 #endif
+
+// rows of 4-byte aligned base and pitches are read as words, others byte by byte (no alignment assumption on a caller's rows)
+__device__ __forceinline__ bool m_aligned(const void* base, long frame_pitch, int row_pitch) {
+  return (((uintptr_t)base | (unsigned long)frame_pitch | (unsigned)row_pitch) & 3) == 0;
+}
 template <int W32>
 __device__ __forceinline__ void mp_load_row(const uint8_t* p, bool aligned, unsigned (&v)[W32]) {
   if (aligned) {
@@ -329,185 +257,9 @@ __device__ __forceinline__ void mp_load_row(const uint8_t* p, bool aligned, unsi
       v[w] = (unsigned)p[4 * w] | ((unsigned)p[4 * w + 1] << 8) | ((unsigned)p[4 * w + 2] << 16) | ((unsigned)p[4 * w + 3] << 24);
   }
 }
-// rows [t0, t1) of one frame (wave-uniform addresses) against the lane's descriptor: the two smallest keys
-template <int W32>
-__device__ __forceinline__ void mp_scan(const unsigned (&qv)[W32], const uint8_t* rows, int pitch, bool aligned, int t0, int t1,
-                                        unsigned& b1, unsigned& b2) {
-  if (aligned) {  // (batch results: 4-byte aligned rows at pitch 64)
-    for (int t = t0; t < t1; ++t) {
-      const unsigned* tp = reinterpret_cast<const unsigned*>(rows + (long)t * pitch);
-      unsigned d = 0;
-#pragma unroll
-      for (int w = 0; w < W32; ++w) d += __popc(qv[w] ^ tp[w]);
-      const unsigned key = (d << MF_IDX_BITS) | (unsigned)t;
-      b2 = min(b2, max(b1, key));
-      b1 = min(b1, key);
-    }
-  } else {  // (a caller's set whose base, frame pitch or row pitch is not)
-    for (int t = t0; t < t1; ++t) {
-      const uint8_t* tp = rows + (long)t * pitch;
-      unsigned d = 0;
-#pragma unroll
-      for (int w = 0; w < W32; ++w) {
-        const unsigned tv = (unsigned)tp[4 * w] | ((unsigned)tp[4 * w + 1] << 8) | ((unsigned)tp[4 * w + 2] << 16) | ((unsigned)tp[4 * w + 3] << 24);
-        d += __popc(qv[w] ^ tv);
-      }
-      const unsigned key = (d << MF_IDX_BITS) | (unsigned)t;
-      b2 = min(b2, max(b1, key));
-      b1 = min(b1, key);
-    }
-  }
-}
-
-template <int W32, bool CROSS>
-__global__ void __launch_bounds__(MP_WAVES * 64) k_match_knn_pairs(const BriskDescSet Q, const BriskDescSet T, const BriskPairSpec P,
-                                                                    int pair0, int k, int rows_cap, BriskDMatch* __restrict__ out,
-                                                                    int* __restrict__ out_count, int* __restrict__ pair_rows) {
-  __shared__ unsigned part[MP_WAVES][2][64];
-  __shared__ unsigned fwd[64];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int p = pair0 + blockIdx.y;
-  int a, b;
-  if (P.pairs) {
-    a = P.pairs[2 * (long)p];
-    b = P.pairs[2 * (long)p + 1];
-  } else {
-    a = P.query_first + p * P.query_step;
-    b = P.train_first + p * P.train_step;
-  }
-  const bool first = blockIdx.x == 0 && threadIdx.x == 0;
-  if (a < 0 || a >= Q.frames || b < 0 || b >= T.frames) {  // (a bad entry of the caller's list; the arithmetic form is checked on the host)
-    if (first) pair_rows[p] = -1;
-    return;
-  }
-  const int n_a = max(0, Q.counts[(long)a * Q.count_stride]), n_b = max(0, T.counts[(long)b * T.count_stride]);
-  if (n_b >= (1 << MF_IDX_BITS) || (CROSS && n_a >= (1 << MF_IDX_BITS))) {  // (the keys hold 22 index bits)
-    if (first) pair_rows[p] = -1;
-    return;
-  }
-  if (first) pair_rows[p] = n_a;
-  const int rows = min(n_a, rows_cap);
-  if ((int)blockIdx.x * 64 >= rows) return;
-  const int q = blockIdx.x * 64 + lane;
-  BriskDMatch* orow = out + ((long)p * rows_cap + q) * k;
-  int* ocnt = out_count + (long)p * rows_cap + q;
-  if (n_b == 0) {  // nothing to match against: empty rows (the reference tops up only when some train image has rows)
-    if (wave == 0 && q < rows) *ocnt = 0;
-    return;
-  }
-  const uint8_t* qrows = Q.desc + (long)a * Q.frame_pitch;
-  const uint8_t* trows = T.desc + (long)b * T.frame_pitch;
-  const bool q_aligned = (((uintptr_t)Q.desc | (unsigned long)Q.frame_pitch | (unsigned)Q.row_pitch) & 3) == 0;
-  const bool t_aligned = (((uintptr_t)T.desc | (unsigned long)T.frame_pitch | (unsigned)T.row_pitch) & 3) == 0;
-  unsigned qv[W32];
-  mp_load_row<W32>(qrows + (long)min(q, rows - 1) * Q.row_pitch, q_aligned, qv);
-  unsigned b1 = 0xFFFFFFFFu, b2 = 0xFFFFFFFFu;
-  {
-    const int per = (n_b + MP_WAVES - 1) / MP_WAVES;
-    const int t0 = __builtin_amdgcn_readfirstlane(wave * per), t1 = min(n_b, t0 + per);
-    mp_scan<W32>(qv, trows, T.row_pitch, t_aligned, t0, t1, b1, b2);
-  }
-  part[wave][0][lane] = b1;
-  part[wave][1][lane] = b2;
-  __syncthreads();
-  unsigned m1 = 0xFFFFFFFFu, m2 = 0xFFFFFFFFu;
-  if (wave == 0) {
-#pragma unroll
-    for (int w = 0; w < MP_WAVES; ++w)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const unsigned key = part[w][i][lane];
-        m2 = min(m2, max(m1, key));
-        m1 = min(m1, key);
-      }
-  }
-  bool keep = true;
-  if (CROSS) {
-    if (wave == 0) fwd[lane] = m1;
-    __syncthreads();  // (also: wave 0 has read part[] before anybody writes it again)
-    const int t = (int)(fwd[lane] & ((1u << MF_IDX_BITS) - 1));  // (n_b >= 1: every lane has a real forward match)
-    unsigned tv[W32];
-    mp_load_row<W32>(trows + (long)t * T.row_pitch, t_aligned, tv);
-    unsigned c1 = 0xFFFFFFFFu, c2 = 0xFFFFFFFFu;
-    const int per = (n_a + MP_WAVES - 1) / MP_WAVES;
-    const int r0 = __builtin_amdgcn_readfirstlane(wave * per), r1 = min(n_a, r0 + per);
-    mp_scan<W32>(tv, qrows, Q.row_pitch, q_aligned, r0, r1, c1, c2);  // ALL rows of frame a, also those beyond rows_cap
-    part[wave][0][lane] = c1;
-    __syncthreads();
-    if (wave == 0) {
-      unsigned best = 0xFFFFFFFFu;
-#pragma unroll
-      for (int w = 0; w < MP_WAVES; ++w) best = min(best, part[w][0][lane]);
-      keep = (int)(best & ((1u << MF_IDX_BITS) - 1)) == q;
-    }
-  }
-  if (wave == 0 && q < rows) {
-    if (!keep) {
-      *ocnt = 0;
-      return;
-    }
-    BriskDMatch m;
-    m.queryIdx = q; m.imgIdx = b;
-    m.trainIdx = (int)(m1 & ((1u << MF_IDX_BITS) - 1)); m.distance = (float)(m1 >> MF_IDX_BITS);
-    orow[0] = m;
-    if (k > 1) {
-      if (m2 != 0xFFFFFFFFu) {
-        m.trainIdx = (int)(m2 & ((1u << MF_IDX_BITS) - 1)); m.distance = (float)(m2 >> MF_IDX_BITS);
-      } else {  // n_b < k: the reference's top-up entry (k_match_knn above; brute-force-matcher.cc:139-153)
-        m.trainIdx = 0; m.distance = 2147483648.0f;
-      }
-      orow[1] = m;
-    }
-    *ocnt = k;
-  }
-}
-
-template <int W32>
-static void mp_launch(const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, int k, bool cross, int rows_cap,
-                      BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s) {
-  const dim3 block(MP_WAVES * 64);
-  for (int p0 = 0; p0 < P.npairs; p0 += 65535) {  // (grid.y holds 65535)
-    const dim3 grid((rows_cap + 63) / 64, min(65535, P.npairs - p0));
-    if (cross)
-      hipLaunchKernelGGL((k_match_knn_pairs<W32, true>), grid, block, 0, s, Q, T, P, p0, k, rows_cap, out, out_count, pair_rows);
-    else
-      hipLaunchKernelGGL((k_match_knn_pairs<W32, false>), grid, block, 0, s, Q, T, P, p0, k, rows_cap, out, out_count, pair_rows);
-  }
-}
-// false: descriptor size not covered (16, 32, 48, 64 bytes are)
-bool brisk_launch_match_knn_pairs(const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, int words32, int k, bool cross,
-                                  int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s) {
-  switch (words32) {
-    case 4: mp_launch<4>(Q, T, P, k, cross, rows_cap, out, out_count, pair_rows, s); break;
-    case 8: mp_launch<8>(Q, T, P, k, cross, rows_cap, out, out_count, pair_rows, s); break;
-    case 12: mp_launch<12>(Q, T, P, k, cross, rows_cap, out, out_count, pair_rows, s); break;
-    case 16: mp_launch<16>(Q, T, P, k, cross, rows_cap, out, out_count, pair_rows, s); break;
-    default: return false;
-  }
-  return true;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Radius matching in k_match_knn_pairs' shape (brisk_hip_match_radius_pairs_device / brisk_hip_match_radius_device): 64 queries
-// per workgroup, one per lane with the descriptor in registers, MP_WAVES waves each scanning a slice of the train rows through
-// wave-uniform loads.  No distance matrix: a hit ((float)d < max_distance, brute-force-matcher.cc:203-207) bumps its query's
-// counter in LDS and, while the query's short LDS list has room, drops its packed key (d << 22 | t) there.  Keys are unique per
-// train row, so the order of collection does not matter:
-//   sparse rows (count <= MRP_LIST): MP_WAVES threads per query rank the keys of the list against each other and store those
-//       of rank < cap at their rank - (distance, trainIdx) order;
-//   dense rows (the list overflowed): one wave per such query runs k_match_radius' algorithm with the distances recomputed on
-//       the fly (lane = train row, the query wave-uniform): histogram over the distances below the threshold, exclusive prefix,
-//       stable placement in train order.  Second phase of the same workgroup: nothing between the phases leaves the CU.
-// The counter holds the number FOUND in both cases.
-// ------------------------------------------------------------------------------------------------
-#ifndef MRP_LIST
-#define MRP_LIST 32  // keys per query held in LDS (8 KiB per workgroup); a row with more hits takes the dense path
-#endif
-#define MRP_BINS 513                    // distances 0 ... 512 (descriptors of at most 64 bytes)
-#define MRP_PER ((MRP_BINS + 63) / 64)  // bins per lane in the prefix
-
+// Hamming distance of a register row to the row at tp (wave-uniform in the scans: scalar loads, v_xor + v_bcnt with accumulate)
 template <int W32, bool ALIGNED>
-__device__ __forceinline__ unsigned mrp_dist(const unsigned (&qv)[W32], const uint8_t* tp) {
+__device__ __forceinline__ unsigned m_dist(const unsigned (&qv)[W32], const uint8_t* tp) {
   unsigned d = 0;
   if (ALIGNED) {
     const unsigned* tp32 = reinterpret_cast<const unsigned*>(tp);
@@ -522,19 +274,114 @@ __device__ __forceinline__ unsigned mrp_dist(const unsigned (&qv)[W32], const ui
   }
   return d;
 }
-// rows [t0, t1) of one frame (wave-uniform addresses) against the lane's descriptor: hits (d < thr) into the lane's counter and list
+__device__ __forceinline__ unsigned m_key(unsigned d, int t) { return (d << MF_IDX_BITS) | (unsigned)t; }
+__device__ __forceinline__ void m_key_to(unsigned key, BriskDMatch& m) {
+  m.trainIdx = (int)(key & MF_IDX_MASK);
+  m.distance = (float)(key >> MF_IDX_BITS);
+}
+// (b1, b2): the two smallest keys seen
+__device__ __forceinline__ void m_top2(unsigned& b1, unsigned& b2, unsigned key) {
+  b2 = min(b2, max(b1, key));
+  b1 = min(b1, key);
+}
+// the lane's two smallest keys over the partial lists of the WAVES waves
+template <int WAVES>
+__device__ __forceinline__ void m_merge(const unsigned (&part)[WAVES][2][64], int lane, unsigned& m1, unsigned& m2) {
+#pragma unroll
+  for (int w = 0; w < WAVES; ++w)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) m_top2(m1, m2, part[w][i][lane]);
+}
+// rows [t0, t1) of one frame (wave-uniform addresses) against the lane's descriptor: the two smallest keys
 template <int W32, bool ALIGNED>
-__device__ __forceinline__ void mrp_scan(const unsigned (&qv)[W32], const uint8_t* rows, int pitch, int t0, int t1, unsigned thr,
-                                         int* cnt, unsigned (*list)[64], int lane) {
-  for (int t = t0; t < t1; ++t) {
-    const unsigned d = mrp_dist<W32, ALIGNED>(qv, rows + (long)t * pitch);
-    if (d < thr) {
-      const int slot = atomicAdd(&cnt[lane], 1);
-      if (slot < MRP_LIST) list[slot][lane] = (d << MF_IDX_BITS) | (unsigned)t;
+__device__ __forceinline__ void mp_scan(const unsigned (&qv)[W32], const uint8_t* rows, int pitch, int t0, int t1, unsigned& b1,
+                                        unsigned& b2) {
+  for (int t = t0; t < t1; ++t) m_top2(b1, b2, m_key(m_dist<W32, ALIGNED>(qv, rows + (long)t * pitch), t));
+}
+
+// ------------------------------------------------------------------------------------------------
+// k-NN for k <= 2, one query set against one train set (the frame-to-frame / frame-to-map case): MF_WAVES waves, wave w scans
+// the w-th slice of the train set; the MF_WAVES partial top-2 lists of a query are merged through LDS.
+// ------------------------------------------------------------------------------------------------
+template <int W32>
+__global__ void __launch_bounds__(MF_WAVES * 64) k_match_knn_fused(const uint8_t* __restrict__ query, int q_pitch, int nq,
+                                                                    const uint8_t* __restrict__ train, int t_pitch, int nt,
+                                                                    int k, BriskDMatch* __restrict__ out,
+                                                                    int* __restrict__ out_count) {
+  __shared__ unsigned part[MF_WAVES][2][64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int q = blockIdx.x * 64 + lane;
+  unsigned qv[W32];
+  mp_load_row<W32>(query + (long)min(q, nq - 1) * q_pitch, false, qv);
+  const int per = (nt + MF_WAVES - 1) / MF_WAVES;
+  const int t0 = __builtin_amdgcn_readfirstlane(wave * per), t1 = min(nt, t0 + per);
+  unsigned b1 = MF_NO_KEY, b2 = MF_NO_KEY;
+  if (m_aligned(train, 0, t_pitch)) mp_scan<W32, true>(qv, train, t_pitch, t0, t1, b1, b2);
+  else mp_scan<W32, false>(qv, train, t_pitch, t0, t1, b1, b2);
+  part[wave][0][lane] = b1;
+  part[wave][1][lane] = b2;
+  __syncthreads();
+  if (wave == 0 && q < nq) {
+    unsigned m1 = MF_NO_KEY, m2 = MF_NO_KEY;
+    m_merge<MF_WAVES>(part, lane, m1, m2);
+    BriskDMatch* orow = out + (long)q * k;
+    BriskDMatch m;
+    m.queryIdx = q; m.imgIdx = 0;
+    m_key_to(m1, m);
+    orow[0] = m;
+    if (k > 1) {
+      m_key_to(m2, m);
+      orow[1] = m;
     }
+    out_count[q] = k;
   }
 }
-// the gated kernels' view of a pair: the gate and the keypoint records of the two frames, row for row with the descriptors
+
+// ------------------------------------------------------------------------------------------------
+// The frame pairs of a batch in one launch: grid (ceil(rows_cap / 64), pairs), MP_WAVES waves.  Everything a pair needs is
+// resolved on the device.
+// ------------------------------------------------------------------------------------------------
+// row 0 of frame f.  (An expression on the kernel's own argument wherever it is used, not a pointer kept in MpPair: with the
+// pointer handed on through the struct the compiler no longer takes the row loads of the radius scans for scalar loads.)
+__device__ __forceinline__ const uint8_t* mp_frame(const BriskDescSet& S, int f) { return S.desc + (long)f * S.frame_pitch; }
+struct MpPair {
+  int a, b;      // query frame of Q, train frame of T
+  int n_a, n_b;  // their row counts
+  int rows;      // min(n_a, rows_cap): the query rows that are matched
+  bool q_aligned, t_aligned;
+};
+// the workgroup finds pair p (arithmetic form or the caller's list), reads the two row counts from the sets' count arrays and
+// reports the pair in pair_rows (-1: no such frames, or more rows than the keys hold; back_keys: keys index frame a's rows
+// too).  false: nothing to do for this workgroup - a bad pair, or its 64 rows lie beyond `rows`
+__device__ __forceinline__ bool mp_resolve(const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, int p, bool back_keys,
+                                           int rows_cap, int* __restrict__ pair_rows, MpPair& R) {
+  if (P.pairs) {
+    R.a = P.pairs[2 * (long)p];
+    R.b = P.pairs[2 * (long)p + 1];
+  } else {
+    R.a = P.query_first + p * P.query_step;
+    R.b = P.train_first + p * P.train_step;
+  }
+  const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+  if (R.a < 0 || R.a >= Q.frames || R.b < 0 || R.b >= T.frames) {  // (a bad entry of the caller's list; the arithmetic form is checked on the host)
+    if (first) pair_rows[p] = -1;
+    return false;
+  }
+  R.n_a = max(0, Q.counts[(long)R.a * Q.count_stride]);
+  R.n_b = max(0, T.counts[(long)R.b * T.count_stride]);
+  if (R.n_b >= (1 << MF_IDX_BITS) || (back_keys && R.n_a >= (1 << MF_IDX_BITS))) {  // (the keys hold 22 index bits)
+    if (first) pair_rows[p] = -1;
+    return false;
+  }
+  if (first) pair_rows[p] = R.n_a;
+  R.rows = min(R.n_a, rows_cap);
+  R.q_aligned = m_aligned(Q.desc, Q.frame_pitch, Q.row_pitch);
+  R.t_aligned = m_aligned(T.desc, T.frame_pitch, T.row_pitch);
+  return (int)blockIdx.x * 64 < R.rows;
+}
+
+// The position gate (brisk_match_gate.h): the mask of a pair is the gate's predicate on the two rows' keypoints, whose records lie
+// row for row with the descriptors.  MpGate: the gate and the records of a pair's two frames.
 struct MpGate {
   BriskMatchGate g;
   const char* qk;
@@ -542,6 +389,210 @@ struct MpGate {
 };
 __device__ __forceinline__ const BriskKeyPoint* mp_kp(const char* kps, int r) {
   return reinterpret_cast<const BriskKeyPoint*>(kps + (long)r * (long)sizeof(BriskKeyPoint));
+}
+// The gated scans.  The keypoint of the wave-uniform row comes through the same scalar loads as the row itself, MPG_CHUNK records
+// ahead of the rows they belong to (one wait for the chunk, not one per row); the predicate is a handful of VALU compares whose
+// result lives in a lane mask.  A row that NO lane of the wave may match is left without its descriptor loads and popcounts: a
+// uniform branch on the mask.  `on`: the lane takes part at all.
+// ok[i]: this lane may match row tc + i; live[i]: the lanes of the wave that may.  The ballots are taken for the whole chunk BEFORE
+// the first branch (a ballot is not moved below a branch), so the chunk's keypoint loads and compares stay together in front of
+// its rows instead of one load and wait in front of each.  (No scheduling barrier between the loads and the compares: with one
+// the compiler no longer takes the loop's loads - the descriptor rows included - for scalar loads.)
+// SWAP (the cross check): the roles swap - the lane holds the train side's keypoint, the row passing by is a query row.
+#define MPG_CHUNK 4
+template <bool SWAP>
+__device__ __forceinline__ void mpg_allowed(const BriskMatchGate& g, const BriskGateLane& L, bool on, const char* kps, int tc, int t1,
+                                            bool (&ok)[MPG_CHUNK], unsigned long long (&live)[MPG_CHUNK]) {
+#pragma unroll
+  for (int i = 0; i < MPG_CHUNK; ++i) {
+    const BriskKeyPoint* kp = mp_kp(kps, min(tc + i, t1 - 1));
+    const bool pass = SWAP ? brisk_gate_train_lane(g, L, kp->x, kp->y, kp->octave) : brisk_gate_query_lane(g, L, kp->x, kp->y, kp->octave);
+    ok[i] = on && tc + i < t1 && pass;
+    live[i] = __ballot(ok[i]);
+  }
+}
+// mp_scan behind the gate: the two smallest keys among the allowed rows
+template <int W32, bool ALIGNED, bool SWAP>
+__device__ __forceinline__ void mpg_scan(const unsigned (&qv)[W32], const uint8_t* rows, int pitch, int t0, int t1, const BriskMatchGate& g,
+                                         const BriskGateLane& L, bool on, const char* kps, unsigned& b1, unsigned& b2) {
+  for (int tc = t0; tc < t1; tc += MPG_CHUNK) {
+    bool ok[MPG_CHUNK];
+    unsigned long long live[MPG_CHUNK];
+    mpg_allowed<SWAP>(g, L, on, kps, tc, t1, ok, live);
+#pragma unroll
+    for (int i = 0; i < MPG_CHUNK; ++i) {
+      if (live[i] == 0) continue;  // wave-uniform
+      const int t = tc + i;
+      const unsigned d = m_dist<W32, ALIGNED>(qv, rows + (long)t * pitch);
+      m_top2(b1, b2, ok[i] ? m_key(d, t) : MF_NO_KEY);
+    }
+  }
+}
+
+// this wave's slice of the n rows of one frame against the lane's descriptor: the two smallest keys.  GATE: `self` is the lane's
+// own keypoint, kps the records of the rows passing by
+template <int W32, bool GATE, bool SWAP>
+__device__ __forceinline__ void mp_scan_slice(const unsigned (&v)[W32], const uint8_t* rows, int pitch, bool aligned, int n, int wave,
+                                              const BriskMatchGate& g, const BriskKeyPoint* self, bool on, const char* kps, unsigned& b1,
+                                              unsigned& b2) {
+  const int per = (n + MP_WAVES - 1) / MP_WAVES;
+  const int t0 = __builtin_amdgcn_readfirstlane(wave * per), t1 = min(n, t0 + per);
+  if (GATE) {
+    const BriskGateLane L = brisk_gate_lane(g, self->x, self->y, self->octave);
+    if (aligned) mpg_scan<W32, true, SWAP>(v, rows, pitch, t0, t1, g, L, on, kps, b1, b2);
+    else mpg_scan<W32, false, SWAP>(v, rows, pitch, t0, t1, g, L, on, kps, b1, b2);
+  } else {
+    if (aligned) mp_scan<W32, true>(v, rows, pitch, t0, t1, b1, b2);  // (batch results: 4-byte aligned rows at pitch 64)
+    else mp_scan<W32, false>(v, rows, pitch, t0, t1, b1, b2);         // (a caller's set whose base, frame pitch or row pitch is not)
+  }
+}
+
+// k-NN of a pair: k_match_knn_fused's scheme with MP_WAVES waves.
+// CROSS (k == 1): the forward match t of row q is kept only if the best match of row t of frame b among ALL rows of frame a is q.
+// Fused: once the forward keys are merged, lane q takes row t of frame b into its registers and the waves scan frame a the same
+// way (top-1) - the same work as a role-swapped launch, without a scratch buffer of backward keys and without any hand-off
+// between workgroups.
+// GATE: a lane the gate forbids keeps MF_NO_KEY, so a row holds min(k, allowed rows) REAL matches and is never topped up; in the
+// cross check a lane without a forward match takes no part.
+template <int W32, bool CROSS, bool GATE>
+__device__ __forceinline__ void mp_body(const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, int pair0, int k, int rows_cap,
+                                        BriskDMatch* __restrict__ out, int* __restrict__ out_count, int* __restrict__ pair_rows,
+                                        const BriskKpSet& QK, const BriskKpSet& TK, const BriskMatchGate& gate) {
+  __shared__ unsigned part[MP_WAVES][2][64];
+  __shared__ unsigned fwd[64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int p = pair0 + blockIdx.y;
+  MpPair R;
+  if (!mp_resolve(Q, T, P, p, CROSS, rows_cap, pair_rows, R)) return;
+  const int q = blockIdx.x * 64 + lane;
+  BriskDMatch* orow = out + ((long)p * rows_cap + q) * k;
+  int* ocnt = out_count + (long)p * rows_cap + q;
+  if (R.n_b == 0) {  // nothing to match against: empty rows (the reference tops up only when some train image has rows)
+    if (wave == 0 && q < R.rows) *ocnt = 0;
+    return;
+  }
+  const uint8_t* qrows = mp_frame(Q, R.a);
+  const uint8_t* trows = mp_frame(T, R.b);
+  const char* qk = GATE ? QK.kps + (long)R.a * QK.frame_pitch : nullptr;
+  const char* tk = GATE ? TK.kps + (long)R.b * TK.frame_pitch : nullptr;
+  unsigned b1 = MF_NO_KEY, b2 = MF_NO_KEY;
+  {
+    unsigned qv[W32];
+    mp_load_row<W32>(qrows + (long)min(q, R.rows - 1) * Q.row_pitch, R.q_aligned, qv);
+    mp_scan_slice<W32, GATE, false>(qv, trows, T.row_pitch, R.t_aligned, R.n_b, wave, gate, GATE ? mp_kp(qk, min(q, R.rows - 1)) : nullptr,
+                                    q < R.rows, tk, b1, b2);
+  }
+  part[wave][0][lane] = b1;
+  part[wave][1][lane] = b2;
+  __syncthreads();
+  unsigned m1 = MF_NO_KEY, m2 = MF_NO_KEY;
+  if (wave == 0) m_merge<MP_WAVES>(part, lane, m1, m2);
+  bool keep = true;
+  if (CROSS) {
+    if (wave == 0) fwd[lane] = m1;
+    __syncthreads();  // (also: wave 0 has read part[] before anybody writes it again)
+    const unsigned f = fwd[lane];
+    const bool has = !GATE || f != MF_NO_KEY;  // (ungated, n_b >= 1: every lane has a real forward match; the gate may have left none)
+    const int t = has ? (int)(f & MF_IDX_MASK) : 0;
+    unsigned tv[W32];
+    mp_load_row<W32>(trows + (long)t * T.row_pitch, R.t_aligned, tv);
+    unsigned c1 = MF_NO_KEY, c2 = MF_NO_KEY;
+    // ALL rows q' of frame a, also those beyond rows_cap
+    mp_scan_slice<W32, GATE, true>(tv, qrows, Q.row_pitch, R.q_aligned, R.n_a, wave, gate, GATE ? mp_kp(tk, t) : nullptr, has, qk, c1, c2);
+    part[wave][0][lane] = c1;
+    __syncthreads();
+    if (wave == 0) {
+      unsigned best = MF_NO_KEY;
+#pragma unroll
+      for (int w = 0; w < MP_WAVES; ++w) best = min(best, part[w][0][lane]);
+      keep = has && (int)(best & MF_IDX_MASK) == q;
+    }
+  }
+  if (wave == 0 && q < R.rows) {
+    int n = 0;
+    if (keep && (!GATE || m1 != MF_NO_KEY)) {
+      BriskDMatch m;
+      m.queryIdx = q; m.imgIdx = R.b;
+      m_key_to(m1, m);
+      orow[0] = m;
+      n = 1;
+      if (k > 1 && (!GATE || m2 != MF_NO_KEY)) {  // (gated: a second entry only where a second row is allowed)
+        if (m2 != MF_NO_KEY) {
+          m_key_to(m2, m);
+        } else {  // n_b < k: the reference's top-up entry (k_match_knn above; brute-force-matcher.cc:139-153)
+          m.trainIdx = 0; m.distance = 2147483648.0f;
+        }
+        orow[1] = m;
+        n = 2;
+      }
+    }
+    *ocnt = n;
+  }
+}
+
+template <int W32, bool CROSS>
+__global__ void __launch_bounds__(MP_WAVES * 64) k_match_knn_pairs(const BriskDescSet Q, const BriskDescSet T, const BriskPairSpec P,
+                                                                    int pair0, int k, int rows_cap, BriskDMatch* __restrict__ out,
+                                                                    int* __restrict__ out_count, int* __restrict__ pair_rows) {
+  mp_body<W32, CROSS, false>(Q, T, P, pair0, k, rows_cap, out, out_count, pair_rows, BriskKpSet(), BriskKpSet(), BriskMatchGate());
+}
+template <int W32, bool CROSS>
+__global__ void __launch_bounds__(MP_WAVES * 64) k_match_knn_pairs_gated(const BriskDescSet Q, const BriskDescSet T, const BriskKpSet QK,
+                                                                          const BriskKpSet TK, const BriskMatchGate gate,
+                                                                          const BriskPairSpec P, int pair0, int k, int rows_cap,
+                                                                          BriskDMatch* __restrict__ out, int* __restrict__ out_count,
+                                                                          int* __restrict__ pair_rows) {
+  mp_body<W32, CROSS, true>(Q, T, P, pair0, k, rows_cap, out, out_count, pair_rows, QK, TK, gate);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Radius matching in mp_body's shape.  No distance matrix: a hit ((float)d < max_distance, brute-force-matcher.cc:203-207) bumps
+// its query's counter in LDS and, while the query's short LDS list has room, drops its packed key there.  Keys are unique per
+// train row, so the order of collection does not matter:
+//   sparse rows (count <= MRP_LIST): MP_WAVES threads per query rank the keys of the list against each other and store those
+//       of rank < cap at their rank - (distance, trainIdx) order;
+//   dense rows (the list overflowed): one wave per such query runs k_match_radius' algorithm with the distances recomputed on
+//       the fly (lane = train row, the query wave-uniform): histogram over the distances below the threshold, exclusive prefix,
+//       stable placement in train order.  Second phase of the same workgroup: nothing between the phases leaves the CU.
+// The counter holds the number FOUND in both cases.
+// ------------------------------------------------------------------------------------------------
+#ifndef MRP_LIST
+#define MRP_LIST 32  // keys per query held in LDS (8 KiB per workgroup); a row with more hits takes the dense path
+#endif
+#define MRP_BINS 513                    // distances 0 ... 512 (descriptors of at most 64 bytes)
+#define MRP_PER ((MRP_BINS + 63) / 64)  // bins per lane in the prefix
+
+// a hit of the lane's query: counted, and listed while the list has room
+__device__ __forceinline__ void mrp_hit(unsigned key, int* cnt, unsigned (*list)[64], int lane) {
+  const int slot = atomicAdd(&cnt[lane], 1);
+  if (slot < MRP_LIST) list[slot][lane] = key;
+}
+// rows [t0, t1) of one frame (wave-uniform addresses) against the lane's descriptor: hits (d < thr) into the lane's counter and list
+template <int W32, bool ALIGNED>
+__device__ __forceinline__ void mrp_scan(const unsigned (&qv)[W32], const uint8_t* rows, int pitch, int t0, int t1, unsigned thr,
+                                         int* cnt, unsigned (*list)[64], int lane) {
+  for (int t = t0; t < t1; ++t) {
+    const unsigned d = m_dist<W32, ALIGNED>(qv, rows + (long)t * pitch);
+    if (d < thr) mrp_hit(m_key(d, t), cnt, list, lane);
+  }
+}
+// mrp_scan behind the gate (mpg_scan's loop)
+template <int W32, bool ALIGNED>
+__device__ __forceinline__ void mrpg_scan(const unsigned (&qv)[W32], const uint8_t* rows, int pitch, int t0, int t1, unsigned thr,
+                                          const BriskMatchGate& g, const BriskGateLane& L, bool on, const char* kps, int* cnt,
+                                          unsigned (*list)[64], int lane) {
+  for (int tc = t0; tc < t1; tc += MPG_CHUNK) {
+    bool ok[MPG_CHUNK];
+    unsigned long long live[MPG_CHUNK];
+    mpg_allowed<false>(g, L, on, kps, tc, t1, ok, live);
+#pragma unroll
+    for (int i = 0; i < MPG_CHUNK; ++i) {
+      if (live[i] == 0) continue;  // wave-uniform
+      const int t = tc + i;
+      const unsigned d = m_dist<W32, ALIGNED>(qv, rows + (long)t * pitch);
+      if (ok[i] && d < thr) mrp_hit(m_key(d, t), cnt, list, lane);
+    }
+  }
 }
 // the dense path's distance of train row t (one per lane) to the wave's query; GATE: a row the gate forbids is no hit (thr)
 template <int W32, bool ALIGNED, bool GATE>
@@ -551,7 +602,7 @@ __device__ __forceinline__ unsigned mrp_dense_dist(const unsigned (&uq)[W32], co
     const BriskKeyPoint* kp = mp_kp(G.tk, t);
     if (!brisk_gate_query_lane(G.g, QL, kp->x, kp->y, kp->octave)) return thr;
   }
-  return mrp_dist<W32, ALIGNED>(uq, trows + (long)t * t_pitch);
+  return m_dist<W32, ALIGNED>(uq, trows + (long)t * t_pitch);
 }
 // one wave, one query with more than MRP_LIST hits.  bins: thr + 1 ints of this wave's own
 template <int W32, bool ALIGNED, bool GATE>
@@ -616,47 +667,6 @@ __device__ __forceinline__ void mrp_dense(int* bins, const unsigned (&uq)[W32], 
       __builtin_amdgcn_s_waitcnt(0);
       __builtin_amdgcn_wave_barrier();
       todo &= ~same;
-    }
-  }
-}
-
-// The gated scans (k_match_knn_pairs_gated / k_match_radius_pairs_gated).  The keypoint of the wave-uniform row comes through the same
-// scalar loads as the row itself, MPG_CHUNK records ahead of the rows they belong to (one wait for the chunk, not one per row); the
-// predicate is a handful of VALU compares whose result lives in a lane mask.  A row that NO lane of the wave may match is left
-// without its descriptor loads and popcounts: a uniform branch on the mask.  `on`: the lane takes part at all.
-// ok[i]: this lane may match row tc + i; live[i]: the lanes of the wave that may.  The ballots are taken for the whole chunk BEFORE
-// the first branch (a ballot is not moved below a branch), so the chunk's keypoint loads and compares stay together in front of
-// its rows instead of one load and wait in front of each.  (No scheduling barrier between the loads and the compares: with one
-// the compiler no longer takes the loop's loads - the descriptor rows included - for scalar loads.)
-#define MPG_CHUNK 4
-template <bool SWAP>
-__device__ __forceinline__ void mpg_allowed(const BriskMatchGate& g, const BriskGateLane& L, bool on, const char* kps, int tc, int t1,
-                                            bool (&ok)[MPG_CHUNK], unsigned long long (&live)[MPG_CHUNK]) {
-#pragma unroll
-  for (int i = 0; i < MPG_CHUNK; ++i) {
-    const BriskKeyPoint* kp = mp_kp(kps, min(tc + i, t1 - 1));
-    const bool pass = SWAP ? brisk_gate_train_lane(g, L, kp->x, kp->y, kp->octave) : brisk_gate_query_lane(g, L, kp->x, kp->y, kp->octave);
-    ok[i] = on && tc + i < t1 && pass;
-    live[i] = __ballot(ok[i]);
-  }
-}
-template <int W32, bool ALIGNED>
-__device__ __forceinline__ void mrpg_scan(const unsigned (&qv)[W32], const uint8_t* rows, int pitch, int t0, int t1, unsigned thr,
-                                          const BriskMatchGate& g, const BriskGateLane& L, bool on, const char* kps, int* cnt,
-                                          unsigned (*list)[64], int lane) {
-  for (int tc = t0; tc < t1; tc += MPG_CHUNK) {
-    bool ok[MPG_CHUNK];
-    unsigned long long live[MPG_CHUNK];
-    mpg_allowed<false>(g, L, on, kps, tc, t1, ok, live);
-#pragma unroll
-    for (int i = 0; i < MPG_CHUNK; ++i) {
-      if (live[i] == 0) continue;  // wave-uniform
-      const int t = tc + i;
-      const unsigned d = mrp_dist<W32, ALIGNED>(qv, rows + (long)t * pitch);
-      if (ok[i] && d < thr) {
-        const int slot = atomicAdd(&cnt[lane], 1);
-        if (slot < MRP_LIST) list[slot][lane] = (d << MF_IDX_BITS) | (unsigned)t;
-      }
     }
   }
 }
@@ -734,233 +744,17 @@ __device__ __forceinline__ void mrp_body(const uint8_t* qrows, int q_pitch, bool
   }
 }
 
-// grid (ceil(rows_cap / 64), pairs): pair and counts resolved as k_match_knn_pairs does
 template <int W32>
 __global__ void __launch_bounds__(MP_WAVES * 64) k_match_radius_pairs(const BriskDescSet Q, const BriskDescSet T, const BriskPairSpec P,
                                                                        int pair0, float max_distance, int cap, int rows_cap,
                                                                        BriskDMatch* __restrict__ out, int* __restrict__ out_count,
                                                                        int* __restrict__ pair_rows) {
   const int p = pair0 + blockIdx.y;
-  int a, b;
-  if (P.pairs) {
-    a = P.pairs[2 * (long)p];
-    b = P.pairs[2 * (long)p + 1];
-  } else {
-    a = P.query_first + p * P.query_step;
-    b = P.train_first + p * P.train_step;
-  }
-  const bool first = blockIdx.x == 0 && threadIdx.x == 0;
-  if (a < 0 || a >= Q.frames || b < 0 || b >= T.frames) {  // (a bad entry of the caller's list; the arithmetic form is checked on the host)
-    if (first) pair_rows[p] = -1;
-    return;
-  }
-  const int n_a = max(0, Q.counts[(long)a * Q.count_stride]), n_b = max(0, T.counts[(long)b * T.count_stride]);
-  if (n_b >= (1 << MF_IDX_BITS)) {  // (the keys hold 22 index bits)
-    if (first) pair_rows[p] = -1;
-    return;
-  }
-  if (first) pair_rows[p] = n_a;
-  const int rows = min(n_a, rows_cap);
-  if ((int)blockIdx.x * 64 >= rows) return;
-  const bool q_aligned = (((uintptr_t)Q.desc | (unsigned long)Q.frame_pitch | (unsigned)Q.row_pitch) & 3) == 0;
-  const bool t_aligned = (((uintptr_t)T.desc | (unsigned long)T.frame_pitch | (unsigned)T.row_pitch) & 3) == 0;
-  mrp_body<W32>(Q.desc + (long)a * Q.frame_pitch, Q.row_pitch, q_aligned, rows, T.desc + (long)b * T.frame_pitch, T.row_pitch, t_aligned,
-                n_b, max_distance, cap, b, out + (long)p * rows_cap * cap, out_count + (long)p * rows_cap);
+  MpPair R;
+  if (!mp_resolve(Q, T, P, p, false, rows_cap, pair_rows, R)) return;
+  mrp_body<W32>(mp_frame(Q, R.a), Q.row_pitch, R.q_aligned, R.rows, mp_frame(T, R.b), T.row_pitch, R.t_aligned, R.n_b, max_distance, cap, R.b,
+                out + (long)p * rows_cap * cap, out_count + (long)p * rows_cap);
 }
-
-// one query set against one train set, counts from the host (brisk_hip_match_radius_device); grid ceil(nq / 64)
-template <int W32>
-__global__ void __launch_bounds__(MP_WAVES * 64) k_match_radius_pairs_one(const uint8_t* __restrict__ query, int q_pitch, int nq,
-                                                                           const uint8_t* __restrict__ train, int t_pitch, int nt,
-                                                                           float max_distance, int cap, BriskDMatch* __restrict__ out,
-                                                                           int* __restrict__ out_count) {
-  const bool q_aligned = (((uintptr_t)query | (unsigned)q_pitch) & 3) == 0, t_aligned = (((uintptr_t)train | (unsigned)t_pitch) & 3) == 0;
-  mrp_body<W32>(query, q_pitch, q_aligned, nq, train, t_pitch, t_aligned, nt, max_distance, cap, 0, out, out_count);
-}
-
-template <int W32>
-static void mrp_launch(const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, float max_distance, int cap, int rows_cap,
-                       BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s) {
-  const dim3 block(MP_WAVES * 64);
-  for (int p0 = 0; p0 < P.npairs; p0 += 65535) {  // (grid.y holds 65535)
-    const dim3 grid((rows_cap + 63) / 64, min(65535, P.npairs - p0));
-    hipLaunchKernelGGL(k_match_radius_pairs<W32>, grid, block, 0, s, Q, T, P, p0, max_distance, cap, rows_cap, out, out_count, pair_rows);
-  }
-}
-// false: descriptor size not covered (16, 32, 48, 64 bytes are)
-bool brisk_launch_match_radius_pairs(const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, int words32, float max_distance,
-                                     int cap, int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s) {
-  switch (words32) {
-    case 4: mrp_launch<4>(Q, T, P, max_distance, cap, rows_cap, out, out_count, pair_rows, s); break;
-    case 8: mrp_launch<8>(Q, T, P, max_distance, cap, rows_cap, out, out_count, pair_rows, s); break;
-    case 12: mrp_launch<12>(Q, T, P, max_distance, cap, rows_cap, out, out_count, pair_rows, s); break;
-    case 16: mrp_launch<16>(Q, T, P, max_distance, cap, rows_cap, out, out_count, pair_rows, s); break;
-    default: return false;
-  }
-  return true;
-}
-// false: not covered (descriptor size, nt >= 2^22): the caller uses the distance-matrix path
-bool brisk_launch_match_radius_fused(const uint8_t* query, int q_pitch, int nq, const uint8_t* train, int t_pitch, int nt, int words32,
-                                     float max_distance, int cap, BriskDMatch* out, int* out_count, hipStream_t s) {
-  if (nq <= 0 || nt < 0 || nt >= (1 << MF_IDX_BITS) || cap < 1) return false;
-  const dim3 grid((nq + 63) / 64), block(MP_WAVES * 64);
-  switch (words32) {
-    case 4: hipLaunchKernelGGL(k_match_radius_pairs_one<4>, grid, block, 0, s, query, q_pitch, nq, train, t_pitch, nt, max_distance, cap, out, out_count); break;
-    case 8: hipLaunchKernelGGL(k_match_radius_pairs_one<8>, grid, block, 0, s, query, q_pitch, nq, train, t_pitch, nt, max_distance, cap, out, out_count); break;
-    case 12: hipLaunchKernelGGL(k_match_radius_pairs_one<12>, grid, block, 0, s, query, q_pitch, nq, train, t_pitch, nt, max_distance, cap, out, out_count); break;
-    case 16: hipLaunchKernelGGL(k_match_radius_pairs_one<16>, grid, block, 0, s, query, q_pitch, nq, train, t_pitch, nt, max_distance, cap, out, out_count); break;
-    default: return false;
-  }
-  return true;
-}
-
-// ------------------------------------------------------------------------------------------------
-// The two pair matchers behind a position gate (brisk_hip_match_knn_pairs_gated_device / brisk_hip_match_radius_pairs_gated_device):
-// the mask of a pair is the predicate of brisk_match_gate.h on the two rows' keypoints, evaluated inside the scan (mpg_allowed
-// above).  Same grid, same 8-wave workgroups, same LDS, no scratch, no workspace.  k-NN: a lane the gate forbids keeps its key
-// 0xFFFFFFFF, so a row holds min(k, allowed rows) REAL matches and is never topped up.  CROSS: the roles swap - the lane holds
-// keypoint T of its forward match (a lane without one takes no part), the row passing by is q'.
-// ------------------------------------------------------------------------------------------------
-// pair, counts and d_pair_rows as k_match_knn_pairs / k_match_radius_pairs resolve them; false: nothing to do for this workgroup
-__device__ __forceinline__ bool mpg_resolve(const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, int p, bool back_keys,
-                                            int rows_cap, int* __restrict__ pair_rows, int& a, int& b, int& n_a, int& n_b, int& rows) {
-  if (P.pairs) {
-    a = P.pairs[2 * (long)p];
-    b = P.pairs[2 * (long)p + 1];
-  } else {
-    a = P.query_first + p * P.query_step;
-    b = P.train_first + p * P.train_step;
-  }
-  const bool first = blockIdx.x == 0 && threadIdx.x == 0;
-  if (a < 0 || a >= Q.frames || b < 0 || b >= T.frames) {  // (a bad entry of the caller's list; the arithmetic form is checked on the host)
-    if (first) pair_rows[p] = -1;
-    return false;
-  }
-  n_a = max(0, Q.counts[(long)a * Q.count_stride]);
-  n_b = max(0, T.counts[(long)b * T.count_stride]);
-  if (n_b >= (1 << MF_IDX_BITS) || (back_keys && n_a >= (1 << MF_IDX_BITS))) {  // (the keys hold 22 index bits)
-    if (first) pair_rows[p] = -1;
-    return false;
-  }
-  if (first) pair_rows[p] = n_a;
-  rows = min(n_a, rows_cap);
-  return (int)blockIdx.x * 64 < rows;
-}
-
-// rows [t0, t1) of one frame against the lane's descriptor, behind the gate: the two smallest keys among the allowed rows
-template <int W32, bool ALIGNED, bool SWAP>
-__device__ __forceinline__ void mpg_scan(const unsigned (&qv)[W32], const uint8_t* rows, int pitch, int t0, int t1, const BriskMatchGate& g,
-                                         const BriskGateLane& L, bool on, const char* kps, unsigned& b1, unsigned& b2) {
-  for (int tc = t0; tc < t1; tc += MPG_CHUNK) {
-    bool ok[MPG_CHUNK];
-    unsigned long long live[MPG_CHUNK];
-    mpg_allowed<SWAP>(g, L, on, kps, tc, t1, ok, live);
-#pragma unroll
-    for (int i = 0; i < MPG_CHUNK; ++i) {
-      if (live[i] == 0) continue;  // wave-uniform
-      const int t = tc + i;
-      const unsigned d = mrp_dist<W32, ALIGNED>(qv, rows + (long)t * pitch);
-      const unsigned key = ok[i] ? (d << MF_IDX_BITS) | (unsigned)t : 0xFFFFFFFFu;
-      b2 = min(b2, max(b1, key));
-      b1 = min(b1, key);
-    }
-  }
-}
-
-template <int W32, bool CROSS>
-__global__ void __launch_bounds__(MP_WAVES * 64) k_match_knn_pairs_gated(const BriskDescSet Q, const BriskDescSet T, const BriskKpSet QK,
-                                                                          const BriskKpSet TK, const BriskMatchGate gate,
-                                                                          const BriskPairSpec P, int pair0, int k, int rows_cap,
-                                                                          BriskDMatch* __restrict__ out, int* __restrict__ out_count,
-                                                                          int* __restrict__ pair_rows) {
-  __shared__ unsigned part[MP_WAVES][2][64];
-  __shared__ unsigned fwd[64];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int p = pair0 + blockIdx.y;
-  int a, b, n_a, n_b, rows;
-  if (!mpg_resolve(Q, T, P, p, CROSS, rows_cap, pair_rows, a, b, n_a, n_b, rows)) return;
-  const int q = blockIdx.x * 64 + lane;
-  BriskDMatch* orow = out + ((long)p * rows_cap + q) * k;
-  int* ocnt = out_count + (long)p * rows_cap + q;
-  if (n_b == 0) {
-    if (wave == 0 && q < rows) *ocnt = 0;
-    return;
-  }
-  const uint8_t* qrows = Q.desc + (long)a * Q.frame_pitch;
-  const uint8_t* trows = T.desc + (long)b * T.frame_pitch;
-  const char* qk = QK.kps + (long)a * QK.frame_pitch;
-  const char* tk = TK.kps + (long)b * TK.frame_pitch;
-  const bool q_aligned = (((uintptr_t)Q.desc | (unsigned long)Q.frame_pitch | (unsigned)Q.row_pitch) & 3) == 0;
-  const bool t_aligned = (((uintptr_t)T.desc | (unsigned long)T.frame_pitch | (unsigned)T.row_pitch) & 3) == 0;
-  unsigned b1 = 0xFFFFFFFFu, b2 = 0xFFFFFFFFu;
-  {
-    unsigned qv[W32];
-    mp_load_row<W32>(qrows + (long)min(q, rows - 1) * Q.row_pitch, q_aligned, qv);
-    const BriskKeyPoint* kp = mp_kp(qk, min(q, rows - 1));
-    const BriskGateLane L = brisk_gate_lane(gate, kp->x, kp->y, kp->octave);
-    const int per = (n_b + MP_WAVES - 1) / MP_WAVES;
-    const int t0 = __builtin_amdgcn_readfirstlane(wave * per), t1 = min(n_b, t0 + per);
-    if (t_aligned) mpg_scan<W32, true, false>(qv, trows, T.row_pitch, t0, t1, gate, L, q < rows, tk, b1, b2);
-    else mpg_scan<W32, false, false>(qv, trows, T.row_pitch, t0, t1, gate, L, q < rows, tk, b1, b2);
-  }
-  part[wave][0][lane] = b1;
-  part[wave][1][lane] = b2;
-  __syncthreads();
-  unsigned m1 = 0xFFFFFFFFu, m2 = 0xFFFFFFFFu;
-  if (wave == 0) {
-#pragma unroll
-    for (int w = 0; w < MP_WAVES; ++w)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const unsigned key = part[w][i][lane];
-        m2 = min(m2, max(m1, key));
-        m1 = min(m1, key);
-      }
-  }
-  bool keep = true;
-  if (CROSS) {
-    if (wave == 0) fwd[lane] = m1;
-    __syncthreads();  // (also: wave 0 has read part[] before anybody writes it again)
-    const unsigned f = fwd[lane];
-    const bool has = f != 0xFFFFFFFFu;  // (the gate may have left the row without a forward match)
-    const int t = has ? (int)(f & ((1u << MF_IDX_BITS) - 1)) : 0;
-    unsigned tv[W32];
-    mp_load_row<W32>(trows + (long)t * T.row_pitch, t_aligned, tv);
-    const BriskKeyPoint* kp = mp_kp(tk, t);
-    const BriskGateLane L = brisk_gate_lane(gate, kp->x, kp->y, kp->octave);
-    unsigned c1 = 0xFFFFFFFFu, c2 = 0xFFFFFFFFu;
-    const int per = (n_a + MP_WAVES - 1) / MP_WAVES;
-    const int r0 = __builtin_amdgcn_readfirstlane(wave * per), r1 = min(n_a, r0 + per);
-    // ALL rows q' of frame a, also those beyond rows_cap: M[q'][t]
-    if (q_aligned) mpg_scan<W32, true, true>(tv, qrows, Q.row_pitch, r0, r1, gate, L, has, qk, c1, c2);
-    else mpg_scan<W32, false, true>(tv, qrows, Q.row_pitch, r0, r1, gate, L, has, qk, c1, c2);
-    part[wave][0][lane] = c1;
-    __syncthreads();
-    if (wave == 0) {
-      unsigned best = 0xFFFFFFFFu;
-#pragma unroll
-      for (int w = 0; w < MP_WAVES; ++w) best = min(best, part[w][0][lane]);
-      keep = has && (int)(best & ((1u << MF_IDX_BITS) - 1)) == q;
-    }
-  }
-  if (wave == 0 && q < rows) {
-    int n = 0;
-    if (keep && m1 != 0xFFFFFFFFu) {
-      BriskDMatch m;
-      m.queryIdx = q; m.imgIdx = b;
-      m.trainIdx = (int)(m1 & ((1u << MF_IDX_BITS) - 1)); m.distance = (float)(m1 >> MF_IDX_BITS);
-      orow[0] = m;
-      n = 1;
-      if (k > 1 && m2 != 0xFFFFFFFFu) {  // (no top-up: a second entry only where a second row is allowed)
-        m.trainIdx = (int)(m2 & ((1u << MF_IDX_BITS) - 1)); m.distance = (float)(m2 >> MF_IDX_BITS);
-        orow[1] = m;
-        n = 2;
-      }
-    }
-    *ocnt = n;
-  }
-}
-
 template <int W32>
 __global__ void __launch_bounds__(MP_WAVES * 64) k_match_radius_pairs_gated(const BriskDescSet Q, const BriskDescSet T, const BriskKpSet QK,
                                                                              const BriskKpSet TK, const BriskMatchGate gate,
@@ -968,67 +762,102 @@ __global__ void __launch_bounds__(MP_WAVES * 64) k_match_radius_pairs_gated(cons
                                                                              int rows_cap, BriskDMatch* __restrict__ out,
                                                                              int* __restrict__ out_count, int* __restrict__ pair_rows) {
   const int p = pair0 + blockIdx.y;
-  int a, b, n_a, n_b, rows;
-  if (!mpg_resolve(Q, T, P, p, false, rows_cap, pair_rows, a, b, n_a, n_b, rows)) return;
-  const bool q_aligned = (((uintptr_t)Q.desc | (unsigned long)Q.frame_pitch | (unsigned)Q.row_pitch) & 3) == 0;
-  const bool t_aligned = (((uintptr_t)T.desc | (unsigned long)T.frame_pitch | (unsigned)T.row_pitch) & 3) == 0;
-  const MpGate G{gate, QK.kps + (long)a * QK.frame_pitch, TK.kps + (long)b * TK.frame_pitch};
-  mrp_body<W32, true>(Q.desc + (long)a * Q.frame_pitch, Q.row_pitch, q_aligned, rows, T.desc + (long)b * T.frame_pitch, T.row_pitch,
-                      t_aligned, n_b, max_distance, cap, b, out + (long)p * rows_cap * cap, out_count + (long)p * rows_cap, G);
+  MpPair R;
+  if (!mp_resolve(Q, T, P, p, false, rows_cap, pair_rows, R)) return;
+  const MpGate G{gate, QK.kps + (long)R.a * QK.frame_pitch, TK.kps + (long)R.b * TK.frame_pitch};
+  mrp_body<W32, true>(mp_frame(Q, R.a), Q.row_pitch, R.q_aligned, R.rows, mp_frame(T, R.b), T.row_pitch, R.t_aligned, R.n_b, max_distance, cap, R.b,
+                      out + (long)p * rows_cap * cap, out_count + (long)p * rows_cap, G);
+}
+// one query set against one train set, counts from the host (brisk_hip_match_radius_device); grid ceil(nq / 64)
+template <int W32>
+__global__ void __launch_bounds__(MP_WAVES * 64) k_match_radius_pairs_one(const uint8_t* __restrict__ query, int q_pitch, int nq,
+                                                                           const uint8_t* __restrict__ train, int t_pitch, int nt,
+                                                                           float max_distance, int cap, BriskDMatch* __restrict__ out,
+                                                                           int* __restrict__ out_count) {
+  mrp_body<W32>(query, q_pitch, m_aligned(query, 0, q_pitch), nq, train, t_pitch, m_aligned(train, 0, t_pitch), nt, max_distance, cap, 0, out,
+                out_count);
 }
 
-template <int W32>
-static void mpg_launch(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK, const BriskMatchGate& gate,
-                       const BriskPairSpec& P, int k, bool cross, int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows,
-                       hipStream_t s) {
-  const dim3 block(MP_WAVES * 64);
-  for (int p0 = 0; p0 < P.npairs; p0 += 65535) {  // (grid.y holds 65535)
-    const dim3 grid((rows_cap + 63) / 64, min(65535, P.npairs - p0));
-    if (cross)
-      hipLaunchKernelGGL((k_match_knn_pairs_gated<W32, true>), grid, block, 0, s, Q, T, QK, TK, gate, P, p0, k, rows_cap, out, out_count,
-                         pair_rows);
-    else
-      hipLaunchKernelGGL((k_match_knn_pairs_gated<W32, false>), grid, block, 0, s, Q, T, QK, TK, gate, P, p0, k, rows_cap, out, out_count,
-                         pair_rows);
+// ------------------------------------------------------------------------------------------------
+// Launches of the register-row path.  The brisk_launch_* functions return false when the case is not covered (the descriptor
+// size, or what each states): the caller uses the distance-matrix path or reports it.
+// ------------------------------------------------------------------------------------------------
+// f(std::integral_constant<int, W32>) for the descriptor sizes the kernels are built for: 16, 32, 48, 64 bytes
+template <class F>
+static bool m_dispatch_words(int words32, F&& f) {
+  switch (words32) {
+    case 4: f(std::integral_constant<int, 4>()); break;
+    case 8: f(std::integral_constant<int, 8>()); break;
+    case 12: f(std::integral_constant<int, 12>()); break;
+    case 16: f(std::integral_constant<int, 16>()); break;
+    default: return false;
   }
+  return true;
 }
-// false: descriptor size not covered (16, 32, 48, 64 bytes are)
+// launch(grid, first pair) for grid (ceil(rows_cap / 64), pairs), 65535 pairs at a time (what grid.y holds)
+template <class F>
+static void mp_launch_pairs(int npairs, int rows_cap, F&& launch) {
+  for (int p0 = 0; p0 < npairs; p0 += 65535) launch(dim3((rows_cap + 63) / 64, min(65535, npairs - p0)), p0);
+}
+
+bool brisk_launch_match_knn_fused(const uint8_t* query, int q_pitch, int nq, const uint8_t* train, int t_pitch, int nt,
+                                  int words32, int k, BriskDMatch* out, int* out_count, hipStream_t s) {
+  if (k < 1 || k > 2 || nt < k || nt >= (1 << MF_IDX_BITS) || nq <= 0) return false;
+  return m_dispatch_words(words32, [&](auto W) {
+    hipLaunchKernelGGL(k_match_knn_fused<decltype(W)::value>, dim3((nq + 63) / 64), dim3(MF_WAVES * 64), 0, s, query, q_pitch, nq, train,
+                       t_pitch, nt, k, out, out_count);
+  });
+}
+bool brisk_launch_match_knn_pairs(const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, int words32, int k, bool cross,
+                                  int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s) {
+  return m_dispatch_words(words32, [&](auto W) {
+    constexpr int W32 = decltype(W)::value;
+    mp_launch_pairs(P.npairs, rows_cap, [&](dim3 grid, int p0) {
+      if (cross) hipLaunchKernelGGL((k_match_knn_pairs<W32, true>), grid, dim3(MP_WAVES * 64), 0, s, Q, T, P, p0, k, rows_cap, out, out_count, pair_rows);
+      else hipLaunchKernelGGL((k_match_knn_pairs<W32, false>), grid, dim3(MP_WAVES * 64), 0, s, Q, T, P, p0, k, rows_cap, out, out_count, pair_rows);
+    });
+  });
+}
 bool brisk_launch_match_knn_pairs_gated(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
                                         const BriskMatchGate& gate, const BriskPairSpec& P, int words32, int k, bool cross, int rows_cap,
                                         BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s) {
-  switch (words32) {
-    case 4: mpg_launch<4>(Q, T, QK, TK, gate, P, k, cross, rows_cap, out, out_count, pair_rows, s); break;
-    case 8: mpg_launch<8>(Q, T, QK, TK, gate, P, k, cross, rows_cap, out, out_count, pair_rows, s); break;
-    case 12: mpg_launch<12>(Q, T, QK, TK, gate, P, k, cross, rows_cap, out, out_count, pair_rows, s); break;
-    case 16: mpg_launch<16>(Q, T, QK, TK, gate, P, k, cross, rows_cap, out, out_count, pair_rows, s); break;
-    default: return false;
-  }
-  return true;
+  return m_dispatch_words(words32, [&](auto W) {
+    constexpr int W32 = decltype(W)::value;
+    mp_launch_pairs(P.npairs, rows_cap, [&](dim3 grid, int p0) {
+      if (cross)
+        hipLaunchKernelGGL((k_match_knn_pairs_gated<W32, true>), grid, dim3(MP_WAVES * 64), 0, s, Q, T, QK, TK, gate, P, p0, k, rows_cap, out, out_count, pair_rows);
+      else
+        hipLaunchKernelGGL((k_match_knn_pairs_gated<W32, false>), grid, dim3(MP_WAVES * 64), 0, s, Q, T, QK, TK, gate, P, p0, k, rows_cap, out, out_count, pair_rows);
+    });
+  });
 }
-
-template <int W32>
-static void mrpg_launch(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK, const BriskMatchGate& gate,
-                        const BriskPairSpec& P, float max_distance, int cap, int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows,
-                        hipStream_t s) {
-  const dim3 block(MP_WAVES * 64);
-  for (int p0 = 0; p0 < P.npairs; p0 += 65535) {  // (grid.y holds 65535)
-    const dim3 grid((rows_cap + 63) / 64, min(65535, P.npairs - p0));
-    hipLaunchKernelGGL(k_match_radius_pairs_gated<W32>, grid, block, 0, s, Q, T, QK, TK, gate, P, p0, max_distance, cap, rows_cap, out,
-                       out_count, pair_rows);
-  }
+bool brisk_launch_match_radius_pairs(const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, int words32, float max_distance,
+                                     int cap, int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s) {
+  return m_dispatch_words(words32, [&](auto W) {
+    mp_launch_pairs(P.npairs, rows_cap, [&](dim3 grid, int p0) {
+      hipLaunchKernelGGL(k_match_radius_pairs<decltype(W)::value>, grid, dim3(MP_WAVES * 64), 0, s, Q, T, P, p0, max_distance, cap, rows_cap, out,
+                         out_count, pair_rows);
+    });
+  });
 }
-// false: descriptor size not covered (16, 32, 48, 64 bytes are)
 bool brisk_launch_match_radius_pairs_gated(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
                                            const BriskMatchGate& gate, const BriskPairSpec& P, int words32, float max_distance, int cap,
                                            int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s) {
-  switch (words32) {
-    case 4: mrpg_launch<4>(Q, T, QK, TK, gate, P, max_distance, cap, rows_cap, out, out_count, pair_rows, s); break;
-    case 8: mrpg_launch<8>(Q, T, QK, TK, gate, P, max_distance, cap, rows_cap, out, out_count, pair_rows, s); break;
-    case 12: mrpg_launch<12>(Q, T, QK, TK, gate, P, max_distance, cap, rows_cap, out, out_count, pair_rows, s); break;
-    case 16: mrpg_launch<16>(Q, T, QK, TK, gate, P, max_distance, cap, rows_cap, out, out_count, pair_rows, s); break;
-    default: return false;
-  }
-  return true;
+  return m_dispatch_words(words32, [&](auto W) {
+    mp_launch_pairs(P.npairs, rows_cap, [&](dim3 grid, int p0) {
+      hipLaunchKernelGGL(k_match_radius_pairs_gated<decltype(W)::value>, grid, dim3(MP_WAVES * 64), 0, s, Q, T, QK, TK, gate, P, p0, max_distance, cap,
+                         rows_cap, out, out_count, pair_rows);
+    });
+  });
+}
+// (also not covered: nt >= 2^22)
+bool brisk_launch_match_radius_fused(const uint8_t* query, int q_pitch, int nq, const uint8_t* train, int t_pitch, int nt, int words32,
+                                     float max_distance, int cap, BriskDMatch* out, int* out_count, hipStream_t s) {
+  if (nq <= 0 || nt < 0 || nt >= (1 << MF_IDX_BITS) || cap < 1) return false;
+  return m_dispatch_words(words32, [&](auto W) {
+    hipLaunchKernelGGL(k_match_radius_pairs_one<decltype(W)::value>, dim3((nq + 63) / 64), dim3(MP_WAVES * 64), 0, s, query, q_pitch, nq, train, t_pitch,
+                       nt, max_distance, cap, out, out_count);
+  });
 }
 
 void brisk_launch_match_dist(const uint8_t* query, int q_pitch, int q0, int nqb, const uint8_t* train, int t_pitch, int nt,
