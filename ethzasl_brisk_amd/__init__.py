@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "brisk_hip_batch_desc_set", "brisk_hip_match_knn_pairs_device",
     "brisk_hip_match_radius_pairs_device", "brisk_hip_match_radius_device",
     "brisk_hip_batch_kp_set", "brisk_hip_match_knn_pairs_gated_device", "brisk_hip_match_radius_pairs_gated_device",
+    "brisk_hip_select_pair_matches_device", "brisk_hip_pair_matches_download", "brisk_hip_pair_matches_wait",
 ]
 # every symbol include/brisk_hip_debug.h declares: test / tuning builds (BRISK_HIP_TUNING) only
 DEBUG_SYMBOLS = [
@@ -95,6 +96,57 @@ class MatchGate(C.Structure):
         return cls(-float("inf"), float("inf"), -float("inf"), float("inf"), -1)
 
 
+class MatchSelect(C.Structure):
+    """brisk_hip_match_select: an entry is kept iff distance < max_distance (and it is no top-up entry); ratio > 0: Lowe's ratio
+    test, the row gives at most its best entry; otherwise the leading keep_per_row entries that pass"""
+    _fields_ = [("max_distance", C.c_float), ("ratio", C.c_float), ("keep_per_row", C.c_int)]
+
+    @classmethod
+    def everything(cls, per_row):
+        return cls(float("inf"), 0.0, int(per_row))
+
+
+class PairHostMatches(C.Structure):
+    """brisk_hip_pair_host_matches: capacities + the five destination arrays of a batch's selected matches in host memory"""
+    _fields_ = [("pairs_cap", C.c_int), ("matches_cap", C.c_longlong), ("pair_rows", C.c_void_p), ("counts", C.c_void_p),
+                ("flags", C.c_void_p), ("offsets", C.c_void_p), ("matches", C.c_void_p)]
+
+
+# flags of a pair in the selected lists (ROWS_CUT: the pair and every pair behind it did not fit matches_cap)
+PAIR_ROWS_CUT, PAIR_BAD, PAIR_ENTRIES_CUT = 1, 2, 4
+
+
+def _host_array(n, dtype, pinned, keep):
+    """n (at least 1) elements of host memory: from torch's pinned allocator (kept alive in `keep`), or a plain NumPy array"""
+    n = max(int(n), 1)
+    if pinned:
+        import torch
+        t = torch.empty(n * np.dtype(dtype).itemsize, dtype=torch.uint8).pin_memory()
+        keep.append(t)
+        return t.numpy().view(dtype)
+    return np.empty(n, dtype)
+
+
+class HostMatches:
+    """Destination arrays of brisk_hip_pair_matches_download: `pairs` pairs, `matches` DMATCH records in total.  pinned as in
+    HostResults."""
+
+    def __init__(self, pairs, matches, pinned=True):
+        self.pairs, self.matches_cap = int(pairs), int(matches)
+        self._keep = []
+        self.pair_rows = _host_array(pairs, np.int32, pinned, self._keep)
+        self.counts = _host_array(pairs, np.int32, pinned, self._keep)
+        self.flags = _host_array(pairs, np.int32, pinned, self._keep)
+        self.offsets = _host_array(pairs + 1, np.int64, pinned, self._keep)
+        self.matches = _host_array(matches, DMATCH, pinned, self._keep)
+        self.struct = PairHostMatches(self.pairs, self.matches_cap, self.pair_rows.ctypes.data, self.counts.ctypes.data,
+                                      self.flags.ctypes.data, self.offsets.ctypes.data, self.matches.ctypes.data)
+
+    def pair(self, p):
+        """the selected matches of pair p, in (query row, rank) order: a view of the records [offsets[p], offsets[p + 1])"""
+        return self.matches[int(self.offsets[p]):int(self.offsets[p + 1])]
+
+
 class HostResults:
     """Destination arrays of brisk_hip_batch_download_all: `frames` frames, `rows` rows in total, descriptor rows of
     `desc_stride` bytes (0 = keypoints only).  pinned=True takes them from torch's pinned allocator (the device then writes
@@ -105,13 +157,7 @@ class HostResults:
         self._keep = []
 
         def arr(n, dtype):
-            n = max(int(n), 1)
-            if pinned:
-                import torch
-                t = torch.empty(n * np.dtype(dtype).itemsize, dtype=torch.uint8).pin_memory()
-                self._keep.append(t)
-                return t.numpy().view(dtype)
-            return np.empty(n, dtype)
+            return _host_array(n, dtype, pinned, self._keep)
         self.counts = arr(frames, np.int32)
         self.flags = arr(frames, np.int32)
         self.offsets = arr(frames + 1, np.int64)
@@ -222,6 +268,11 @@ def load_library():
     L.brisk_hip_match_radius_pairs_gated_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
                                                             C.POINTER(MatchGate), C.POINTER(PairSpec), C.c_int, C.c_float, C.c_int, C.c_int,
                                                             vp, vp, vp, vp]
+    L.brisk_hip_select_pair_matches_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(MatchSelect), C.c_longlong,
+                                                       vp, vp, vp, vp, vp]
+    L.brisk_hip_pair_matches_download.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(MatchSelect),
+                                                  C.POINTER(PairHostMatches), vp, C.POINTER(C.c_uint)]
+    L.brisk_hip_pair_matches_wait.argtypes = [vp, C.c_uint, ip]
     L.brisk_hip_reserve.argtypes = [vp, C.c_int, C.c_int]
     L.brisk_hip_detect_uniform.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
                                            C.c_double, C.c_int, vp, C.c_int, ip]
@@ -588,6 +639,45 @@ class Context:
         nrows = [min(max(int(hr[p]), 0), rows_cap) for p in range(n)]
         return ([[hm[p, q, :min(int(hc[p, q]), cpq)].copy() for q in range(nrows[p])] for p in range(n)],
                 [hc[p, :nrows[p]].copy() for p in range(n)])
+
+    # -- the pair matchers' exit: selected matches, packed --
+    def select_pair_matches(self, out_triple, per_row, select, matches_cap=None, stream=None):
+        """brisk_hip_select_pair_matches_device on what match_knn_pairs / match_radius_pairs returned (out_triple; per_row = that
+        call's k or cap_per_query).  select: a MatchSelect.  matches_cap None = every stored entry fits (npairs * rows_cap * per_row).
+        Returns the device tensors (matches [matches_cap, 4] int32 - DMATCH records in (pair, query row, rank) order -, counts
+        [npairs], flags [npairs], offsets [npairs + 1] int64; offsets[npairs] = matches stored).  Asynchronous on `stream`."""
+        import torch
+        m, cnt, rows = out_triple
+        n, rows_cap = int(cnt.shape[0]), int(cnt.shape[1])
+        if matches_cap is None:
+            matches_cap = n * rows_cap * int(per_row)
+        dev = m.device
+        res = (torch.empty((max(int(matches_cap), 0), 4), dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+               torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n + 1, dtype=torch.int64, device=dev))
+        self.check(self._L.brisk_hip_select_pair_matches_device(self._h, m.data_ptr(), cnt.data_ptr(), rows.data_ptr(), n, rows_cap,
+                                                                int(per_row), C.byref(select), int(matches_cap), res[1].data_ptr(),
+                                                                res[2].data_ptr(), res[3].data_ptr(), res[0].data_ptr(),
+                                                                C.c_void_p(stream) if stream else None))
+        return res
+
+    def pair_matches_download(self, out_triple, per_row, select, dst, stream=None):
+        """brisk_hip_pair_matches_download: selection + transfer of out_triple's matches into `dst` (HostMatches) queued on `stream`
+        (the stream the matcher ran on); out_triple may be overwritten by the next batch in stream order.  Returns the ticket."""
+        m, cnt, rows = out_triple
+        t = C.c_uint()
+        self.check(self._L.brisk_hip_pair_matches_download(self._h, m.data_ptr(), cnt.data_ptr(), rows.data_ptr(), int(cnt.shape[0]),
+                                                           int(cnt.shape[1]), int(per_row), C.byref(select), C.byref(dst.struct),
+                                                           C.c_void_p(stream) if stream else None, C.byref(t)))
+        return t.value
+
+    def pair_matches_wait(self, ticket, check=True):
+        """completes transfer `ticket`; returns the number of flagged pairs (check=False: (rc, flagged) instead of raising)"""
+        n = C.c_int()
+        rc = self._L.brisk_hip_pair_matches_wait(self._h, ticket, C.byref(n))
+        if not check:
+            return rc, n.value
+        self.check(rc)
+        return n.value
 
     def match_radius_device(self, d_query, nq, q_pitch, d_train, nt, t_pitch, dim_bytes, max_distance, cap_per_query, d_out, d_out_count,
                             stream=None):

@@ -152,6 +152,21 @@ struct brisk_hip_ctx {
   } ex[2];
   hipStream_t egress = nullptr;
   unsigned ex_seq = 0;
+  // brisk_hip_pair_matches_download: two slots of its own (a stream that downloads rows AND matches keeps two batches in flight)
+  struct MatchSlot {
+    DeviceBuf slab;
+    PinnedBuf bounce;
+    hipEvent_t packed = nullptr, done = nullptr;
+    bool done_valid = false, pending = false, use_bounce = false;  // as ExportSlot's
+    unsigned ticket = 0;
+    int npairs = 0;
+    brisk_hip_pair_host_matches dst{};  // the caller's destinations
+    brisk_hip_pair_host_matches wr{};   // where the egress kernel writes (the caller's arrays, or the bounce buffer)
+    int rc = BRISK_HIP_OK, flagged = 0;
+    std::string msg;
+  } mx[2];
+  unsigned mx_seq = 0;
+  DeviceBuf d_select;  // brisk_hip_select_pair_matches_device / _pair_matches_download: the per-workgroup sums of the selection passes
   int last_strings = 0;  // descriptor bytes of the pattern the last describing call used
 };
 
@@ -500,6 +515,10 @@ void brisk_hip_destroy(brisk_hip_ctx* c) {
   if (c->kin_pin_ev) hipEventDestroy(c->kin_pin_ev);
   if (c->copy_stream) hipStreamDestroy(c->copy_stream);
   for (auto& E : c->ex) {
+    if (E.packed) hipEventDestroy(E.packed);
+    if (E.done) hipEventDestroy(E.done);
+  }
+  for (auto& E : c->mx) {
     if (E.packed) hipEventDestroy(E.packed);
     if (E.done) hipEventDestroy(E.done);
   }
@@ -1341,6 +1360,22 @@ static void export_finish(brisk_hip_ctx* ctx, brisk_hip_ctx::ExportSlot& E) {
   }
 }
 
+// The stream of a transfer to the host.  A context that runs detect + describe batches already owns a second stream - `side`, where the integral
+// kernel runs beside the detector's tail - and the transfer goes there: a process gets 4 hardware queues by default, and with the
+// caller's own stream, the context's main, side and copy streams a FIFTH active stream shares a queue with one of them (measured:
+// host-to-host 26.3 k -> 21.1 k frames/s after batches on a caller's stream).  Behind the transfer the next batch's integral kernel
+// starts up to half a millisecond late, inside its window beside the tie chain.  Contexts without a side stream get an egress stream.
+static int egress_stream(brisk_hip_ctx* ctx, hipStream_t* out) {
+  static const bool own_egress = tuning_env("BRISK_EXPORT_OWN_STREAM") && atoi(tuning_env("BRISK_EXPORT_OWN_STREAM")) == 1;  // A / B runs
+  hipStream_t es = (ctx->side && !own_egress) ? ctx->side : ctx->egress;
+  if (!es) {
+    HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->egress, hipStreamNonBlocking));
+    es = ctx->egress;
+  }
+  *out = es;
+  return BRISK_HIP_OK;
+}
+
 static int download_all_locked(brisk_hip_ctx* ctx, int which, const brisk_hip_batch_host_results* dst, hipStream_t s, unsigned* ticket,
                                bool known_pinned = false /* the arrays come from hipHostMalloc (the pool's own): no pointer queries */,
                                bool egress_on_s = false /* the transfer on the batch's own stream (the pool: its contexts run one group at a time) */) {
@@ -1360,17 +1395,9 @@ static int download_all_locked(brisk_hip_ctx* ctx, int which, const brisk_hip_ba
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const int dstride = want_desc ? dst->desc_stride : 4;
   brisk_hip_ctx::ExportSlot& E = ctx->ex[(ctx->ex_seq + 1) & 1];
-  // The transfer's stream.  A context that runs detect + describe batches already owns a second stream - `side`, where the integral
-  // kernel runs beside the detector's tail - and the transfer goes there: a process gets 4 hardware queues by default, and with the
-  // caller's own stream, the context's main, side and copy streams a FIFTH active stream shares a queue with one of them (measured:
-  // host-to-host 26.3 k -> 21.1 k frames/s after batches on a caller's stream).  Behind the transfer the next batch's integral kernel
-  // starts up to half a millisecond late, inside its window beside the tie chain.  Contexts without a side stream get an egress stream.
-  static const bool own_egress = tuning_env("BRISK_EXPORT_OWN_STREAM") && atoi(tuning_env("BRISK_EXPORT_OWN_STREAM")) == 1;  // A / B runs
-  hipStream_t es = egress_on_s ? s : ((ctx->side && !own_egress) ? ctx->side : ctx->egress);
-  if (!es) {
-    HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->egress, hipStreamNonBlocking));
-    es = ctx->egress;
-  }
+  hipStream_t es = s;
+  if (!egress_on_s)
+    if (int rc = egress_stream(ctx, &es)) return rc;
   if (!E.packed) {
     HIPCHK(ctx, hipEventCreateWithFlags(&E.packed, hipEventDisableTiming));
     HIPCHK(ctx, hipEventCreateWithFlags(&E.done, hipEventDisableTiming));
@@ -1442,15 +1469,18 @@ int brisk_hip_batch_download_all(brisk_hip_ctx* ctx, int which, const brisk_hip_
   return download_all_locked(ctx, which, dst, stream ? (hipStream_t)stream : ctx->stream, ticket);
 }
 
-int brisk_hip_batch_download_wait(brisk_hip_ctx* ctx, unsigned ticket, int* frames_flagged) {
-  if (!ctx) return BRISK_HIP_ERR_ARG;
-  std::unique_lock<std::mutex> lk(ctx->mu);
-  if (frames_flagged) *frames_flagged = 0;
+// Completes the transfers of `slots` up to `ticket`, oldest first, and reports `ticket`'s outcome (brisk_hip_batch_download_wait and
+// brisk_hip_pair_matches_wait: ctx->mu held through `lk`, released while the host waits for the device).  finish(slot): the slot's
+// egress kernel is done.  name: the head of the messages.
+extern "C++" {
+template <class Slot, class Finish>
+static int wait_transfers(brisk_hip_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot (&slots)[2], unsigned ticket, int* flagged, Finish finish,
+                          const char* name) {
+  if (flagged) *flagged = 0;
   if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BRISK_HIP_ERR_HIP, "hipSetDevice failed");
-  // the transfers up to `ticket`, oldest first; the lock is released while the host waits for the device
   for (int pass = 0; pass < 2; ++pass) {
-    brisk_hip_ctx::ExportSlot* E = nullptr;
-    for (auto& X : ctx->ex)
+    Slot* E = nullptr;
+    for (auto& X : slots)
       if (X.pending && (int)(X.ticket - ticket) <= 0 && (!E || (int)(X.ticket - E->ticket) < 0)) E = &X;
     if (!E) break;
     const unsigned t = E->ticket;
@@ -1459,18 +1489,26 @@ int brisk_hip_batch_download_wait(brisk_hip_ctx* ctx, unsigned ticket, int* fram
     const hipError_t e = hipEventSynchronize(ev);
     lk.lock();
     if (e != hipSuccess) {
-      ctx->err = std::string("brisk_hip_batch_download_wait: ") + hipGetErrorString(e);
+      ctx->err = std::string(name) + ": " + hipGetErrorString(e);
       return BRISK_HIP_ERR_HIP;
     }
-    if (E->pending && E->ticket == t) export_finish(ctx, *E);  // (unless another thread completed it meanwhile)
+    if (E->pending && E->ticket == t) finish(*E);  // (unless another thread completed it meanwhile)
   }
-  for (auto& X : ctx->ex)
+  for (auto& X : slots)
     if (X.ticket == ticket && ticket != 0 && !X.pending) {
-      if (frames_flagged) *frames_flagged = X.flagged;
+      if (flagged) *flagged = X.flagged;
       if (X.rc) ctx->err = X.msg;
       return X.rc;
     }
-  return fail(ctx, BRISK_HIP_ERR_ARG, "download_wait: unknown ticket (never issued on this context, or two later transfers have replaced it)");
+  return fail(ctx, BRISK_HIP_ERR_ARG, (std::string(name) + ": unknown ticket (never issued on this context, or two later transfers have replaced it)").c_str());
+}
+}
+
+int brisk_hip_batch_download_wait(brisk_hip_ctx* ctx, unsigned ticket, int* frames_flagged) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::unique_lock<std::mutex> lk(ctx->mu);
+  return wait_transfers(ctx, lk, ctx->ex, ticket, frames_flagged, [&](brisk_hip_ctx::ExportSlot& E) { export_finish(ctx, E); },
+                        "brisk_hip_batch_download_wait");
 }
 
 int brisk_hip_detect_describe_batch_host_results(brisk_hip_ctx* ctx, const brisk_hip_pattern* pat, const uint8_t* h_frames,
@@ -2144,6 +2182,196 @@ int brisk_hip_match_radius_pairs_gated_device(brisk_hip_ctx* ctx, const brisk_hi
   std::lock_guard<std::mutex> lock(ctx->mu);
   return match_radius_pairs_call({ctx, "match_radius_pairs", query, train, pairs, dim_bytes, true, query_kps, train_kps, gate}, max_distance,
                                  cap_per_query, rows_cap, d_out, d_out_count, d_pair_rows, stream);
+}
+
+// ---- the pair matchers' exit: selected matches, packed (kernels: brisk_match_export.hip) -----------------------------------------
+static_assert(BRISK_PAIR_ROWS_CUT == BRISK_HIP_PAIR_ROWS_CUT && BRISK_PAIR_BAD == BRISK_HIP_PAIR_BAD &&
+              BRISK_PAIR_ENTRIES_CUT == BRISK_HIP_PAIR_ENTRIES_CUT && BRISK_PAIR_MATCHES_CUT == BRISK_HIP_ROWS_CUT, "pair flags");
+static_assert(sizeof(brisk_hip_match_select) == 12 && sizeof(brisk_hip_dmatch) == 16 && sizeof(BriskDMatch) == 16, "select / cv::DMatch layout");
+
+// what the device and the host form check alike, before anything is launched (the output arrays are the forms' own)
+static const char* select_check(const brisk_hip_dmatch* d_out, const int* d_out_count, const int* d_pair_rows, int npairs, int rows_cap,
+                                int per_row, const brisk_hip_match_select* sel, long long matches_cap) {
+  if (npairs < 0 || rows_cap < 1 || per_row < 1 || matches_cap < 0) return "select_pair_matches: npairs / matches_cap negative, or rows_cap / per_row below 1";
+  if (!sel || sel->keep_per_row < 1) return "select_pair_matches: null select, or keep_per_row below 1";
+  if (sel->ratio > 0.0f && per_row < 2) return "select_pair_matches: the ratio test needs rows of two entries (per_row >= 2)";
+  if (npairs > 0 && (!d_out || !d_out_count || !d_pair_rows)) return "select_pair_matches: null match arrays";
+  if (((uintptr_t)d_out & 15) || (((uintptr_t)d_out_count | (uintptr_t)d_pair_rows) & 3)) return "select_pair_matches: d_out must be 16-byte aligned, the counts 4-byte";
+  return nullptr;
+}
+
+// the three selection kernels on `st` (npairs > 0, arguments checked; the workspace is held by the caller): the context's scratch
+// grows to the call's size first
+static int select_launch(brisk_hip_ctx* ctx, const brisk_hip_dmatch* d_out, const int* d_out_count, const int* d_pair_rows, int npairs,
+                         int rows_cap, int per_row, const brisk_hip_match_select* sel, long long matches_cap, int* counts, int* flags,
+                         long long* offsets, brisk_hip_dmatch* matches, int* rows_copy, hipStream_t st) {
+  const size_t nblk = (size_t)npairs * (size_t)brisk_match_export_blocks_per_pair(rows_cap);
+  if (ctx->d_select.cap < nblk * 12) {
+    HIPCHK(ctx, wait_own_work(ctx));  // (every user of the scratch is a workspace call)
+    HIPCHK(ctx, ctx->d_select.grow(nblk * 12));
+  }
+  long long* blk = ctx->d_select.as<long long>();
+  const BriskMatchSelect S{sel->max_distance, sel->ratio, sel->keep_per_row};
+  brisk_launch_pair_select(reinterpret_cast<const BriskDMatch*>(d_out), d_out_count, d_pair_rows, npairs, rows_cap, per_row, S, blk,
+                           reinterpret_cast<int*>(blk + nblk), matches_cap, counts, flags, offsets, reinterpret_cast<BriskDMatch*>(matches),
+                           rows_copy, st);
+  HIPCHK(ctx, hipGetLastError());
+  return BRISK_HIP_OK;
+}
+
+int brisk_hip_select_pair_matches_device(brisk_hip_ctx* ctx, const brisk_hip_dmatch* d_out, const int* d_out_count, const int* d_pair_rows,
+                                         int npairs, int rows_cap, int per_row, const brisk_hip_match_select* select, long long matches_cap,
+                                         int* d_counts, int* d_flags, long long* d_offsets, brisk_hip_dmatch* d_matches, void* stream) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (const char* msg = select_check(d_out, d_out_count, d_pair_rows, npairs, rows_cap, per_row, select, matches_cap))
+    return fail(ctx, BRISK_HIP_ERR_ARG, msg);
+  if (npairs > 0 && (!d_counts || !d_flags || !d_offsets || (matches_cap > 0 && !d_matches)))
+    return fail(ctx, BRISK_HIP_ERR_ARG, "select_pair_matches: null output array");
+  if ((((uintptr_t)d_counts | (uintptr_t)d_flags) & 3) || ((uintptr_t)d_offsets & 7) || ((uintptr_t)d_matches & 15))
+    return fail(ctx, BRISK_HIP_ERR_ARG, "select_pair_matches: d_matches must be 16-byte aligned, d_offsets 8-byte, counts and flags 4-byte");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  if (npairs == 0) {
+    if (d_offsets) HIPCHK(ctx, hipMemsetAsync(d_offsets, 0, sizeof(long long), st));
+    return BRISK_HIP_OK;
+  }
+  // the context's scratch is written: the stream is ordered behind the previous call's work, the next call behind this one
+  if (workspace_acquire(ctx, st)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
+  WorkspaceGuard guard(ctx, st);
+  if (int rc = select_launch(ctx, d_out, d_out_count, d_pair_rows, npairs, rows_cap, per_row, select, matches_cap, d_counts, d_flags, d_offsets,
+                             d_matches, nullptr, st))
+    return rc;
+  if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
+  return BRISK_HIP_OK;
+}
+
+// byte offsets of the five arrays inside a slab / bounce buffer holding `pairs` pairs and `matches` records
+struct MatchLayout {
+  size_t rows, counts, flags, offsets, matches, bytes;
+  MatchLayout(int pairs, long long nmatches) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    rows = 0;
+    counts = up(rows + sizeof(int) * (size_t)pairs);
+    flags = up(counts + sizeof(int) * (size_t)pairs);
+    offsets = up(flags + sizeof(int) * (size_t)pairs);
+    matches = up(offsets + sizeof(long long) * ((size_t)pairs + 1));
+    bytes = up(matches + sizeof(brisk_hip_dmatch) * (size_t)nmatches) + 256;
+  }
+  brisk_hip_pair_host_matches at(uint8_t* base, int pairs, long long nmatches) const {
+    return brisk_hip_pair_host_matches{pairs, nmatches, reinterpret_cast<int*>(base + rows), reinterpret_cast<int*>(base + counts),
+                                       reinterpret_cast<int*>(base + flags), reinterpret_cast<long long*>(base + offsets),
+                                       reinterpret_cast<brisk_hip_dmatch*>(base + matches)};
+  }
+};
+
+// the egress kernel of slot E has finished (ctx->mu held): status of the transfer, and - for a pageable destination - the copy
+// out of the bounce buffer
+static void matches_finish(brisk_hip_ctx::MatchSlot& E) {
+  const brisk_hip_pair_host_matches& W = E.wr;
+  int flagged = 0, cut = 0;
+  for (int p = 0; p < E.npairs; ++p)
+    if (W.flags[p]) { ++flagged; cut += (W.flags[p] & BRISK_HIP_ROWS_CUT) != 0; }
+  if (E.use_bounce) {
+    const long long n = W.offsets[E.npairs];
+    memcpy(E.dst.pair_rows, W.pair_rows, sizeof(int) * (size_t)E.npairs);
+    memcpy(E.dst.counts, W.counts, sizeof(int) * (size_t)E.npairs);
+    memcpy(E.dst.flags, W.flags, sizeof(int) * (size_t)E.npairs);
+    memcpy(E.dst.offsets, W.offsets, sizeof(long long) * ((size_t)E.npairs + 1));
+    if (n > 0) memcpy(E.dst.matches, W.matches, sizeof(brisk_hip_dmatch) * (size_t)n);
+  }
+  E.pending = false;
+  E.flagged = flagged;
+  E.rc = BRISK_HIP_OK;
+  E.msg.clear();
+  if (cut) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "%d pair(s) did not fit the destination's matches_cap (flags[p] & BRISK_HIP_ROWS_CUT); their counts are reported", cut);
+    E.rc = BRISK_HIP_ERR_CAPACITY;
+    E.msg = msg;
+  }
+}
+
+int brisk_hip_pair_matches_download(brisk_hip_ctx* ctx, const brisk_hip_dmatch* d_out, const int* d_out_count, const int* d_pair_rows,
+                                    int npairs, int rows_cap, int per_row, const brisk_hip_match_select* select,
+                                    const brisk_hip_pair_host_matches* dst, void* stream, unsigned* ticket) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (!dst || !ticket) return fail(ctx, BRISK_HIP_ERR_ARG, "pair_matches_download: null destination / ticket");
+  *ticket = 0;
+  if (const char* msg = select_check(d_out, d_out_count, d_pair_rows, npairs, rows_cap, per_row, select, dst->matches_cap))
+    return fail(ctx, BRISK_HIP_ERR_ARG, msg);
+  if (dst->pairs_cap < npairs || !dst->offsets || (npairs > 0 && (!dst->pair_rows || !dst->counts || !dst->flags)) ||
+      (dst->matches_cap > 0 && !dst->matches))
+    return fail(ctx, BRISK_HIP_ERR_ARG, "pair_matches_download: pairs_cap below npairs, or a null pair_rows / counts / flags / offsets / matches array");
+  if ((((uintptr_t)dst->pair_rows | (uintptr_t)dst->counts | (uintptr_t)dst->flags | (uintptr_t)dst->matches) & 3) || ((uintptr_t)dst->offsets & 7))
+    return fail(ctx, BRISK_HIP_ERR_ARG, "pair_matches_download: destination arrays must be 4-byte aligned (offsets: 8)");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream, es = nullptr;
+  if (int rc = egress_stream(ctx, &es)) return rc;
+  brisk_hip_ctx::MatchSlot& E = ctx->mx[(ctx->mx_seq + 1) & 1];
+  if (!E.packed) {
+    HIPCHK(ctx, hipEventCreateWithFlags(&E.packed, hipEventDisableTiming));
+    HIPCHK(ctx, hipEventCreateWithFlags(&E.done, hipEventDisableTiming));
+  }
+  if (E.pending) {  // a third transfer in flight: complete the oldest first
+    HIPCHK(ctx, hipEventSynchronize(E.done));
+    matches_finish(E);
+  }
+  const int pairs = npairs > 0 ? npairs : 1;
+  const MatchLayout LY(pairs, dst->matches_cap);
+  if (LY.bytes > E.slab.cap) {
+    if (E.done_valid) HIPCHK(ctx, hipEventSynchronize(E.done));
+    HIPCHK(ctx, E.slab.grow(LY.bytes));
+  }
+  // where the egress kernel writes: the caller's arrays when the device can reach all of them, else the bounce buffer
+  void* dv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  const bool direct = (npairs == 0 || (device_can_write(dst->pair_rows, &dv[0]) && device_can_write(dst->counts, &dv[1]) &&
+                                       device_can_write(dst->flags, &dv[2]))) &&
+                      device_can_write(dst->offsets, &dv[3]) && (dst->matches_cap == 0 || device_can_write(dst->matches, &dv[4]));
+  brisk_hip_pair_host_matches W = *dst, H = *dst;  // W: device-side addresses for the kernel, H: what the host reads at the wait
+  if (direct) {
+    W.pair_rows = static_cast<int*>(dv[0]); W.counts = static_cast<int*>(dv[1]); W.flags = static_cast<int*>(dv[2]);
+    W.offsets = static_cast<long long*>(dv[3]); W.matches = static_cast<brisk_hip_dmatch*>(dv[4]);
+  } else {
+    HIPCHK(ctx, E.bounce.grow(LY.bytes));
+    W = H = LY.at(E.bounce.as<uint8_t>(), pairs, dst->matches_cap);
+  }
+  const brisk_hip_pair_host_matches S = LY.at(E.slab.as<uint8_t>(), pairs, dst->matches_cap);
+  if (workspace_acquire(ctx, s)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
+  WorkspaceGuard guard(ctx, s);
+  if (E.done_valid) HIPCHK(ctx, hipStreamWaitEvent(s, E.done, 0));  // the slab's previous transfer
+  if (npairs > 0) {
+    if (int rc = select_launch(ctx, d_out, d_out_count, d_pair_rows, npairs, rows_cap, per_row, select, dst->matches_cap, S.counts, S.flags,
+                               S.offsets, S.matches, S.pair_rows, s))
+      return rc;
+  } else {
+    HIPCHK(ctx, hipMemsetAsync(S.offsets, 0, sizeof(long long), s));
+  }
+  HIPCHK(ctx, hipEventRecord(E.packed, s));
+  if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
+  HIPCHK(ctx, hipStreamWaitEvent(es, E.packed, 0));
+  brisk_launch_pair_select_egress(S.pair_rows, S.counts, S.flags, S.offsets, reinterpret_cast<const BriskDMatch*>(S.matches), npairs, W.pair_rows,
+                                  W.counts, W.flags, W.offsets, W.matches, es);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipEventRecord(E.done, es));
+  E.done_valid = true;
+  E.pending = true;
+  E.use_bounce = !direct;
+  E.npairs = npairs;
+  E.dst = *dst;
+  E.wr = H;
+  E.ticket = ++ctx->mx_seq;
+  if (!E.ticket) E.ticket = ++ctx->mx_seq;  // (0 is never a ticket)
+  *ticket = E.ticket;
+  return BRISK_HIP_OK;
+}
+
+int brisk_hip_pair_matches_wait(brisk_hip_ctx* ctx, unsigned ticket, int* pairs_flagged) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::unique_lock<std::mutex> lk(ctx->mu);
+  return wait_transfers(ctx, lk, ctx->mx, ticket, pairs_flagged, [](brisk_hip_ctx::MatchSlot& E) { matches_finish(E); },
+                        "brisk_hip_pair_matches_wait");
 }
 
 int brisk_hip_match_radius_device(brisk_hip_ctx* ctx, const uint8_t* d_query, int nq, int q_pitch, const uint8_t* d_train, int nt,

@@ -14,6 +14,7 @@
 
 #include "brisk_common.h"
 #include "brisk_kernels.h"
+#include "brisk_export_copy.h"
 
 #define EX_THREADS 1024
 
@@ -91,19 +92,6 @@ __global__ void __launch_bounds__(256) k_export_rows(const BriskKeyPoint* __rest
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n * ddw; i += gridDim.x * blockDim.x) {
     const int row = i / ddw, c = i - row * ddw;
     dst_d[i] = c < sdw ? *reinterpret_cast<const uint32_t*>(src_d + (long)row * dev_pitch + 4 * c) : 0u;
-  }
-}
-
-// dwords [0, n) of src (16-byte aligned) -> dst (host memory, 4-byte aligned): 16-byte stores where dst allows them
-__device__ __forceinline__ void ex_copy_words(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, long long n, long gt, long gn) {
-  if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-    const long long nv = n >> 2;
-    const uint4* s4 = reinterpret_cast<const uint4*>(src);
-    uint4* d4 = reinterpret_cast<uint4*>(dst);
-    for (long long i = gt; i < nv; i += gn) d4[i] = s4[i];
-    for (long long i = (nv << 2) + gt; i < n; i += gn) dst[i] = src[i];
-  } else {
-    for (long long i = gt; i < n; i += gn) dst[i] = src[i];
   }
 }
 

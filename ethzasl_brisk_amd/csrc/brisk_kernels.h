@@ -4,6 +4,7 @@
 
 #include "brisk_common.h"
 #include "brisk_match_gate.h"
+#include "brisk_match_select.h"
 
 #define BRISK_DETECT_TILE_W 64
 #ifndef BRISK_DETECT_ROWS_PER_THREAD
@@ -185,6 +186,21 @@ bool brisk_launch_match_knn_pairs_gated(const BriskDescSet& Q, const BriskDescSe
 bool brisk_launch_match_radius_pairs_gated(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
                                            const BriskMatchGate& gate, const BriskPairSpec& P, int words32, float max_distance, int cap,
                                            int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s);
+
+// ---- the pair matchers' exit: selected matches, packed (brisk_match_export.hip; the rule: brisk_match_select.h) ----
+// flags of a pair (mirror BRISK_HIP_PAIR_* / BRISK_HIP_ROWS_CUT of brisk_hip.h)
+enum { BRISK_PAIR_ROWS_CUT = 1, BRISK_PAIR_BAD = 2, BRISK_PAIR_ENTRIES_CUT = 4, BRISK_PAIR_MATCHES_CUT = 0x100 };
+int brisk_match_export_blocks_per_pair(int rows_cap);
+// out / out_count / pair_rows: what a pair matcher wrote.  blk [npairs * blocks_per_pair] long long and blk_over (ints, as many):
+// scratch.  counts / flags [npairs], offsets [npairs + 1], matches [matches_cap] (16-byte aligned, like out); rows_copy: NULL or
+// [npairs], a copy of pair_rows
+void brisk_launch_pair_select(const BriskDMatch* out, const int* out_count, const int* pair_rows, int npairs, int rows_cap, int per_row,
+                              const BriskMatchSelect& sel, long long* blk, int* blk_over, long long matches_cap, int* counts, int* flags,
+                              long long* offsets, BriskDMatch* matches, int* rows_copy, hipStream_t s);
+// packed results -> host memory the device can write: the stored matches only
+void brisk_launch_pair_select_egress(const int* s_rows, const int* s_counts, const int* s_flags, const long long* s_offsets,
+                                     const BriskDMatch* s_matches, int npairs, int* h_rows, int* h_counts, int* h_flags, long long* h_offsets,
+                                     void* h_matches, hipStream_t s);
 
 // ---- uniformity enforcement / keypoint bucketing (brisk_uniformity.hip): optional post-filters of the detector's keypoints ----
 void brisk_launch_bucketing(BriskKeyPoint* kp, BriskFrameCounters* counters, int* order, BriskKeyPoint* tmp, int kp_cap, int rows,

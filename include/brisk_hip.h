@@ -507,6 +507,74 @@ int brisk_hip_match_radius_pairs_gated_device(brisk_hip_ctx* ctx, const brisk_hi
                                               float max_distance, int cap_per_query, int rows_cap, brisk_hip_dmatch* d_out,
                                               int* d_out_count, int* d_pair_rows, void* stream);
 
+/* ---- the pair matchers' exit: selected matches, packed, on the device or in HOST memory ------------------------------------
+ * The four pair matchers leave padded arrays in HBM (d_out [npairs][rows_cap][per_row], d_out_count, d_pair_rows; per_row = the
+ * call's k or cap_per_query).  What every consumer does first - a distance bound, Lowe's ratio test on k = 2 rows, a limit of
+ * entries per row - is applied on the device, and the selected records are packed in (pair, query row, rank) order: exact
+ * prefix sums, no padding, the order deterministic (stable compaction, no atomics).
+ * The rule (csrc/brisk_match_select.h is its one definition).  Row (p, q) has c = d_out_count[p][q] and the stored entries
+ * e[0 .. min(c, per_row)), in (distance, trainIdx) order.
+ *   An entry passes iff e.distance < max_distance (strict fp32 compare; +INFINITY = no bound, NaN keeps nothing) and it is no
+ *   top-up entry.  DEVIATION FROM THE REFERENCE, on purpose, the one the gated matchers make: the entry brisk_hip_match_knn's
+ *   rows are topped up with when 0 < n_b < k (distance 2147483648.f, brute-force-matcher.cc:139-153) is never selected.
+ *   ratio > 0: the row gives at most e[0] - iff e[0] passes and (the row has one stored entry, or e[1] is a top-up entry, or
+ *     e[0].distance < ratio * e[1].distance: one fp32 multiplication, one fp32 compare, no contraction).  An ungated row with
+ *     n_b == 1 and a gated row with one allowed train row therefore behave the same.  Needs per_row >= 2.
+ *   ratio <= 0 or NaN (off): the leading min(stored, keep_per_row) entries that pass (a prefix: rows are sorted by distance).
+ *   Rows q >= min(d_pair_rows[p], rows_cap) are never read; a pair with d_pair_rows[p] < 0 gives nothing. */
+typedef struct brisk_hip_match_select {
+  float max_distance; /* entry kept iff distance < max_distance */
+  float ratio;        /* > 0: the ratio test; <= 0 or NaN: off */
+  int keep_per_row;   /* at most this many leading entries of a row; >= 1 */
+} brisk_hip_match_select;
+/* flags of a pair (0 = clean); BRISK_HIP_ROWS_CUT is the fourth */
+#define BRISK_HIP_PAIR_ROWS_CUT 0x1    /* d_pair_rows[p] > rows_cap: the matcher cut the pair's query rows; the matched rows are stored */
+#define BRISK_HIP_PAIR_BAD 0x2         /* d_pair_rows[p] == -1 (an entry of d_pairs outside its set): nothing is stored */
+#define BRISK_HIP_PAIR_ENTRIES_CUT 0x4 /* some row had count > per_row (a radius row cut by cap_per_query): what was stored is used */
+/* d_out / d_out_count / d_pair_rows: what one of the four pair matchers wrote with this npairs, rows_cap and per_row.  Outputs, all
+ * in caller-provided DEVICE memory:
+ *   d_counts  [npairs]      matches selected for pair p
+ *   d_flags   [npairs]      the bits above; BRISK_HIP_ROWS_CUT = this pair and every pair behind it did not fit matches_cap: their
+ *                           counts are still reported, nothing of them is stored, their offsets stay at the total
+ *   d_offsets [npairs + 1]  exclusive prefix sums of the stored counts; d_offsets[npairs] = matches stored
+ *   d_matches [matches_cap] the selected records, byte-identical to the source records; nothing behind d_offsets[npairs] is written
+ * d_out and d_matches 16-byte aligned, d_offsets 8-byte.  Asynchronous on `stream` (hipStream_t, NULL = the context's stream), no
+ * allocation per call once the context's scratch has grown to the call's size (npairs x ceil(rows_cap / 256) sums).
+ * BRISK_HIP_ERR_ARG, before anything is launched: npairs < 0, rows_cap < 1, per_row < 1, matches_cap < 0, keep_per_row < 1, a NULL
+ * select, the ratio test with per_row < 2, and - with npairs > 0 - a NULL or misaligned array (d_matches may be NULL when
+ * matches_cap == 0).  npairs == 0: BRISK_HIP_OK, d_offsets[0] = 0 (d_offsets NULL is then allowed too). */
+int brisk_hip_select_pair_matches_device(brisk_hip_ctx* ctx, const brisk_hip_dmatch* d_out, const int* d_out_count, const int* d_pair_rows,
+                                         int npairs, int rows_cap, int per_row, const brisk_hip_match_select* select, long long matches_cap,
+                                         int* d_counts, int* d_flags, long long* d_offsets, brisk_hip_dmatch* d_matches, void* stream);
+/* The same into HOST memory, the way brisk_hip_batch_download_all delivers keypoints and descriptors.  The caller fills in the
+ * capacities and the five destination pointers (4-byte aligned, offsets 8):
+ *   pair_rows [pairs]  d_pair_rows    counts [pairs]  flags [pairs]  offsets [pairs + 1]  as above    matches [matches_cap] */
+typedef struct brisk_hip_pair_host_matches {
+  int pairs_cap;         /* pairs the arrays hold: >= npairs */
+  long long matches_cap; /* records `matches` holds */
+  int* pair_rows;
+  int* counts;
+  int* flags;
+  long long* offsets;
+  brisk_hip_dmatch* matches;
+} brisk_hip_pair_host_matches;
+/* Queues selection + transfer and returns: the three kernels of brisk_hip_select_pair_matches_device run on `stream` (the stream
+ * the matcher ran on; NULL = the context's) into a slab the context owns - d_out / d_out_count / d_pair_rows may be overwritten
+ * by the next batch in stream order -, the transfer of the exact bytes runs on the context's second stream beside whatever the
+ * context does next.  Pinned / registered destinations are written by the device directly; pageable ones go through a pinned
+ * buffer of the context and a host copy inside brisk_hip_pair_matches_wait.  *ticket names the transfer.  Two transfers of
+ * matches are in flight per context at most - slots of their own, beside the two of brisk_hip_batch_download_all: a stream that
+ * downloads rows AND matches of every batch keeps two batches in flight -, a third call first completes the oldest.  `dst`
+ * (the struct) is copied; its arrays must stay valid until the ticket has been waited for.  Errors as the device form's, and
+ * BRISK_HIP_ERR_ARG for pairs_cap < npairs or a NULL ticket / destination array. */
+int brisk_hip_pair_matches_download(brisk_hip_ctx* ctx, const brisk_hip_dmatch* d_out, const int* d_out_count, const int* d_pair_rows,
+                                    int npairs, int rows_cap, int per_row, const brisk_hip_match_select* select,
+                                    const brisk_hip_pair_host_matches* dst, void* stream, unsigned* ticket);
+/* Blocks until transfer `ticket` (and every earlier one of matches) is complete; the context's lock is not held while waiting.
+ * *pairs_flagged (may be NULL) = pairs whose flags[] entry is non-zero.  BRISK_HIP_OK, or - with every clean pair in place -
+ * BRISK_HIP_ERR_CAPACITY when a pair carries BRISK_HIP_ROWS_CUT (the other flags are information, not errors). */
+int brisk_hip_pair_matches_wait(brisk_hip_ctx* ctx, unsigned ticket, int* pairs_flagged);
+
 /* ---- per-stage timing: HIP events recorded on the launch stream around every kernel of the batch path ---- */
 int brisk_hip_profile_enable(brisk_hip_ctx* ctx, int enable);       /* resets the accumulated calls */
 int brisk_hip_profile_stages(void);                                 /* number of stages */

@@ -25,6 +25,13 @@ With --gate dx_min,dx_max,dy_min,dy_max[,octaves] (with and without --radius) fi
 plus, computed on the host from the downloaded keypoints: the share of (64-query wave, train row) steps in which no lane is
 allowed (the steps the gated kernels skip), the share of query rows with no allowed row, the mask density, and whether G's rows
 equal C's (k-NN: C's rows without the reference's top-up entries of distance 2147483648, which the gated call never writes).
+With --export (k-NN only, profiles/match_pairs_export.json) the cost of getting the matches to the HOST, three windows:
+  B  detect_describe_batch + match_knn_pairs on the same stream: the matches stay in HBM
+  E  B + pair_matches_download (brisk_hip_pair_matches_download: ratio test 0.8, best match per row) into pinned memory, two
+     destinations alternating, a ticket waited for two batches later
+  D  B + a plain asynchronous device-to-host copy of the three padded arrays (at --rows-cap) on a copy stream, two device triples
+     and two pinned destinations alternating - what a caller could do without the packed exit
+plus the bytes E and D move per batch and the share of query rows whose match is selected.
 Usage: python tools/bench_match_pairs.py [--repeats 5] [--window 0.4] [--rows-cap 2048] [--radius R [--cap N]] [--gate ...] [--out FILE]
        --stats-pass: warm-up + a few B iterations (with --gate: B, G and I) only, nothing written (the run a
        `rocprofv3 --kernel-trace --stats` pass wraps; its kernel statistics are kept as profiles/match_pairs_kernel_stats.csv)"""
@@ -59,6 +66,120 @@ class DeviceInts:
         self.__cuda_array_interface__ = {"shape": (n,), "typestr": "<i4", "data": (ptr, False), "version": 2}
 
 
+def export_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, batch, run_b):
+    """--export: windows B, E, D (see the module's text); writes a.out"""
+    st = work.cuda_stream
+    select = B.MatchSelect(float("inf"), 0.8, 1)
+    dst = [B.HostMatches(n - 1, (n - 1) * cap, pinned=True) for _ in range(2)]        # (one match per row at the most)
+    tickets = []
+
+    def run_e():
+        run_b()
+        if len(tickets) >= 2:                                      # the destination about to be reused: its ticket from two batches ago
+            ctx.pair_matches_wait(tickets[-2])
+        tickets.append(ctx.pair_matches_download(outs["B"], k, select, dst[len(tickets) % 2], stream=st))
+
+    def drain_e():
+        for t in tickets[-2:]:
+            ctx.pair_matches_wait(t)
+        del tickets[:]
+
+    copy = torch.cuda.Stream(device=dev)
+    triples = [outs["B"], outs["C"]]
+    pinned = [tuple(torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in outs["B"]) for _ in range(2)]
+    copied = [torch.cuda.Event(), torch.cuda.Event()]
+    calls_d = [0]
+
+    def run_d():
+        i = calls_d[0] % 2
+        calls_d[0] += 1
+        work.wait_event(copied[i])                                 # this triple's copy of two batches ago
+        copied[i].synchronize()                                    # ... and the host is done with its destination (as E's wait)
+        batch()
+        dset, dim = ctx.batch_desc_set()
+        ctx.match_knn_pairs(dset, dset, B.PairSpec(n - 1, 1, 1, 0, 1, None), k, rows_cap=cap, stream=st, dim_bytes=dim, out=triples[i])
+        copy.wait_stream(work)
+        with torch.cuda.stream(copy):
+            for h, t in zip(pinned[i], triples[i]):
+                h.copy_(t, non_blocking=True)
+            copied[i].record(copy)
+
+    for ev in copied:
+        ev.record(work)
+    runs = {"B": run_b, "E": run_e, "D": run_d}
+    ends = {"B": lambda: None, "E": drain_e, "D": lambda: None}
+    order = "BED"
+    for v in order + "BE":                                         # warm-up: buffers sized, slabs grown
+        runs[v]()
+        ends[v]()
+        torch.cuda.synchronize()
+
+    # what E delivers, checked against the padded arrays D copied (the same batch content in every call)
+    run_e()
+    drain_e()
+    run_d()
+    torch.cuda.synchronize()
+    m, cnt, rows = (h.numpy() for h in pinned[(calls_d[0] - 1) % 2])
+    m = m.view(B.DMATCH).reshape(n - 1, cap, k)
+    d0, d1 = m[:, :, 0]["distance"], m[:, :, k - 1]["distance"]
+    valid = (np.arange(cap)[None, :] < np.minimum(rows, cap)[:, None]) & (cnt >= 1)
+    top = np.float32(2147483648.0)
+    keep = valid & (d0 != top) & ((cnt == 1) | (d1 == top) | (d0 < np.float32(0.8) * d1)) if k >= 2 else valid & (d0 != top)
+    got = [d for d in dst if int(d.offsets[n - 1]) == int(keep.sum())]
+    identical = bool(got) and got[0].matches[:int(keep.sum())].tobytes() == m[:, :, 0][keep].tobytes()
+    selected = int(keep.sum())
+    bytes_e = 4 * 3 * (n - 1) + 8 * n + 16 * selected
+    bytes_d = sum(t.numel() * t.element_size() for t in outs["B"])
+
+    fps = {v: [] for v in order}
+    for _ in range(a.repeats):
+        for v in order:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            calls = 0
+            while True:
+                runs[v]()
+                calls += 1
+                if time.perf_counter() - t0 >= a.window:
+                    break
+            ends[v]()
+            torch.cuda.synchronize()
+            fps[v].append(calls * n / (time.perf_counter() - t0))
+    med = {v: float(np.median(fps[v])) for v in order}
+    ms = {v: 1e3 * n / med[v] for v in order}
+    spread = {v: (max(fps[v]) - min(fps[v])) / med[v] for v in order}
+    res = {
+        "workload": "bench.py's stream: %dx%d, threshold %d, %d octaves, %d frames per batch (%d distinct) in HBM; frame-to-previous-frame, "
+                    "k = %d, rows_cap %d; E selects with ratio 0.8, one match per row" % (W, H, THRESHOLD, OCTAVES, n, nd, k, cap),
+        "kernel_revision": ctx.kernel_revision(),
+        "device": torch.cuda.get_device_name(0),
+        "windows": {"repeats": a.repeats, "seconds_each": a.window,
+                    "order": ", ".join(order) + " alternating; every window ends with its transfers complete and a synchronise"},
+        "frames_per_s": {v: round(med[v], 1) for v in order},
+        "frames_per_s_all": {v: [round(x, 1) for x in fps[v]] for v in order},
+        "spread_rel": {v: round(spread[v], 4) for v in order},
+        "ms_per_batch": {v: round(ms[v], 4) for v in order},
+        "exit_ms_per_batch": {"E_minus_B": round(ms["E"] - ms["B"], 4), "D_minus_B": round(ms["D"] - ms["B"], 4)},
+        "E_over_B_frames_per_s": round(med["E"] / med["B"], 4),
+        "E_over_D_frames_per_s": round(med["E"] / med["D"], 4),
+        "bytes_per_batch": {"E": bytes_e, "D": bytes_d},
+        "rows_with_entries": int(valid.sum()),
+        "matches_selected": selected,
+        "share_of_rows_selected": round(selected / max(int(valid.sum()), 1), 4),
+        "E_equals_rule_on_D_arrays": identical,
+        "legend": {"B": "detect_describe_batch + brisk_hip_match_knn_pairs_device on the same stream",
+                   "E": "B + brisk_hip_pair_matches_download (ratio 0.8) into pinned memory, waited for two batches later",
+                   "D": "B + asynchronous device-to-host copies of d_out, d_out_count, d_pair_rows (padded) on a copy stream"},
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+    ext.close()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=512)
@@ -73,6 +194,7 @@ def main():
     ap.add_argument("--out", default=None, help="default: profiles/match_pairs.json, with --radius profiles/match_radius_pairs.json, "
                                                 "with --gate the same names ending in _gated.json")
     ap.add_argument("--stats-pass", action="store_true")
+    ap.add_argument("--export", action="store_true", help="windows B, E (packed, selected matches to the host) and D (padded arrays to the host)")
     a = ap.parse_args()
 
     radius = a.radius
@@ -80,6 +202,11 @@ def main():
     if a.gate is not None:
         g = [float(v) for v in a.gate.split(",")]
         gate = (g[0], g[1], g[2], g[3], int(g[4]) if len(g) > 4 else -1)
+    if a.export:
+        if radius is not None or gate:
+            ap.error("--export measures the k-NN pair call: without --radius / --gate")
+        if a.out is None:
+            a.out = os.path.join(ROOT, "profiles", "match_pairs_export.json")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", ("match_radius_pairs" if radius is not None else "match_pairs") +
                              ("_gated" if gate else "") + ".json")
@@ -124,6 +251,10 @@ def main():
         else:
             ctx.match_knn_pairs(dset, dset, spec, k, rows_cap=cap, stream=st, dim_bytes=dim, out=outs[which], gate=g, query_kps=kps,
                                 train_kps=kps)
+
+    if a.export:
+        export_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, batch, run_b)
+        return
 
     vp = C.c_void_p
 
