@@ -152,9 +152,10 @@ def test_cross_check_on_the_batch(batch):
 
 class SynthSet:
     """frames of low-entropy descriptors (plenty of equal distances) in one device buffer: every byte outside the counted
-    rows is random too, so a kernel that reads a row it should not read computes something else"""
+    rows is random too, so a kernel that reads a row it should not read computes something else.  prepared: frame -> its rows
+    ([counts[f], dim] uint8) where a test builds them itself instead of taking random ones"""
 
-    def __init__(self, B, rng, dim, row_pitch, counts, cap, base_off=0, count_stride=3, frame_slack=0):
+    def __init__(self, B, rng, dim, row_pitch, counts, cap, base_off=0, count_stride=3, frame_slack=0, prepared=None):
         import torch
         self.counts, self.dim = list(counts), dim
         frames = len(counts)
@@ -162,12 +163,15 @@ class SynthSet:
         buf = (rng.integers(0, 4, base_off + frames * frame_pitch + 64, dtype=np.uint8) * 85).astype(np.uint8)
         self.desc = []
         for f, c in enumerate(counts):
-            rows = (rng.integers(0, 4, (c, dim), dtype=np.uint8) * 85).astype(np.uint8)
-            if f > 0 and c > 4 and len(self.desc[0]) > 4:
-                rows[:3] = self.desc[0][:3]                         # the same descriptors in several frames: distance 0
-            for r in range(c):
-                o = base_off + f * frame_pitch + r * row_pitch
-                buf[o:o + dim] = rows[r]
+            if prepared is not None and f in prepared:
+                rows = np.ascontiguousarray(prepared[f], np.uint8)
+                assert rows.shape == (c, dim)
+            else:
+                rows = (rng.integers(0, 4, (c, dim), dtype=np.uint8) * 85).astype(np.uint8)
+                if f > 0 and c > 4 and len(self.desc[0]) > 4:
+                    rows[:3] = self.desc[0][:3]                     # the same descriptors in several frames: distance 0
+            o = base_off + f * frame_pitch
+            np.lib.stride_tricks.as_strided(buf[o:], (c, dim), (row_pitch, 1))[...] = rows
             self.desc.append(rows)
         cnt = rng.integers(100, 1000, frames * count_stride + 1).astype(np.int32)
         cnt[0:frames * count_stride:count_stride] = counts
