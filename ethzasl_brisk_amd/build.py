@@ -35,7 +35,8 @@ def kernel_revision():
     import hashlib
     h = hashlib.sha1()
     for f in sorted(os.listdir(CSRC)):
-        if f.endswith((".hip", ".h", ".inc")) and f not in ("brisk_capi.hip", "brisk_pool.inc", "brisk_hostmem.h"):  # (host code only)
+        # (host code only: no kernel changes with these, and the committed profiles stay valid when they change)
+        if f.endswith((".hip", ".h", ".inc")) and f not in ("brisk_capi.hip", "brisk_pool.inc", "brisk_hostmem.h", "brisk_slab_layout.h", "brisk_transfer.h"):
             h.update(open(os.path.join(CSRC, f), "rb").read())
     return h.hexdigest()[:12]
 

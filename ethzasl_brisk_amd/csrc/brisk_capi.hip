@@ -23,6 +23,8 @@
 #include "brisk_pattern.h"
 #include "brisk_device_describe.h"
 #include "brisk_hostmem.h"
+#include "brisk_slab_layout.h"
+#include "brisk_transfer.h"
 
 static_assert(sizeof(brisk_hip_keypoint) == 28 && sizeof(BriskKeyPoint) == 28, "cv::KeyPoint layout");
 
@@ -135,37 +137,10 @@ struct brisk_hip_ctx {
     const uint8_t* l0_ext = nullptr;  // layer 0 was read in place from the staging buffer (width a multiple of 64)
     int hits = 0;                     // describe calls that reused the device copy (brisk_hip_debug_image_reuse)
   } img_cache;
-  // brisk_hip_batch_download_all: two slots of {device slab, pinned bounce buffer, events, the transfer in flight}
-  struct ExportSlot {
-    DeviceBuf slab;
-    PinnedBuf bounce;  // staging for destinations the device cannot write (pageable memory)
-    hipEvent_t packed = nullptr, done = nullptr;
-    bool done_valid = false;  // `done` has been recorded: the slab is in use until it fires
-    bool pending = false;     // the transfer has not been completed by a wait yet
-    bool use_bounce = false;
-    unsigned ticket = 0;
-    int nframes = 0;
-    brisk_hip_batch_host_results dst{};  // the caller's destinations
-    brisk_hip_batch_host_results wr{};   // where k_export_egress writes (the caller's arrays, or the bounce buffer)
-    int rc = BRISK_HIP_OK, flagged = 0;
-    std::string msg;
-  } ex[2];
+  // the two exits to host memory: each keeps two transfers in flight and issues its own tickets (brisk_transfer.h)
+  TransferRing<brisk_hip_batch_host_results> ex;  // brisk_hip_batch_download_all
+  TransferRing<brisk_hip_pair_host_matches> mx;   // brisk_hip_pair_matches_download
   hipStream_t egress = nullptr;
-  unsigned ex_seq = 0;
-  // brisk_hip_pair_matches_download: two slots of its own (a stream that downloads rows AND matches keeps two batches in flight)
-  struct MatchSlot {
-    DeviceBuf slab;
-    PinnedBuf bounce;
-    hipEvent_t packed = nullptr, done = nullptr;
-    bool done_valid = false, pending = false, use_bounce = false;  // as ExportSlot's
-    unsigned ticket = 0;
-    int npairs = 0;
-    brisk_hip_pair_host_matches dst{};  // the caller's destinations
-    brisk_hip_pair_host_matches wr{};   // where the egress kernel writes (the caller's arrays, or the bounce buffer)
-    int rc = BRISK_HIP_OK, flagged = 0;
-    std::string msg;
-  } mx[2];
-  unsigned mx_seq = 0;
   DeviceBuf d_select;  // brisk_hip_select_pair_matches_device / _pair_matches_download: the per-workgroup sums of the selection passes
   int last_strings = 0;  // descriptor bytes of the pattern the last describing call used
 };
@@ -514,14 +489,8 @@ void brisk_hip_destroy(brisk_hip_ctx* c) {
   }
   if (c->kin_pin_ev) hipEventDestroy(c->kin_pin_ev);
   if (c->copy_stream) hipStreamDestroy(c->copy_stream);
-  for (auto& E : c->ex) {
-    if (E.packed) hipEventDestroy(E.packed);
-    if (E.done) hipEventDestroy(E.done);
-  }
-  for (auto& E : c->mx) {
-    if (E.packed) hipEventDestroy(E.packed);
-    if (E.done) hipEventDestroy(E.done);
-  }
+  c->ex.destroy_events();
+  c->mx.destroy_events();
   if (c->egress) hipStreamDestroy(c->egress);
   brisk_prof_destroy(&c->prof);
   if (c->side) { hipStreamDestroy(c->side); hipEventDestroy(c->side_fork); hipEventDestroy(c->side_join); }
@@ -918,7 +887,6 @@ static int host_slice_frames() {
   return v;
 }
 
-static bool device_can_write(const void* p, void** dev);
 #define BRISK_STAGED_SLICE 32  // frames per pinned staging buffer of the multi-image calls
 // host threads that copy pageable images into the pinned staging buffers (the caller's thread is one of them)
 static int copy_threads() {
@@ -1294,70 +1262,49 @@ int brisk_hip_batch_download(brisk_hip_ctx* ctx, int frame, int which, brisk_hip
 }
 
 // ---- the batch path's exit to host memory (brisk_hip_batch_download_all; kernels: brisk_export.hip) ------------------
-// Can the device write to this address?  Pinned / registered host memory, managed and device memory: yes (through the
-// device-side alias the runtime reports); pageable host memory: no - the transfer then lands in the context's pinned bounce
-// buffer and brisk_hip_batch_download_wait copies it out.
-static bool device_can_write(const void* p, void** dev) {
-  hipPointerAttribute_t a;
-  memset(&a, 0, sizeof a);
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();  // (an unregistered pointer is an error on older runtimes, hipMemoryTypeUnregistered on newer ones)
-    return false;
-  }
-  if (a.type != hipMemoryTypeHost && a.type != hipMemoryTypeDevice && a.type != hipMemoryTypeManaged && a.type != hipMemoryTypeUnified)
-    return false;
-  *dev = a.devicePointer ? a.devicePointer : const_cast<void*>(p);
-  return true;
+using ExportSlot = TransferRing<brisk_hip_batch_host_results>::Slot;
+
+// the five arrays of a batch's results for `frames` frames and `rows` rows, in the order a slab, a bounce buffer and a pool
+// group's block hold them
+static SlabLayout export_layout(int frames, long long rows, int desc_stride) {
+  SlabLayout LY;
+  LY.add(sizeof(int) * (size_t)frames);              // counts
+  LY.add(sizeof(int) * (size_t)frames);              // flags
+  LY.add(sizeof(long long) * ((size_t)frames + 1));  // offsets
+  LY.add(sizeof(BriskKeyPoint) * (size_t)rows);      // kps
+  LY.add((size_t)rows * (size_t)desc_stride);        // desc
+  return LY;
+}
+static brisk_hip_batch_host_results export_at(const SlabLayout& LY, uint8_t* base, int frames, int desc_stride, long long rows) {
+  return brisk_hip_batch_host_results{frames, desc_stride, rows, LY.at<int>(base, 0), LY.at<int>(base, 1), LY.at<long long>(base, 2),
+                                      LY.at<brisk_hip_keypoint>(base, 3), LY.at<uint8_t>(base, 4)};
 }
 
-// byte offsets of the five arrays inside a slab / bounce buffer holding `frames` frames and `rows` rows
-struct ExportLayout {
-  size_t counts, flags, offsets, kps, desc, bytes;
-  ExportLayout(int frames, long long rows, int desc_stride) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    counts = 0;
-    flags = up(counts + sizeof(int) * (size_t)frames);
-    offsets = up(flags + sizeof(int) * (size_t)frames);
-    kps = up(offsets + sizeof(long long) * ((size_t)frames + 1));
-    desc = up(kps + sizeof(BriskKeyPoint) * (size_t)rows);
-    bytes = up(desc + (size_t)rows * (size_t)desc_stride) + 256;
-  }
-};
-
-// the egress kernel of slot E has finished (ctx->mu held): status of the transfer, and - for a pageable destination - the
-// copy out of the bounce buffer
-static void export_finish(brisk_hip_ctx* ctx, brisk_hip_ctx::ExportSlot& E) {
+// what transfer_finish leaves to this exit: the copy out of the bounce buffer (a pageable destination) ...
+static void export_copy_out(ExportSlot& E) {
   const brisk_hip_batch_host_results& W = E.wr;
-  int flagged = 0, orf = 0;
-  for (int f = 0; f < E.nframes; ++f)
-    if (W.flags[f]) { ++flagged; orf |= W.flags[f]; }
-  if (E.use_bounce) {
-    const long long rows = W.offsets[E.nframes];
-    memcpy(E.dst.counts, W.counts, sizeof(int) * (size_t)E.nframes);
-    memcpy(E.dst.flags, W.flags, sizeof(int) * (size_t)E.nframes);
-    memcpy(E.dst.offsets, W.offsets, sizeof(long long) * ((size_t)E.nframes + 1));
-    if (rows > 0) memcpy(E.dst.kps, W.kps, sizeof(BriskKeyPoint) * (size_t)rows);
-    if (rows > 0 && E.dst.desc) memcpy(E.dst.desc, W.desc, (size_t)rows * (size_t)E.dst.desc_stride);
-  }
-  E.pending = false;
-  E.flagged = flagged;
-  E.rc = BRISK_HIP_OK;
-  E.msg.clear();
-  if (flagged) {
+  const long long rows = W.offsets[E.n];
+  memcpy(E.dst.counts, W.counts, sizeof(int) * (size_t)E.n);
+  memcpy(E.dst.flags, W.flags, sizeof(int) * (size_t)E.n);
+  memcpy(E.dst.offsets, W.offsets, sizeof(long long) * ((size_t)E.n + 1));
+  if (rows > 0) memcpy(E.dst.kps, W.kps, sizeof(BriskKeyPoint) * (size_t)rows);
+  if (rows > 0 && E.dst.desc) memcpy(E.dst.desc, W.desc, (size_t)rows * (size_t)E.dst.desc_stride);
+}
+// ... and the status of a transfer with flagged frames: the detector's overflow bits first, then the rows that did not fit
+static void export_status(brisk_hip_ctx* ctx, ExportSlot& E, int orf) {
+  if (!(orf & 7) && (orf & BRISK_HIP_ROWS_CUT)) {
     char msg[200];
-    if (orf & 7) {
-      E.rc = overflow_to_rc(ctx, orf);
-      E.msg = ctx->err;
-    } else if (orf & BRISK_HIP_ROWS_CUT) {
-      snprintf(msg, sizeof msg, "%d frame(s) did not fit the destination's rows_cap (flags[f] & BRISK_HIP_ROWS_CUT); their counts are reported",
-               flagged);
-      E.rc = BRISK_HIP_ERR_CAPACITY;
-      E.msg = msg;
-    } else {
-      E.rc = overflow_to_rc(ctx, orf);
-      E.msg = ctx->err;
-    }
+    snprintf(msg, sizeof msg, "%d frame(s) did not fit the destination's rows_cap (flags[f] & BRISK_HIP_ROWS_CUT); their counts are reported",
+             E.flagged);
+    E.rc = BRISK_HIP_ERR_CAPACITY;
+    E.msg = msg;
+  } else {
+    E.rc = overflow_to_rc(ctx, orf);
+    E.msg = ctx->err;
   }
+}
+static void export_finish(brisk_hip_ctx* ctx, ExportSlot& E) {
+  transfer_finish(E, export_copy_out, [ctx](ExportSlot& X, int orf) { export_status(ctx, X, orf); });
 }
 
 // The stream of a transfer to the host.  A context that runs detect + describe batches already owns a second stream - `side`, where the integral
@@ -1394,43 +1341,29 @@ static int download_all_locked(brisk_hip_ctx* ctx, int which, const brisk_hip_ba
     return fail(ctx, BRISK_HIP_ERR_ARG, "download_all: destination arrays must be 4-byte aligned (offsets: 8)");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const int dstride = want_desc ? dst->desc_stride : 4;
-  brisk_hip_ctx::ExportSlot& E = ctx->ex[(ctx->ex_seq + 1) & 1];
   hipStream_t es = s;
   if (!egress_on_s)
     if (int rc = egress_stream(ctx, &es)) return rc;
-  if (!E.packed) {
-    HIPCHK(ctx, hipEventCreateWithFlags(&E.packed, hipEventDisableTiming));
-    HIPCHK(ctx, hipEventCreateWithFlags(&E.done, hipEventDisableTiming));
-  }
-  if (E.pending) {  // a third transfer in flight: complete the oldest first
-    HIPCHK(ctx, hipEventSynchronize(E.done));
-    export_finish(ctx, E);
-  }
-  const ExportLayout LY(dst->frames_cap, dst->rows_cap, dstride);
-  if (LY.bytes > E.slab.cap) {
-    if (E.done_valid) HIPCHK(ctx, hipEventSynchronize(E.done));
-    HIPCHK(ctx, E.slab.grow(LY.bytes));
-  }
+  const SlabLayout LY = export_layout(dst->frames_cap, dst->rows_cap, dstride);
+  ExportSlot* slot = nullptr;
+  if (int rc = ctx->ex.open(LY.bytes(), ctx->err, [ctx](ExportSlot& X) { export_finish(ctx, X); }, &slot)) return rc;
+  ExportSlot& E = *slot;
   // where the egress kernel writes: the caller's arrays when the device can reach all of them, else the bounce buffer
-  brisk_hip_batch_host_results W = *dst;
-  void* dv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (known_pinned) { dv[0] = dst->counts; dv[1] = dst->flags; dv[2] = dst->offsets; dv[3] = dst->kps; dv[4] = dst->desc; }
-  const bool direct = known_pinned || (device_can_write(dst->counts, &dv[0]) && device_can_write(dst->flags, &dv[1]) && device_can_write(dst->offsets, &dv[2]) &&
-                (dst->rows_cap == 0 || device_can_write(dst->kps, &dv[3])) && (!want_desc || device_can_write(dst->desc, &dv[4])));
+  brisk_hip_batch_host_results D = *dst;  // the caller's arrays this transfer fills
+  if (!want_desc) D.desc = nullptr;
+  brisk_hip_batch_host_results W = D, H = D;  // W: device-side addresses for the kernel, H: what the host reads at the wait
+  HostDst dv[5] = {{D.counts, true}, {D.flags, true}, {D.offsets, true}, {D.kps, dst->rows_cap != 0}, {D.desc, want_desc}};
+  const bool direct = device_can_write_all(dv, known_pinned);
   if (direct) {
-    W.counts = static_cast<int*>(dv[0]); W.flags = static_cast<int*>(dv[1]); W.offsets = static_cast<long long*>(dv[2]);
-    W.kps = static_cast<brisk_hip_keypoint*>(dv[3]); W.desc = want_desc ? static_cast<uint8_t*>(dv[4]) : nullptr;
+    W.counts = static_cast<int*>(dv[0].p); W.flags = static_cast<int*>(dv[1].p); W.offsets = static_cast<long long*>(dv[2].p);
+    W.kps = static_cast<brisk_hip_keypoint*>(dv[3].p); W.desc = static_cast<uint8_t*>(dv[4].p);
   } else {
-    HIPCHK(ctx, E.bounce.grow(LY.bytes));
-    uint8_t* const bo = E.bounce.as<uint8_t>();
-    W.counts = reinterpret_cast<int*>(bo + LY.counts); W.flags = reinterpret_cast<int*>(bo + LY.flags);
-    W.offsets = reinterpret_cast<long long*>(bo + LY.offsets); W.kps = reinterpret_cast<brisk_hip_keypoint*>(bo + LY.kps);
-    W.desc = want_desc ? bo + LY.desc : nullptr;
+    HIPCHK(ctx, E.bounce.grow(LY.bytes()));
+    W = H = export_at(LY, E.bounce.as<uint8_t>(), dst->frames_cap, dst->desc_stride, dst->rows_cap);
+    if (!want_desc) W.desc = H.desc = nullptr;
   }
   uint8_t* sl = E.slab.as<uint8_t>();
-  const BriskExportSlab S{reinterpret_cast<int*>(sl + LY.counts), reinterpret_cast<int*>(sl + LY.flags),
-                          reinterpret_cast<long long*>(sl + LY.offsets), reinterpret_cast<uint32_t*>(sl + LY.kps),
-                          reinterpret_cast<uint32_t*>(sl + LY.desc)};
+  const BriskExportSlab S{LY.at<int>(sl, 0), LY.at<int>(sl, 1), LY.at<long long>(sl, 2), LY.at<uint32_t>(sl, 3), LY.at<uint32_t>(sl, 4)};
   if (workspace_acquire(ctx, s)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
   WorkspaceGuard guard(ctx, s);
   if (E.done_valid) HIPCHK(ctx, hipStreamWaitEvent(s, E.done, 0));  // the slab's previous transfer
@@ -1444,22 +1377,9 @@ static int download_all_locked(brisk_hip_ctx* ctx, int which, const brisk_hip_ba
   static const bool egress_off = tuning_env("BRISK_EXPORT_EGRESS") && atoi(tuning_env("BRISK_EXPORT_EGRESS")) == 0;  // timing experiments: pack only (the destination stays unwritten)
   if (!egress_off) brisk_launch_export_egress(S, nframes, dstride, W.counts, W.flags, W.offsets, W.kps, W.desc, es);
   HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipEventRecord(E.done, es));
-  E.done_valid = true;
-  E.pending = true;
-  E.use_bounce = !direct;
-  E.nframes = nframes;
-  E.dst = *dst;
-  if (!want_desc) E.dst.desc = nullptr;
-  if (direct) {  // the host reads the caller's own arrays
-    W = *dst;
-    if (!want_desc) W.desc = nullptr;
-  }
-  E.wr = W;
-  E.ticket = ++ctx->ex_seq;
-  if (!E.ticket) E.ticket = ++ctx->ex_seq;  // (0 is never a ticket)
-  *ticket = E.ticket;
-  return BRISK_HIP_OK;
+  E.dst = D;
+  E.wr = H;
+  return ctx->ex.close(E, es, !direct, nframes, ctx->err, ticket);
 }
 
 int brisk_hip_batch_download_all(brisk_hip_ctx* ctx, int which, const brisk_hip_batch_host_results* dst, void* stream,
@@ -1469,46 +1389,11 @@ int brisk_hip_batch_download_all(brisk_hip_ctx* ctx, int which, const brisk_hip_
   return download_all_locked(ctx, which, dst, stream ? (hipStream_t)stream : ctx->stream, ticket);
 }
 
-// Completes the transfers of `slots` up to `ticket`, oldest first, and reports `ticket`'s outcome (brisk_hip_batch_download_wait and
-// brisk_hip_pair_matches_wait: ctx->mu held through `lk`, released while the host waits for the device).  finish(slot): the slot's
-// egress kernel is done.  name: the head of the messages.
-extern "C++" {
-template <class Slot, class Finish>
-static int wait_transfers(brisk_hip_ctx* ctx, std::unique_lock<std::mutex>& lk, Slot (&slots)[2], unsigned ticket, int* flagged, Finish finish,
-                          const char* name) {
-  if (flagged) *flagged = 0;
-  if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BRISK_HIP_ERR_HIP, "hipSetDevice failed");
-  for (int pass = 0; pass < 2; ++pass) {
-    Slot* E = nullptr;
-    for (auto& X : slots)
-      if (X.pending && (int)(X.ticket - ticket) <= 0 && (!E || (int)(X.ticket - E->ticket) < 0)) E = &X;
-    if (!E) break;
-    const unsigned t = E->ticket;
-    hipEvent_t ev = E->done;
-    lk.unlock();
-    const hipError_t e = hipEventSynchronize(ev);
-    lk.lock();
-    if (e != hipSuccess) {
-      ctx->err = std::string(name) + ": " + hipGetErrorString(e);
-      return BRISK_HIP_ERR_HIP;
-    }
-    if (E->pending && E->ticket == t) finish(*E);  // (unless another thread completed it meanwhile)
-  }
-  for (auto& X : slots)
-    if (X.ticket == ticket && ticket != 0 && !X.pending) {
-      if (flagged) *flagged = X.flagged;
-      if (X.rc) ctx->err = X.msg;
-      return X.rc;
-    }
-  return fail(ctx, BRISK_HIP_ERR_ARG, (std::string(name) + ": unknown ticket (never issued on this context, or two later transfers have replaced it)").c_str());
-}
-}
-
 int brisk_hip_batch_download_wait(brisk_hip_ctx* ctx, unsigned ticket, int* frames_flagged) {
   if (!ctx) return BRISK_HIP_ERR_ARG;
   std::unique_lock<std::mutex> lk(ctx->mu);
-  return wait_transfers(ctx, lk, ctx->ex, ticket, frames_flagged, [&](brisk_hip_ctx::ExportSlot& E) { export_finish(ctx, E); },
-                        "brisk_hip_batch_download_wait");
+  return ctx->ex.wait(ctx->device, ctx->err, lk, ticket, frames_flagged, [ctx](ExportSlot& E) { export_finish(ctx, E); },
+                      "brisk_hip_batch_download_wait");
 }
 
 int brisk_hip_detect_describe_batch_host_results(brisk_hip_ctx* ctx, const brisk_hip_pattern* pat, const uint8_t* h_frames,
@@ -2246,51 +2131,44 @@ int brisk_hip_select_pair_matches_device(brisk_hip_ctx* ctx, const brisk_hip_dma
   return BRISK_HIP_OK;
 }
 
-// byte offsets of the five arrays inside a slab / bounce buffer holding `pairs` pairs and `matches` records
-struct MatchLayout {
-  size_t rows, counts, flags, offsets, matches, bytes;
-  MatchLayout(int pairs, long long nmatches) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    rows = 0;
-    counts = up(rows + sizeof(int) * (size_t)pairs);
-    flags = up(counts + sizeof(int) * (size_t)pairs);
-    offsets = up(flags + sizeof(int) * (size_t)pairs);
-    matches = up(offsets + sizeof(long long) * ((size_t)pairs + 1));
-    bytes = up(matches + sizeof(brisk_hip_dmatch) * (size_t)nmatches) + 256;
-  }
-  brisk_hip_pair_host_matches at(uint8_t* base, int pairs, long long nmatches) const {
-    return brisk_hip_pair_host_matches{pairs, nmatches, reinterpret_cast<int*>(base + rows), reinterpret_cast<int*>(base + counts),
-                                       reinterpret_cast<int*>(base + flags), reinterpret_cast<long long*>(base + offsets),
-                                       reinterpret_cast<brisk_hip_dmatch*>(base + matches)};
-  }
-};
+using MatchSlot = TransferRing<brisk_hip_pair_host_matches>::Slot;
 
-// the egress kernel of slot E has finished (ctx->mu held): status of the transfer, and - for a pageable destination - the copy
-// out of the bounce buffer
-static void matches_finish(brisk_hip_ctx::MatchSlot& E) {
-  const brisk_hip_pair_host_matches& W = E.wr;
-  int flagged = 0, cut = 0;
-  for (int p = 0; p < E.npairs; ++p)
-    if (W.flags[p]) { ++flagged; cut += (W.flags[p] & BRISK_HIP_ROWS_CUT) != 0; }
-  if (E.use_bounce) {
-    const long long n = W.offsets[E.npairs];
-    memcpy(E.dst.pair_rows, W.pair_rows, sizeof(int) * (size_t)E.npairs);
-    memcpy(E.dst.counts, W.counts, sizeof(int) * (size_t)E.npairs);
-    memcpy(E.dst.flags, W.flags, sizeof(int) * (size_t)E.npairs);
-    memcpy(E.dst.offsets, W.offsets, sizeof(long long) * ((size_t)E.npairs + 1));
-    if (n > 0) memcpy(E.dst.matches, W.matches, sizeof(brisk_hip_dmatch) * (size_t)n);
-  }
-  E.pending = false;
-  E.flagged = flagged;
-  E.rc = BRISK_HIP_OK;
-  E.msg.clear();
-  if (cut) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "%d pair(s) did not fit the destination's matches_cap (flags[p] & BRISK_HIP_ROWS_CUT); their counts are reported", cut);
-    E.rc = BRISK_HIP_ERR_CAPACITY;
-    E.msg = msg;
-  }
+// the five arrays of a call's selected matches for `pairs` pairs and `nmatches` records, in the order a slab and a bounce buffer hold them
+static SlabLayout match_layout(int pairs, long long nmatches) {
+  SlabLayout LY;
+  LY.add(sizeof(int) * (size_t)pairs);                   // pair_rows
+  LY.add(sizeof(int) * (size_t)pairs);                   // counts
+  LY.add(sizeof(int) * (size_t)pairs);                   // flags
+  LY.add(sizeof(long long) * ((size_t)pairs + 1));       // offsets
+  LY.add(sizeof(brisk_hip_dmatch) * (size_t)nmatches);   // matches
+  return LY;
 }
+static brisk_hip_pair_host_matches match_at(const SlabLayout& LY, uint8_t* base, int pairs, long long nmatches) {
+  return brisk_hip_pair_host_matches{pairs, nmatches, LY.at<int>(base, 0), LY.at<int>(base, 1), LY.at<int>(base, 2), LY.at<long long>(base, 3),
+                                     LY.at<brisk_hip_dmatch>(base, 4)};
+}
+
+// what transfer_finish leaves to this exit: the copy out of the bounce buffer (a pageable destination) ...
+static void matches_copy_out(MatchSlot& E) {
+  const brisk_hip_pair_host_matches& W = E.wr;
+  const long long n = W.offsets[E.n];
+  memcpy(E.dst.pair_rows, W.pair_rows, sizeof(int) * (size_t)E.n);
+  memcpy(E.dst.counts, W.counts, sizeof(int) * (size_t)E.n);
+  memcpy(E.dst.flags, W.flags, sizeof(int) * (size_t)E.n);
+  memcpy(E.dst.offsets, W.offsets, sizeof(long long) * ((size_t)E.n + 1));
+  if (n > 0) memcpy(E.dst.matches, W.matches, sizeof(brisk_hip_dmatch) * (size_t)n);
+}
+// ... and the status of a transfer with flagged pairs: only the pairs that did not fit are an error (the matchers' own flags are information)
+static void matches_status(MatchSlot& E, int orf) {
+  if (!(orf & BRISK_HIP_ROWS_CUT)) return;
+  int cut = 0;
+  for (int p = 0; p < E.n; ++p) cut += (E.wr.flags[p] & BRISK_HIP_ROWS_CUT) != 0;
+  char msg[200];
+  snprintf(msg, sizeof msg, "%d pair(s) did not fit the destination's matches_cap (flags[p] & BRISK_HIP_ROWS_CUT); their counts are reported", cut);
+  E.rc = BRISK_HIP_ERR_CAPACITY;
+  E.msg = msg;
+}
+static void matches_finish(MatchSlot& E) { transfer_finish(E, matches_copy_out, matches_status); }
 
 int brisk_hip_pair_matches_download(brisk_hip_ctx* ctx, const brisk_hip_dmatch* d_out, const int* d_out_count, const int* d_pair_rows,
                                     int npairs, int rows_cap, int per_row, const brisk_hip_match_select* select,
@@ -2309,35 +2187,24 @@ int brisk_hip_pair_matches_download(brisk_hip_ctx* ctx, const brisk_hip_dmatch* 
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream, es = nullptr;
   if (int rc = egress_stream(ctx, &es)) return rc;
-  brisk_hip_ctx::MatchSlot& E = ctx->mx[(ctx->mx_seq + 1) & 1];
-  if (!E.packed) {
-    HIPCHK(ctx, hipEventCreateWithFlags(&E.packed, hipEventDisableTiming));
-    HIPCHK(ctx, hipEventCreateWithFlags(&E.done, hipEventDisableTiming));
-  }
-  if (E.pending) {  // a third transfer in flight: complete the oldest first
-    HIPCHK(ctx, hipEventSynchronize(E.done));
-    matches_finish(E);
-  }
   const int pairs = npairs > 0 ? npairs : 1;
-  const MatchLayout LY(pairs, dst->matches_cap);
-  if (LY.bytes > E.slab.cap) {
-    if (E.done_valid) HIPCHK(ctx, hipEventSynchronize(E.done));
-    HIPCHK(ctx, E.slab.grow(LY.bytes));
-  }
+  const SlabLayout LY = match_layout(pairs, dst->matches_cap);
+  MatchSlot* slot = nullptr;
+  if (int rc = ctx->mx.open(LY.bytes(), ctx->err, matches_finish, &slot)) return rc;
+  MatchSlot& E = *slot;
   // where the egress kernel writes: the caller's arrays when the device can reach all of them, else the bounce buffer
-  void* dv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  const bool direct = (npairs == 0 || (device_can_write(dst->pair_rows, &dv[0]) && device_can_write(dst->counts, &dv[1]) &&
-                                       device_can_write(dst->flags, &dv[2]))) &&
-                      device_can_write(dst->offsets, &dv[3]) && (dst->matches_cap == 0 || device_can_write(dst->matches, &dv[4]));
+  HostDst dv[5] = {{dst->pair_rows, npairs != 0}, {dst->counts, npairs != 0}, {dst->flags, npairs != 0}, {dst->offsets, true},
+                   {dst->matches, dst->matches_cap != 0}};
+  const bool direct = device_can_write_all(dv);
   brisk_hip_pair_host_matches W = *dst, H = *dst;  // W: device-side addresses for the kernel, H: what the host reads at the wait
   if (direct) {
-    W.pair_rows = static_cast<int*>(dv[0]); W.counts = static_cast<int*>(dv[1]); W.flags = static_cast<int*>(dv[2]);
-    W.offsets = static_cast<long long*>(dv[3]); W.matches = static_cast<brisk_hip_dmatch*>(dv[4]);
+    W.pair_rows = static_cast<int*>(dv[0].p); W.counts = static_cast<int*>(dv[1].p); W.flags = static_cast<int*>(dv[2].p);
+    W.offsets = static_cast<long long*>(dv[3].p); W.matches = static_cast<brisk_hip_dmatch*>(dv[4].p);
   } else {
-    HIPCHK(ctx, E.bounce.grow(LY.bytes));
-    W = H = LY.at(E.bounce.as<uint8_t>(), pairs, dst->matches_cap);
+    HIPCHK(ctx, E.bounce.grow(LY.bytes()));
+    W = H = match_at(LY, E.bounce.as<uint8_t>(), pairs, dst->matches_cap);
   }
-  const brisk_hip_pair_host_matches S = LY.at(E.slab.as<uint8_t>(), pairs, dst->matches_cap);
+  const brisk_hip_pair_host_matches S = match_at(LY, E.slab.as<uint8_t>(), pairs, dst->matches_cap);
   if (workspace_acquire(ctx, s)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
   WorkspaceGuard guard(ctx, s);
   if (E.done_valid) HIPCHK(ctx, hipStreamWaitEvent(s, E.done, 0));  // the slab's previous transfer
@@ -2354,24 +2221,15 @@ int brisk_hip_pair_matches_download(brisk_hip_ctx* ctx, const brisk_hip_dmatch* 
   brisk_launch_pair_select_egress(S.pair_rows, S.counts, S.flags, S.offsets, reinterpret_cast<const BriskDMatch*>(S.matches), npairs, W.pair_rows,
                                   W.counts, W.flags, W.offsets, W.matches, es);
   HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipEventRecord(E.done, es));
-  E.done_valid = true;
-  E.pending = true;
-  E.use_bounce = !direct;
-  E.npairs = npairs;
   E.dst = *dst;
   E.wr = H;
-  E.ticket = ++ctx->mx_seq;
-  if (!E.ticket) E.ticket = ++ctx->mx_seq;  // (0 is never a ticket)
-  *ticket = E.ticket;
-  return BRISK_HIP_OK;
+  return ctx->mx.close(E, es, !direct, npairs, ctx->err, ticket);
 }
 
 int brisk_hip_pair_matches_wait(brisk_hip_ctx* ctx, unsigned ticket, int* pairs_flagged) {
   if (!ctx) return BRISK_HIP_ERR_ARG;
   std::unique_lock<std::mutex> lk(ctx->mu);
-  return wait_transfers(ctx, lk, ctx->mx, ticket, pairs_flagged, [](brisk_hip_ctx::MatchSlot& E) { matches_finish(E); },
-                        "brisk_hip_pair_matches_wait");
+  return ctx->mx.wait(ctx->device, ctx->err, lk, ticket, pairs_flagged, matches_finish, "brisk_hip_pair_matches_wait");
 }
 
 int brisk_hip_match_radius_device(brisk_hip_ctx* ctx, const uint8_t* d_query, int nq, int q_pitch, const uint8_t* d_train, int nt,

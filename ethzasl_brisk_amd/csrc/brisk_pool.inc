@@ -119,16 +119,9 @@ static int pool_prepare_group(brisk_hip_pool* P, std::unique_lock<std::mutex>& l
   const int rstride = key.kind == 2 ? key.pat->host.strings : 4;  // descriptor rows packed at the descriptor size
   if (!G.res_mem.p || rstride > G.res_stride_cap) {
     G.res_stride_cap = rstride > 64 ? rstride : 64;
-    const ExportLayout LY(P->maxb, P->rows_per_group, G.res_stride_cap);
-    if (G.res_mem.grow(LY.bytes) != hipSuccess) return BRISK_HIP_ERR_HIP;
-    uint8_t* const m = G.res_mem.as<uint8_t>();
-    G.res.frames_cap = P->maxb;
-    G.res.rows_cap = P->rows_per_group;
-    G.res.counts = reinterpret_cast<int*>(m + LY.counts);
-    G.res.flags = reinterpret_cast<int*>(m + LY.flags);
-    G.res.offsets = reinterpret_cast<long long*>(m + LY.offsets);
-    G.res.kps = reinterpret_cast<brisk_hip_keypoint*>(m + LY.kps);
-    G.res.desc = m + LY.desc;
+    const SlabLayout LY = export_layout(P->maxb, P->rows_per_group, G.res_stride_cap);
+    if (G.res_mem.grow(LY.bytes()) != hipSuccess) return BRISK_HIP_ERR_HIP;
+    G.res = export_at(LY, G.res_mem.as<uint8_t>(), P->maxb, rstride, P->rows_per_group);
   }
   G.res.desc_stride = rstride;
   G.key = key;

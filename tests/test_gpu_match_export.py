@@ -392,3 +392,107 @@ def test_arguments(B, synth):
     # keep_per_row above per_row is fine: the stored entries bound it
     assert raw_select(ctx, triple, 2, B.MatchSelect(INF, 0.0, 1000), 64 * 1024, sentinel_select_outputs(npairs, 64 * 1024)) == 0
     torch.cuda.synchronize()
+
+
+# ---- 8: both exits in flight on one context ---------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def three_frames(golden_ast):
+    import torch
+    frames = np.ascontiguousarray(batch_frames(golden_ast)[:3])     # img2, img1, img1 shifted: keypoints in every frame
+    return torch.from_numpy(frames).cuda(), frames.shape
+
+
+class BothExits:
+    """a fresh context with a described batch of three frames and its k = 2 matches over the pairs (0, 1), (1, 2), (0, 2), all on the
+    context's own stream, and what the synchronous routes deliver for them: per-frame batch_download, select_pair_matches + copy"""
+    SEL = (INF, 0.0, 2)
+
+    def __init__(self, B, three_frames):
+        import torch
+        d, (n, h, w) = three_frames
+        self.B, self.n = B, n
+        self.ctx = B.Context(0)
+        self.ext = B.BriskDescriptorExtractor(context=self.ctx)
+        self.d_pairs = torch.from_numpy(np.array([(0, 1), (1, 2), (0, 2)], np.int32)).cuda()
+        torch.cuda.synchronize()
+        self.ctx.detect_describe_batch(self.ext, d.data_ptr(), n, w, h, w * h, w, 70, 2)
+        st, self.dim = self.ctx.batch_desc_set()
+        self.out = self.ctx.match_knn_pairs(st, st, B.PairSpec(3, 0, 0, 0, 0, self.d_pairs.data_ptr()), 2)
+        self.rows = [self.ctx.batch_download(f, True, strings=self.dim) for f in range(n)]
+        self.nrows = sum(len(k) for k, _ in self.rows)
+        self.matches = self.select()
+        self.nmatches = int(self.matches[3][-1])
+        self.pair_rows = self.out[2].cpu().numpy()                  # (behind select()'s synchronise)
+        assert all(len(k) > 100 for k, _ in self.rows) and (self.matches[1] > 100).all() and self.dim % 4 == 0
+
+    def select(self, matches_cap=None):
+        m, c, f, o = device_select(self.B, self.ctx, self.out, 2, self.SEL, matches_cap)    # (synchronises before the copy)
+        return m[:int(o[-1])], c, f, o                              # the stored records, not the array's capacity
+
+    def downloads(self, rows_cap, matches_cap, pinned):
+        """queues one transfer of each exit; -> (HostResults, its ticket, HostMatches, its ticket)"""
+        r, m = self.B.HostResults(self.n, rows_cap, self.dim, pinned=pinned), self.B.HostMatches(3, matches_cap, pinned=pinned)
+        tr = self.ctx.batch_download_all(r)
+        return r, tr, m, self.ctx.pair_matches_download(self.out, 2, self.B.MatchSelect(*self.SEL), m)
+
+    def last_error(self):
+        return self.ctx._L.brisk_hip_last_error(self.ctx._h).decode()
+
+    def close(self):
+        self.ext.close()
+        self.ctx.close()
+
+
+@pytest.mark.parametrize("pinned", [True, False])
+def test_both_exits_in_flight(B, three_frames, pinned):
+    """three transfers of rows and three of matches queued alternately without a wait, completed in reverse order of issue: each exit
+    keeps its own two transfers in flight and counts its own tickets; pageable destinations go through both exits' bounce buffers"""
+    X = BothExits(B, three_frames)
+    ctx = X.ctx
+    got = [X.downloads(X.nrows, X.nmatches, pinned) for _ in range(3)]
+    assert [g[1] for g in got] == [1, 2, 3] and [g[3] for g in got] == [1, 2, 3]
+    for i in (2, 1, 0):
+        rc_m, flagged_m = ctx.pair_matches_wait(got[i][3], check=False)
+        msg_m = X.last_error()
+        rc_r, flagged_r = ctx.batch_download_wait(got[i][1], check=False)
+        msg_r = X.last_error()
+        if i == 0:                                                  # completed when the third transfer took the slot, then replaced
+            assert (rc_m, rc_r) == (1, 1)
+            assert msg_m.startswith("brisk_hip_pair_matches_wait: unknown ticket") and msg_r.startswith("brisk_hip_batch_download_wait: unknown ticket")
+        else:
+            assert (rc_m, flagged_m, rc_r, flagged_r) == (0, 0, 0, 0)
+    for r, _, m, _ in got[1:]:
+        assert np.array_equal(r.counts, [len(k) for k, _ in X.rows]) and not r.flags.any()
+        assert np.array_equal(r.offsets, np.cumsum([0] + [len(k) for k, _ in X.rows]))
+        for f in range(X.n):
+            assert r.frame(f, X.dim)[0].tobytes() == X.rows[f][0].tobytes() and r.frame(f, X.dim)[1].tobytes() == X.rows[f][1].tobytes()
+        same_selection(host_got(m, 3), X.matches)
+        assert m.matches[:X.nmatches].tobytes() == X.matches[0][:X.nmatches].tobytes()
+        assert np.array_equal(m.pair_rows, X.pair_rows)
+    X.close()
+
+
+@pytest.mark.parametrize("pinned", [True, False])
+def test_both_exits_short_of_capacity(B, three_frames, pinned):
+    """rows_cap and matches_cap one below what the batch needs, in both exits at once: each wait answers BRISK_HIP_ERR_CAPACITY with
+    its own message and its own count of flagged entries"""
+    X = BothExits(B, three_frames)
+    ctx = X.ctx
+    r, tr, m, tm = X.downloads(X.nrows - 1, X.nmatches - 1, pinned)
+    assert (tr, tm) == (1, 1)
+    want = X.select(matches_cap=X.nmatches - 1)                     # the last pair does not fit
+    assert list(want[2] & ROWS_CUT) == [0, 0, ROWS_CUT]
+    rc, flagged = ctx.pair_matches_wait(tm, check=False)
+    assert (rc, flagged) == (4, int((want[2] != 0).sum())) and flagged >= 1
+    assert "1 pair(s) did not fit the destination's matches_cap" in X.last_error()
+    rc, flagged = ctx.batch_download_wait(tr, check=False)
+    assert (rc, flagged) == (4, 1)                                  # the last frame does not fit
+    assert "1 frame(s) did not fit the destination's rows_cap" in X.last_error()
+    same_selection(host_got(m, 3), want)
+    counts = [len(k) for k, _ in X.rows]
+    assert np.array_equal(r.counts, counts) and list(r.flags) == [0, 0, ROWS_CUT]
+    assert list(r.offsets) == [0, counts[0], counts[0] + counts[1], counts[0] + counts[1]]
+    for f in range(2):                                              # the frames before the cut are in place
+        assert r.frame(f, X.dim)[0].tobytes() == X.rows[f][0].tobytes() and r.frame(f, X.dim)[1].tobytes() == X.rows[f][1].tobytes()
+    X.close()
