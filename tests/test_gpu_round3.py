@@ -7,6 +7,7 @@ import pytest
 
 import oracle_lib as O
 import synth
+from batch_scale_lib import slot_frame
 from test_gpu_parity import same_kps, explain  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -22,8 +23,9 @@ def B():
 
 
 def _run_batch_and_compare(B, frames_distinct, n, thr, octaves, w, h, every_slot=True):
-    """n slots filled round-robin from the distinct frames; every slot (or the first, middle and last ones of each
-    distinct frame) is compared with the oracle: keypoints as detected, keypoints as described, descriptors."""
+    """n slots filled from the distinct frames - slot f holds frame slot_frame(f, nd), so that slots 8 apart (the engine's
+    cross-frame bookkeeping is modulo 8) never hold the same one; every slot (or the first, middle and last nd ones) is
+    compared with the oracle: keypoints as detected, keypoints as described, descriptors."""
     import torch
     nd = len(frames_distinct)
     X = O.Extractor()
@@ -31,7 +33,7 @@ def _run_batch_and_compare(B, frames_distinct, n, thr, octaves, w, h, every_slot
     for img in frames_distinct:
         ko = O.detect(img, thr, octaves)
         want.append((ko,) + X.compute(img, ko))
-    stack = np.stack([frames_distinct[f % nd] for f in range(n)])
+    stack = np.stack([frames_distinct[slot_frame(f, nd)] for f in range(n)])
     d = torch.from_numpy(stack).cuda()
     cap = max(len(k[0]) for k in want)
     ctx = B.Context(0, 4 * cap, 2 * cap) if cap > 12000 else B.Context(0)
@@ -42,7 +44,7 @@ def _run_batch_and_compare(B, frames_distinct, n, thr, octaves, w, h, every_slot
         assert ctx.batch_status(n) == 0
         slots = range(n) if every_slot else sorted(set(list(range(nd)) + list(range(n // 2, n // 2 + nd)) + list(range(n - nd, n))))
         for f in slots:
-            ko, ko2, do = want[f % nd]
+            ko, ko2, do = want[slot_frame(f, nd)]
             kd, _ = ctx.batch_download(f, described=False)
             kg, dg = ctx.batch_download(f, described=True)
             assert same_kps(kd, ko), (n, rep, f, explain(kd, ko))
