@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "brisk_hip_match_radius_pairs_device", "brisk_hip_match_radius_device",
     "brisk_hip_batch_kp_set", "brisk_hip_match_knn_pairs_gated_device", "brisk_hip_match_radius_pairs_gated_device",
     "brisk_hip_select_pair_matches_device", "brisk_hip_pair_matches_download", "brisk_hip_pair_matches_wait",
+    "brisk_hip_link_tracks_device", "brisk_hip_list_tracks_device",
 ]
 # every symbol include/brisk_hip_debug.h declares: test / tuning builds (BRISK_HIP_TUNING) only
 DEBUG_SYMBOLS = [
@@ -110,6 +111,17 @@ class PairHostMatches(C.Structure):
     """brisk_hip_pair_host_matches: capacities + the five destination arrays of a batch's selected matches in host memory"""
     _fields_ = [("pairs_cap", C.c_int), ("matches_cap", C.c_longlong), ("pair_rows", C.c_void_p), ("counts", C.c_void_p),
                 ("flags", C.c_void_p), ("offsets", C.c_void_p), ("matches", C.c_void_p)]
+
+
+class TrackSeed(C.Structure):
+    """brisk_hip_track_seed: d_track / d_age [rows_cap] device arrays (row r of node 0 continues track d_track[r] >= 0 at age
+    d_age[r]; both None = no seeds), first_new = the first number the call may give - read from the device word d_first_new when
+    that is set (the previous call's summary).  The structure holds raw pointers: the caller keeps the tensors alive."""
+    _fields_ = [("d_track", C.c_void_p), ("d_age", C.c_void_p), ("first_new", C.c_longlong), ("d_first_new", C.c_void_p)]
+
+
+TRACK_OBS = np.dtype([("node", "<i4"), ("row", "<i4")])   # brisk_hip_track_obs
+TRACKS_CUT = 1                                              # flag bit 0 of list_tracks' summary
 
 
 # flags of a pair in the selected lists (ROWS_CUT: the pair and every pair behind it did not fit matches_cap)
@@ -273,6 +285,9 @@ def load_library():
     L.brisk_hip_pair_matches_download.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(MatchSelect),
                                                   C.POINTER(PairHostMatches), vp, C.POINTER(C.c_uint)]
     L.brisk_hip_pair_matches_wait.argtypes = [vp, C.c_uint, ip]
+    L.brisk_hip_link_tracks_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(TrackSeed), vp, vp, vp, vp, vp]
+    L.brisk_hip_list_tracks_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_longlong, C.c_longlong,
+                                               vp, vp, vp, vp, vp, vp]
     L.brisk_hip_reserve.argtypes = [vp, C.c_int, C.c_int]
     L.brisk_hip_detect_uniform.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
                                            C.c_double, C.c_int, vp, C.c_int, ip]
@@ -678,6 +693,56 @@ class Context:
             return rc, n.value
         self.check(rc)
         return n.value
+
+    # -- a batch's pair matches linked into feature tracks --
+    @staticmethod
+    def _node_rows(node_rows):
+        """(device pointer, stride in ints) of a chain's row counts: a (tensor, stride) pair, or a (DescSet, first, step) triple -
+        the frames first + i * step of the set"""
+        if len(node_rows) == 3:
+            st, first, step = node_rows
+            return int(st.d_counts) + 4 * int(first) * int(st.count_stride), int(step) * int(st.count_stride)
+        t, stride = node_rows
+        return t.data_ptr(), int(stride)
+
+    def link_tracks(self, node_rows, nodes, rows_cap, offsets, matches, seed=None, stream=None):
+        """brisk_hip_link_tracks_device.  node_rows: (int32 device tensor, stride) or (DescSet, first, step); offsets / matches: what
+        select_pair_matches returned for the chain's nodes - 1 pairs (None with nodes == 1); seed: a TrackSeed.  Returns the device
+        tensors (prev [nodes, rows_cap] int32, track [nodes, rows_cap] int64, age [nodes, rows_cap] int32, summary [8] int64); only
+        the rows below each node's count are written.  Asynchronous on `stream`."""
+        import torch
+        ptr, stride = self._node_rows(node_rows)
+        dev = "cuda:%d" % self.device
+        shape = (int(nodes), int(rows_cap))
+        res = (torch.empty(shape, dtype=torch.int32, device=dev), torch.empty(shape, dtype=torch.int64, device=dev),
+               torch.empty(shape, dtype=torch.int32, device=dev), torch.empty(8, dtype=torch.int64, device=dev))
+        self.check(self._L.brisk_hip_link_tracks_device(self._h, ptr, stride, int(nodes), int(rows_cap),
+                                                        None if offsets is None else offsets.data_ptr(),
+                                                        None if matches is None else matches.data_ptr(),
+                                                        C.byref(seed) if seed is not None else None, res[0].data_ptr(), res[1].data_ptr(),
+                                                        res[2].data_ptr(), res[3].data_ptr(), C.c_void_p(stream) if stream else None))
+        return res
+
+    def list_tracks(self, node_rows, nodes, rows_cap, prev, track, age, min_len, tracks_cap=None, obs_cap=None, stream=None):
+        """brisk_hip_list_tracks_device on what link_tracks returned.  tracks_cap / obs_cap None = everything fits (nodes * rows_cap).
+        Returns the device tensors (list_track [tracks_cap] int64, list_len [tracks_cap] int32, list_offsets [tracks_cap + 1] int64,
+        list_obs [obs_cap, 2] int32 - {node, row} records -, summary [4] int64: pieces listed, their observations, pieces stored,
+        flags).  Asynchronous on `stream`."""
+        import torch
+        ptr, stride = self._node_rows(node_rows)
+        if tracks_cap is None:
+            tracks_cap = int(nodes) * int(rows_cap)
+        if obs_cap is None:
+            obs_cap = int(nodes) * int(rows_cap)
+        dev, tc, oc = prev.device, max(int(tracks_cap), 0), max(int(obs_cap), 0)
+        res = (torch.empty(tc, dtype=torch.int64, device=dev), torch.empty(tc, dtype=torch.int32, device=dev),
+               torch.empty(tc + 1, dtype=torch.int64, device=dev), torch.empty((oc, 2), dtype=torch.int32, device=dev),
+               torch.empty(4, dtype=torch.int64, device=dev))
+        self.check(self._L.brisk_hip_list_tracks_device(self._h, ptr, stride, int(nodes), int(rows_cap), prev.data_ptr(), track.data_ptr(),
+                                                        age.data_ptr(), int(min_len), int(tracks_cap), int(obs_cap), res[0].data_ptr(),
+                                                        res[1].data_ptr(), res[2].data_ptr(), res[3].data_ptr(), res[4].data_ptr(),
+                                                        C.c_void_p(stream) if stream else None))
+        return res
 
     def match_radius_device(self, d_query, nq, q_pitch, d_train, nt, t_pitch, dim_bytes, max_distance, cap_per_query, d_out, d_out_count,
                             stream=None):

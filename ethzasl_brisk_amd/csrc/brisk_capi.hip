@@ -142,6 +142,7 @@ struct brisk_hip_ctx {
   TransferRing<brisk_hip_pair_host_matches> mx;   // brisk_hip_pair_matches_download
   hipStream_t egress = nullptr;
   DeviceBuf d_select;  // brisk_hip_select_pair_matches_device / _pair_matches_download: the per-workgroup sums of the selection passes
+  DeviceBuf d_track;   // brisk_hip_link_tracks_device / _list_tracks_device: claim words, forward pointers, piece words, workgroup sums
   int last_strings = 0;  // descriptor bytes of the pattern the last describing call used
 };
 
@@ -2127,6 +2128,98 @@ int brisk_hip_select_pair_matches_device(brisk_hip_ctx* ctx, const brisk_hip_dma
   if (int rc = select_launch(ctx, d_out, d_out_count, d_pair_rows, npairs, rows_cap, per_row, select, matches_cap, d_counts, d_flags, d_offsets,
                              d_matches, nullptr, st))
     return rc;
+  if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
+  return BRISK_HIP_OK;
+}
+
+// ---- a batch's pair matches linked into feature tracks (kernels: brisk_track.hip) --------------------------------------------
+static_assert(sizeof(brisk_hip_track_seed) == 32 && sizeof(brisk_hip_track_obs) == 8 && BRISK_TRACK_LIST_CUT == BRISK_HIP_TRACKS_CUT,
+              "track seed / observation layout");
+
+// what both calls check of the chain, before anything is launched
+static const char* track_chain_check(const int* d_node_rows, int node_rows_stride, int nodes, int rows_cap) {
+  if (nodes < 1 || rows_cap < 1 || node_rows_stride < 1) return "tracks: nodes, rows_cap or node_rows_stride below 1";
+  if (!d_node_rows || ((uintptr_t)d_node_rows & 3)) return "tracks: d_node_rows null or not 4-byte aligned";
+  return nullptr;
+}
+
+// the scratch of both calls, one region behind the other, each 16-byte aligned
+struct TrackScratch {
+  size_t bytes = 0;
+  size_t add(size_t n) { const size_t at = bytes; bytes += (n + 15) & ~(size_t)15; return at; }
+};
+
+static int track_scratch_grow(brisk_hip_ctx* ctx, size_t bytes) {
+  if (ctx->d_track.cap < bytes) {
+    HIPCHK(ctx, wait_own_work(ctx));  // (every user of the scratch is a workspace call)
+    HIPCHK(ctx, ctx->d_track.grow(bytes));
+  }
+  return BRISK_HIP_OK;
+}
+
+int brisk_hip_link_tracks_device(brisk_hip_ctx* ctx, const int* d_node_rows, int node_rows_stride, int nodes, int rows_cap,
+                                 const long long* d_offsets, const brisk_hip_dmatch* d_matches, const brisk_hip_track_seed* seed,
+                                 int* d_prev, long long* d_track, int* d_age, long long* d_summary, void* stream) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (const char* msg = track_chain_check(d_node_rows, node_rows_stride, nodes, rows_cap)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
+  if (nodes > 1 && (!d_offsets || !d_matches)) return fail(ctx, BRISK_HIP_ERR_ARG, "link_tracks: null match lists");
+  if (!d_prev || !d_track || !d_age || !d_summary) return fail(ctx, BRISK_HIP_ERR_ARG, "link_tracks: null output array");
+  if (seed && (!seed->d_track != !seed->d_age)) return fail(ctx, BRISK_HIP_ERR_ARG, "link_tracks: a seed needs both d_track and d_age");
+  if (((uintptr_t)d_matches & 15) || (((uintptr_t)d_offsets | (uintptr_t)d_track | (uintptr_t)d_summary) & 7) ||
+      (((uintptr_t)d_prev | (uintptr_t)d_age) & 3) ||
+      (seed && ((((uintptr_t)seed->d_track | (uintptr_t)seed->d_first_new) & 7) || ((uintptr_t)seed->d_age & 3))))
+    return fail(ctx, BRISK_HIP_ERR_ARG, "link_tracks: d_matches must be 16-byte aligned, the long long arrays 8-byte, the int arrays 4-byte");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  const size_t cells = (size_t)nodes * (size_t)rows_cap, nblk = (size_t)nodes * (size_t)brisk_track_blocks_per_node(rows_cap);
+  TrackScratch L;
+  const size_t at_claims = L.add(cells * 8), at_blk = L.add(nblk * 8), at_counters = L.add(BRISK_TRACK_COUNTERS * 8), at_words = L.add(8);
+  // the context's scratch is written: the stream is ordered behind the previous call's work, the next call behind this one
+  if (workspace_acquire(ctx, st)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
+  WorkspaceGuard guard(ctx, st);
+  if (int rc = track_scratch_grow(ctx, L.bytes)) return rc;
+  char* base = ctx->d_track.as<char>();
+  brisk_launch_track_link(d_node_rows, node_rows_stride, nodes, rows_cap, d_offsets, reinterpret_cast<const BriskDMatch*>(d_matches),
+                          seed ? seed->d_track : nullptr, seed ? seed->d_age : nullptr, seed ? seed->first_new : 0,
+                          seed ? seed->d_first_new : nullptr, reinterpret_cast<unsigned long long*>(base + at_claims),
+                          reinterpret_cast<long long*>(base + at_blk), reinterpret_cast<unsigned long long*>(base + at_counters),
+                          reinterpret_cast<long long*>(base + at_words), d_prev, d_track, d_age, d_summary, st);
+  HIPCHK(ctx, hipGetLastError());
+  if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
+  return BRISK_HIP_OK;
+}
+
+int brisk_hip_list_tracks_device(brisk_hip_ctx* ctx, const int* d_node_rows, int node_rows_stride, int nodes, int rows_cap,
+                                 const int* d_prev, const long long* d_track, const int* d_age, int min_len, long long tracks_cap,
+                                 long long obs_cap, long long* d_list_track, int* d_list_len, long long* d_list_offsets,
+                                 brisk_hip_track_obs* d_list_obs, long long* d_summary, void* stream) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (const char* msg = track_chain_check(d_node_rows, node_rows_stride, nodes, rows_cap)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
+  if (min_len < 1 || tracks_cap < 0 || obs_cap < 0) return fail(ctx, BRISK_HIP_ERR_ARG, "list_tracks: min_len below 1, or a negative capacity");
+  if (!d_prev || !d_track || !d_age) return fail(ctx, BRISK_HIP_ERR_ARG, "list_tracks: null track arrays");
+  if (!d_list_offsets || !d_summary || (tracks_cap > 0 && (!d_list_track || !d_list_len)) || (obs_cap > 0 && !d_list_obs))
+    return fail(ctx, BRISK_HIP_ERR_ARG, "list_tracks: null output array");
+  if ((((uintptr_t)d_track | (uintptr_t)d_list_track | (uintptr_t)d_list_offsets | (uintptr_t)d_list_obs | (uintptr_t)d_summary) & 7) ||
+      (((uintptr_t)d_prev | (uintptr_t)d_age | (uintptr_t)d_list_len) & 3))
+    return fail(ctx, BRISK_HIP_ERR_ARG, "list_tracks: the long long arrays and d_list_obs must be 8-byte aligned, the int arrays 4-byte");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  const size_t cells = (size_t)nodes * (size_t)rows_cap, nblk = (size_t)nodes * (size_t)brisk_track_blocks_per_node(rows_cap);
+  TrackScratch L;
+  const size_t at_piece = L.add(cells * 8), at_next = L.add(cells * 4), at_len = L.add(cells * 4), at_bp = L.add(nblk * 8),
+               at_bo = L.add(nblk * 8), at_words = L.add(16);
+  if (workspace_acquire(ctx, st)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
+  WorkspaceGuard guard(ctx, st);
+  if (int rc = track_scratch_grow(ctx, L.bytes)) return rc;
+  char* base = ctx->d_track.as<char>();
+  brisk_launch_track_list(d_node_rows, node_rows_stride, nodes, rows_cap, d_prev, d_track, d_age, min_len, tracks_cap, obs_cap,
+                          reinterpret_cast<int*>(base + at_next), reinterpret_cast<int*>(base + at_len),
+                          reinterpret_cast<long long*>(base + at_piece), reinterpret_cast<long long*>(base + at_bp),
+                          reinterpret_cast<long long*>(base + at_bo), reinterpret_cast<long long*>(base + at_words), d_list_track, d_list_len,
+                          d_list_offsets, d_list_obs, d_summary, st);
+  HIPCHK(ctx, hipGetLastError());
   if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
   return BRISK_HIP_OK;
 }

@@ -5,6 +5,7 @@
 #include "brisk_common.h"
 #include "brisk_match_gate.h"
 #include "brisk_match_select.h"
+#include "brisk_track_link.h"
 
 #define BRISK_DETECT_TILE_W 64
 #ifndef BRISK_DETECT_ROWS_PER_THREAD
@@ -201,6 +202,26 @@ void brisk_launch_pair_select(const BriskDMatch* out, const int* out_count, cons
 void brisk_launch_pair_select_egress(const int* s_rows, const int* s_counts, const int* s_flags, const long long* s_offsets,
                                      const BriskDMatch* s_matches, int npairs, int* h_rows, int* h_counts, int* h_flags, long long* h_offsets,
                                      void* h_matches, hipStream_t s);
+
+// ---- a batch's pair matches linked into feature tracks (brisk_track.hip; the rule: brisk_track_link.h) ----
+enum { BRISK_TRACK_C_LINKS = 0, BRISK_TRACK_C_LOST = 1, BRISK_TRACK_C_IGNORED = 2, BRISK_TRACK_COUNTERS = 4 };  // the link call's counters
+enum { BRISK_TRACK_LIST_CUT = 1 };  // flag bit 0 of the list's summary (mirrors BRISK_HIP_TRACKS_CUT)
+int brisk_track_blocks_per_node(int rows_cap);
+// node i has node_rows[i * stride] rows; offsets [nodes] / matches: the packed lists of the nodes - 1 pairs (pair p: query node p + 1,
+// train node p).  Scratch: claims [nodes * rows_cap] (cleared here), blk [nodes * blocks_per_node], counters [BRISK_TRACK_COUNTERS],
+// words [1].  seed_track / seed_age [rows_cap] or both NULL; d_first_new NULL = first_new.  prev / track / age [nodes][rows_cap],
+// summary [8]
+void brisk_launch_track_link(const int* node_rows, long long stride, int nodes, int rows_cap, const long long* offsets, const BriskDMatch* matches,
+                             const long long* seed_track, const int* seed_age, long long first_new, const long long* d_first_new,
+                             unsigned long long* claims, long long* blk, unsigned long long* counters, long long* words, int* prev,
+                             long long* track, int* age, long long* summary, hipStream_t s);
+// prev / track / age: what brisk_launch_track_link wrote for this chain.  Scratch: next, len [nodes * rows_cap] ints, piece as many
+// long long, blk_pieces / blk_obs [nodes * blocks_per_node], words [2].  list_track / list_len [tracks_cap], list_offsets
+// [tracks_cap + 1], list_obs [obs_cap] x {int node, int row}, summary [4]
+void brisk_launch_track_list(const int* node_rows, long long stride, int nodes, int rows_cap, const int* prev, const long long* track,
+                             const int* age, int min_len, long long tracks_cap, long long obs_cap, int* next, int* len, long long* piece,
+                             long long* blk_pieces, long long* blk_obs, long long* words, long long* list_track, int* list_len,
+                             long long* list_offsets, void* list_obs, long long* summary, hipStream_t s);
 
 // ---- uniformity enforcement / keypoint bucketing (brisk_uniformity.hip): optional post-filters of the detector's keypoints ----
 void brisk_launch_bucketing(BriskKeyPoint* kp, BriskFrameCounters* counters, int* order, BriskKeyPoint* tmp, int kp_cap, int rows,

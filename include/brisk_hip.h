@@ -575,6 +575,75 @@ int brisk_hip_pair_matches_download(brisk_hip_ctx* ctx, const brisk_hip_dmatch* 
  * BRISK_HIP_ERR_CAPACITY when a pair carries BRISK_HIP_ROWS_CUT (the other flags are information, not errors). */
 int brisk_hip_pair_matches_wait(brisk_hip_ctx* ctx, unsigned ticket, int* pairs_flagged);
 
+/* ---- a batch's pair matches linked into feature tracks, on the device ----------------------------------------------------------
+ * What every consumer of a frame-to-previous-frame matcher does next: "row q of frame i matched row t of frame i - 1" becomes
+ * tracks - which keypoints are the same point seen again, since when, which tracks are long enough to use.  An integer problem
+ * with an exact answer; csrc/brisk_track_link.h is the one definition of the rule.
+ * THE CHAIN: `nodes` >= 1 frames in time order.  Node i has n_i = d_node_rows[i * node_rows_stride] rows (DEVICE memory); with a
+ * brisk_hip_desc_set and the frames first + i * step: d_node_rows = d_counts + first * count_stride, node_rows_stride = step *
+ * count_stride (a mono stream: step 1; one camera of an interleaved stereo stream: step 2).  Only the rows r < lim_i =
+ * min(max(n_i, 0), rows_cap) exist.  Pair p (0 <= p < nodes - 1) has node p + 1 as query and node p as train - what the pair spec
+ * {nodes - 1, first + step, step, first, step, NULL} gives the matchers - and its matches are the records
+ * d_matches[d_offsets[p] .. d_offsets[p + 1]) as brisk_hip_select_pair_matches_device writes them: in (query row, rank) order, a
+ * pair cut at matches_cap with an empty range.  (The d_pairs form of a pair spec is no chain.)
+ * THE RULE.  Record j of pair p is a PROPOSAL iff it is the first record of its query row (j is the first of the pair's range, or
+ * record j - 1 has another queryIdx), 0 <= queryIdx < lim_{p+1}, 0 <= trainIdx < lim_p, and the bit pattern of its distance, read
+ * as u32, is <= 0x7F800000 (no NaN, no sign bit).  Every other record is ignored (and counted): a row proposes with its best entry
+ * only, and a row that loses does not fall back to its second.  Among the proposals for one train row t the smallest 64-bit key
+ * (distance bits << 32 | queryIdx) WINS - for such floats the bit order is the numeric order, ties go to the smaller query row:
+ * the winner q gets prev[p + 1][q] = t, every other row of node p + 1 and every row of node 0 gets -1.  (Cross-checked k = 1 lists:
+ * every proposal wins.)  If one query row's records are not contiguous in a list, the result for that row is unspecified; every
+ * access stays inside the arrays.
+ * A row with prev == -1 is a HEAD, a row with prev >= 0 an interior row: its track is its predecessor's, its age its predecessor's
+ * + 1.  A head of node 0 with a seed d_track[r] >= 0 continues that track at age d_age[r]; every other head STARTS a track at age
+ * 0, numbered first_new + the starting heads before it in (node, row) order.  Track numbers are 64-bit.
+ * SPLITTING: a chain split at node m into two calls gives the numbers and ages of the single call when the second call's node 0 is
+ * the first call's node m, seeded with that call's track / age rows of node m and with its next_new. */
+typedef struct brisk_hip_track_seed {
+  const long long* d_track;      /* [rows_cap] DEVICE: the track row r of node 0 continues, < 0 = none; NULL (with d_age) = no seeds */
+  const int* d_age;              /* [rows_cap] DEVICE: its age */
+  long long first_new;           /* the first number this call may give ... */
+  const long long* d_first_new;  /* ... taken from this DEVICE word instead when non-NULL (the previous call's d_summary: no synchronisation) */
+} brisk_hip_track_seed;
+/* Outputs, all in caller-provided DEVICE memory, padded like the matchers' arrays: d_prev [nodes][rows_cap] int, d_track
+ * [nodes][rows_cap] long long, d_age [nodes][rows_cap] int - only rows r < lim_i are written, everything else is left untouched -
+ * and d_summary, eight long long:
+ *   [0] next_new, the first number the next call may give   [1] tracks started   [2] links (winners)   [3] proposals that lost
+ *   [4] records ignored   [5] observations (the sum of lim_i)   [6] 0   [7] 0
+ * seed NULL = no seeds, first_new 0.  The seed arrays must not overlap this call's outputs, with one exception: d_first_new may
+ * be this call's own d_summary (it is read before the summary is written).
+ * Asynchronous on `stream` (hipStream_t, NULL = the context's stream), no host synchronisation, no allocation per call once the
+ * context's scratch has grown to the call's size (a 64-bit claim word per row of the chain, cleared by the call itself, and
+ * nodes x ceil(rows_cap / 256) sums).  BRISK_HIP_ERR_ARG, before anything is launched: nodes < 1, rows_cap < 1, node_rows_stride < 1,
+ * a NULL array (d_offsets and d_matches may be NULL when nodes == 1: there are no pairs and every row is a head; a seed needs both
+ * of d_track and d_age or neither), a misaligned array (d_matches 16-byte, the long long arrays 8-byte, the int arrays 4-byte). */
+int brisk_hip_link_tracks_device(brisk_hip_ctx* ctx, const int* d_node_rows, int node_rows_stride, int nodes, int rows_cap,
+                                 const long long* d_offsets, const brisk_hip_dmatch* d_matches, const brisk_hip_track_seed* seed,
+                                 int* d_prev, long long* d_track, int* d_age, long long* d_summary, void* stream);
+/* Packs the tracks worth keeping.  A track PIECE is a head and the rows that follow it in this call; it is LISTED iff (the age of
+ * its last row + 1) >= min_len - a continued track counts its length before the call.  Listed pieces are stored in (node, row)
+ * order of their heads, each piece's observations in node order: exact prefix sums, stable compaction, no atomics.
+ *   d_list_track   [tracks_cap]      the piece's track number
+ *   d_list_len     [tracks_cap]      the age of its last row + 1
+ *   d_list_offsets [tracks_cap + 1]  exclusive prefix sums of the in-call observation counts
+ *   d_list_obs     [obs_cap]         the observations
+ *   d_summary      four long long:   pieces listed, their observations, pieces stored, flags
+ * The first piece that does not fit tracks_cap or obs_cap is cut together with every piece behind it (the cut
+ * brisk_hip_select_pair_matches_device makes): the true counts are still reported, nothing of the cut pieces is stored,
+ * d_list_offsets[stored] = the observations stored, BRISK_HIP_TRACKS_CUT is set in the flags.  Nothing behind the stored counts is
+ * written.  d_prev / d_track / d_age: what brisk_hip_link_tracks_device wrote for this chain.  Asynchronous and allocation-free
+ * like it (scratch: 16 bytes per row of the chain).  BRISK_HIP_ERR_ARG, before anything is launched: the chain's errors, min_len <
+ * 1, a negative capacity, a NULL or misaligned array (d_list_obs 8-byte; it may be NULL when obs_cap == 0, d_list_track and
+ * d_list_len when tracks_cap == 0). */
+typedef struct brisk_hip_track_obs {
+  int node, row;
+} brisk_hip_track_obs;
+#define BRISK_HIP_TRACKS_CUT 0x1
+int brisk_hip_list_tracks_device(brisk_hip_ctx* ctx, const int* d_node_rows, int node_rows_stride, int nodes, int rows_cap,
+                                 const int* d_prev, const long long* d_track, const int* d_age, int min_len, long long tracks_cap,
+                                 long long obs_cap, long long* d_list_track, int* d_list_len, long long* d_list_offsets,
+                                 brisk_hip_track_obs* d_list_obs, long long* d_summary, void* stream);
+
 /* ---- per-stage timing: HIP events recorded on the launch stream around every kernel of the batch path ---- */
 int brisk_hip_profile_enable(brisk_hip_ctx* ctx, int enable);       /* resets the accumulated calls */
 int brisk_hip_profile_stages(void);                                 /* number of stages */

@@ -32,6 +32,13 @@ With --export (k-NN only, profiles/match_pairs_export.json) the cost of getting 
   D  B + a plain asynchronous device-to-host copy of the three padded arrays (at --rows-cap) on a copy stream, two device triples
      and two pinned destinations alternating - what a caller could do without the packed exit
 plus the bytes E and D move per batch and the share of query rows whose match is selected.
+With --tracks (k-NN only, profiles/track_pairs.json) what linking the matches into feature tracks adds, two windows:
+  B  detect_describe_batch + match_knn_pairs + select_pair_matches (ratio 0.8, best match per row) on the same stream
+  T  B + brisk_hip_link_tracks_device + brisk_hip_list_tracks_device (min_len 3) on the same stream, every batch numbered on from
+     the one before through d_first_new (the call's own summary word: no synchronisation)
+plus the HIP-event time of the link call and of the list call (six launches each; a `rocprofv3 --kernel-trace --stats` pass
+around --tracks --stats-pass gives the single kernels: profiles/track_pairs_kernel_stats.csv), tracks and links per batch, and
+whether the device's arrays equal a host restatement of the rule on the downloaded lists of one batch.
 Usage: python tools/bench_match_pairs.py [--repeats 5] [--window 0.4] [--rows-cap 2048] [--radius R [--cap N]] [--gate ...] [--out FILE]
        --stats-pass: warm-up + a few B iterations (with --gate: B, G and I) only, nothing written (the run a
        `rocprofv3 --kernel-trace --stats` pass wraps; its kernel statistics are kept as profiles/match_pairs_kernel_stats.csv)"""
@@ -180,6 +187,134 @@ def export_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, batch, run_b):
     ctx.close()
 
 
+def tracks_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
+    """--tracks: windows B and T (see the module's text); writes a.out"""
+    from test_abi_tracks import restated_link, restated_list, SENT32
+    st = work.cuda_stream
+    select = B.MatchSelect(float("inf"), 0.8, 1)
+    L, h = ctx._L, ctx._h
+    mcap = (n - 1) * cap                                            # (one match per row at the most)
+    sel = (torch.zeros((mcap, 4), dtype=torch.int32, device=dev), torch.zeros(n - 1, dtype=torch.int32, device=dev),
+           torch.zeros(n - 1, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int64, device=dev))
+    prev, age = (torch.zeros((n, cap), dtype=torch.int32, device=dev) for _ in range(2))
+    track = torch.zeros((n, cap), dtype=torch.int64, device=dev)
+    summary = torch.zeros(8, dtype=torch.int64, device=dev)
+    tcap, ocap = n * cap // 4, n * cap
+    lists = (torch.zeros(tcap, dtype=torch.int64, device=dev), torch.zeros(tcap, dtype=torch.int32, device=dev),
+             torch.zeros(tcap + 1, dtype=torch.int64, device=dev), torch.zeros((ocap, 2), dtype=torch.int32, device=dev),
+             torch.zeros(4, dtype=torch.int64, device=dev))
+    seed = B.TrackSeed(None, None, 0, summary.data_ptr())           # numbered on from the call before
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+    m, cnt, rows = outs["B"]
+
+    def run_b():
+        run_b0()
+        ctx.check(L.brisk_hip_select_pair_matches_device(h, m.data_ptr(), cnt.data_ptr(), rows.data_ptr(), n - 1, cap, k, C.byref(select), mcap,
+                                                         sel[1].data_ptr(), sel[2].data_ptr(), sel[3].data_ptr(), sel[0].data_ptr(), st))
+
+    def run_t(timed=False):
+        run_b()
+        dset, _ = ctx.batch_desc_set()
+        ptr, stride = ctx._node_rows((dset, 0, 1))
+        if timed:
+            ev[0].record(work)
+        ctx.check(L.brisk_hip_link_tracks_device(h, ptr, stride, n, cap, sel[3].data_ptr(), sel[0].data_ptr(), C.byref(seed), prev.data_ptr(),
+                                                 track.data_ptr(), age.data_ptr(), summary.data_ptr(), st))
+        if timed:
+            ev[1].record(work)
+        ctx.check(L.brisk_hip_list_tracks_device(h, ptr, stride, n, cap, prev.data_ptr(), track.data_ptr(), age.data_ptr(), 3, tcap, ocap,
+                                                 lists[0].data_ptr(), lists[1].data_ptr(), lists[2].data_ptr(), lists[3].data_ptr(),
+                                                 lists[4].data_ptr(), st))
+        if timed:
+            ev[2].record(work)
+
+    runs = {"B": run_b, "T": run_t}
+    order = "BT"
+    for v in order + "BT":                                          # warm-up: buffers sized, scratch grown
+        runs[v]()
+        torch.cuda.synchronize()
+    if a.stats_pass:
+        for _ in range(8):
+            run_t()
+        torch.cuda.synchronize()
+        return
+
+    # one batch against the restatement of the rule on its downloaded lists
+    summary.zero_()
+    run_t()
+    torch.cuda.synchronize()
+    dset, _ = ctx.batch_desc_set()
+    ints = dset.count_stride
+    node_rows = torch.as_tensor(DeviceInts(dset.d_counts, (n - 1) * ints + 1), device=dev)[::ints].cpu().numpy()
+    want = restated_link(node_rows, cap, sel[3].cpu().numpy(), sel[0].cpu().numpy().view(B.DMATCH).reshape(-1))
+    wrote = want[0] != SENT32
+    got = [t.cpu().numpy() for t in (prev, track, age, summary)]
+    identical = all(np.array_equal(g[wrote], w[wrote]) for g, w in zip(got[:3], want[:3])) and got[3].tolist() == want[3].tolist()
+    wl = restated_list(node_rows, cap, *want[:3], 3, tcap, ocap)
+    gl = [t.cpu().numpy() for t in lists]
+    stored, sobs = int(wl[4][2]), int(wl[2][-1])
+    identical = bool(identical and gl[4].tolist() == wl[4].tolist() and gl[0][:stored].tobytes() == wl[0].tobytes() and
+                     gl[1][:stored].tobytes() == wl[1].tobytes() and gl[2][:stored + 1].tobytes() == wl[2].tobytes() and
+                     gl[3][:sobs].tobytes() == wl[3].tobytes())
+    lens = wl[1]
+
+    call_ms = {"link": [], "list": []}
+    for _ in range(max(a.repeats, 5)):
+        run_t(timed=True)
+        torch.cuda.synchronize()
+        call_ms["link"].append(ev[0].elapsed_time(ev[1]))
+        call_ms["list"].append(ev[1].elapsed_time(ev[2]))
+
+    fps = {v: [] for v in order}
+    for _ in range(a.repeats):
+        for v in order:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            calls = 0
+            while True:
+                runs[v]()
+                calls += 1
+                if time.perf_counter() - t0 >= a.window:
+                    break
+            torch.cuda.synchronize()
+            fps[v].append(calls * n / (time.perf_counter() - t0))
+    med = {v: float(np.median(fps[v])) for v in order}
+    ms = {v: 1e3 * n / med[v] for v in order}
+    spread = {v: (max(fps[v]) - min(fps[v])) / med[v] for v in order}
+    res = {
+        "workload": "bench.py's stream: %dx%d, threshold %d, %d octaves, %d frames per batch (%d distinct) in HBM; frame-to-previous-frame, "
+                    "k = %d, rows_cap %d, ratio 0.8, one match per row; tracks of min_len 3, tracks_cap %d, obs_cap %d"
+                    % (W, H, THRESHOLD, OCTAVES, n, nd, k, cap, tcap, ocap),
+        "kernel_revision": ctx.kernel_revision(),
+        "device": torch.cuda.get_device_name(0),
+        "windows": {"repeats": a.repeats, "seconds_each": a.window, "order": ", ".join(order) + " alternating; every window ends in a synchronise"},
+        "frames_per_s": {v: round(med[v], 1) for v in order},
+        "frames_per_s_all": {v: [round(x, 1) for x in fps[v]] for v in order},
+        "spread_rel": {v: round(spread[v], 4) for v in order},
+        "ms_per_batch": {v: round(ms[v], 4) for v in order},
+        "tracking_ms_per_batch": {"T_minus_B": round(ms["T"] - ms["B"], 4)},
+        "T_over_B_frames_per_s": round(med["T"] / med["B"], 4),
+        "hip_event_ms": {"link_call_6_launches": {"median": round(float(np.median(call_ms["link"])), 4), "all": [round(x, 4) for x in call_ms["link"]]},
+                         "list_call_6_launches": {"median": round(float(np.median(call_ms["list"])), 4), "all": [round(x, 4) for x in call_ms["list"]]}},
+        "chain_walk": "a walk from each head along the forward pointers (the only form built): nodes - 1 = %d dependent loads on the longest "
+                      "possible track" % (n - 1),
+        "per_batch": {"nodes": n, "observations": int(want[3][5]), "tracks_started": int(want[3][1]), "links": int(want[3][2]),
+                      "proposals_lost": int(want[3][3]), "records_ignored": int(want[3][4]), "tracks_listed_min_len_3": int(wl[4][0]),
+                      "their_observations": int(wl[4][1]), "longest_track": int(lens.max()) if len(lens) else 0,
+                      "list_cut": bool(wl[4][3])},
+        "T_equals_the_restated_rule": identical,
+        "legend": {"B": "detect_describe_batch + brisk_hip_match_knn_pairs_device + brisk_hip_select_pair_matches_device on one stream",
+                   "T": "B + brisk_hip_link_tracks_device + brisk_hip_list_tracks_device on the same stream"},
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+    ext.close()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=512)
@@ -195,6 +330,7 @@ def main():
                                                 "with --gate the same names ending in _gated.json")
     ap.add_argument("--stats-pass", action="store_true")
     ap.add_argument("--export", action="store_true", help="windows B, E (packed, selected matches to the host) and D (padded arrays to the host)")
+    ap.add_argument("--tracks", action="store_true", help="windows B (match + select) and T (B + link_tracks + list_tracks)")
     a = ap.parse_args()
 
     radius = a.radius
@@ -207,6 +343,11 @@ def main():
             ap.error("--export measures the k-NN pair call: without --radius / --gate")
         if a.out is None:
             a.out = os.path.join(ROOT, "profiles", "match_pairs_export.json")
+    if a.tracks:
+        if radius is not None or gate or a.export:
+            ap.error("--tracks measures the k-NN pair call: without --radius / --gate / --export")
+        if a.out is None:
+            a.out = os.path.join(ROOT, "profiles", "track_pairs.json")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", ("match_radius_pairs" if radius is not None else "match_pairs") +
                              ("_gated" if gate else "") + ".json")
@@ -254,6 +395,9 @@ def main():
 
     if a.export:
         export_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, batch, run_b)
+        return
+    if a.tracks:
+        tracks_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b)
         return
 
     vp = C.c_void_p
