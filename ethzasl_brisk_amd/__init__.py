@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "brisk_hip_batch_kp_set", "brisk_hip_match_knn_pairs_gated_device", "brisk_hip_match_radius_pairs_gated_device",
     "brisk_hip_select_pair_matches_device", "brisk_hip_pair_matches_download", "brisk_hip_pair_matches_wait",
     "brisk_hip_link_tracks_device", "brisk_hip_list_tracks_device",
+    "brisk_hip_track_points_device", "brisk_hip_tracks_download", "brisk_hip_tracks_wait",
 ]
 # every symbol include/brisk_hip_debug.h declares: test / tuning builds (BRISK_HIP_TUNING) only
 DEBUG_SYMBOLS = [
@@ -122,6 +123,14 @@ class TrackSeed(C.Structure):
 
 TRACK_OBS = np.dtype([("node", "<i4"), ("row", "<i4")])   # brisk_hip_track_obs
 TRACKS_CUT = 1                                              # flag bit 0 of list_tracks' summary
+# brisk_hip_track_point: an observation and the keypoint it names, byte-identical to the source record
+TRACK_POINT = np.dtype([("node", "<i4"), ("row", "<i4")] + [(n, KEYPOINT.fields[n][0]) for n in KEYPOINT.names])
+
+
+class HostTracks(C.Structure):
+    """brisk_hip_host_tracks: capacities + the five destination arrays of a batch's listed tracks in host memory"""
+    _fields_ = [("tracks_cap", C.c_longlong), ("points_cap", C.c_longlong), ("summary", C.c_void_p), ("track", C.c_void_p),
+                ("len", C.c_void_p), ("offsets", C.c_void_p), ("points", C.c_void_p)]
 
 
 # flags of a pair in the selected lists (ROWS_CUT: the pair and every pair behind it did not fit matches_cap)
@@ -157,6 +166,30 @@ class HostMatches:
     def pair(self, p):
         """the selected matches of pair p, in (query row, rank) order: a view of the records [offsets[p], offsets[p + 1])"""
         return self.matches[int(self.offsets[p]):int(self.offsets[p + 1])]
+
+
+class HostTrackList:
+    """Destination arrays of brisk_hip_tracks_download: `tracks` pieces, `points` TRACK_POINT records in total; summary = pieces
+    listed, their observations, pieces stored, flags.  pinned as in HostResults."""
+
+    def __init__(self, tracks, points, pinned=True):
+        self.tracks_cap, self.points_cap = int(tracks), int(points)
+        self._keep = []
+        self.summary = _host_array(4, np.int64, pinned, self._keep)
+        self.track = _host_array(tracks, np.int64, pinned, self._keep)
+        self.len = _host_array(tracks, np.int32, pinned, self._keep)
+        self.offsets = _host_array(tracks + 1, np.int64, pinned, self._keep)
+        self.points = _host_array(points, TRACK_POINT, pinned, self._keep)
+        self.struct = HostTracks(self.tracks_cap, self.points_cap, self.summary.ctypes.data, self.track.ctypes.data, self.len.ctypes.data,
+                                 self.offsets.ctypes.data, self.points.ctypes.data)
+
+    @property
+    def stored(self):
+        return int(self.summary[2])
+
+    def piece(self, i):
+        """(track number, length, points) of stored piece i: the points a view of the records [offsets[i], offsets[i + 1])"""
+        return int(self.track[i]), int(self.len[i]), self.points[int(self.offsets[i]):int(self.offsets[i + 1])]
 
 
 class HostResults:
@@ -288,6 +321,11 @@ def load_library():
     L.brisk_hip_link_tracks_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(TrackSeed), vp, vp, vp, vp, vp]
     L.brisk_hip_list_tracks_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_longlong, C.c_longlong,
                                                vp, vp, vp, vp, vp, vp]
+    L.brisk_hip_track_points_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_longlong, C.POINTER(KpSet), C.c_int,
+                                                C.c_int, vp, vp]
+    L.brisk_hip_tracks_download.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.POINTER(KpSet), C.c_int, C.c_int,
+                                            C.POINTER(HostTracks), vp, C.POINTER(C.c_uint)]
+    L.brisk_hip_tracks_wait.argtypes = [vp, C.c_uint, ip]
     L.brisk_hip_reserve.argtypes = [vp, C.c_int, C.c_int]
     L.brisk_hip_detect_uniform.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
                                            C.c_double, C.c_int, vp, C.c_int, ip]
@@ -743,6 +781,44 @@ class Context:
                                                         res[1].data_ptr(), res[2].data_ptr(), res[3].data_ptr(), res[4].data_ptr(),
                                                         C.c_void_p(stream) if stream else None))
         return res
+
+    # -- the tracker's exit: the listed tracks with their keypoints --
+    def track_points(self, node_rows, nodes, rows_cap, list_offsets, list_obs, list_summary, kps=None, kp_first=0, kp_step=1, stream=None):
+        """brisk_hip_track_points_device on what list_tracks returned (list_offsets, list_obs, list_summary).  kps: a KpSet (None =
+        the last batch's); node i's keypoints are frame kp_first + i * kp_step of it.  Returns the device tensor points [obs_cap, 9]
+        int32 - TRACK_POINT records -; only the points of the stored observations are written.  Asynchronous on `stream`."""
+        import torch
+        ptr, stride = self._node_rows(node_rows)
+        if kps is None:
+            kps = self.batch_kp_set()
+        cap = int(list_obs.shape[0])
+        points = torch.empty((cap, 9), dtype=torch.int32, device=list_obs.device)
+        self.check(self._L.brisk_hip_track_points_device(self._h, ptr, stride, int(nodes), int(rows_cap), list_offsets.data_ptr(),
+                                                         list_obs.data_ptr(), list_summary.data_ptr(), cap, C.byref(kps), int(kp_first),
+                                                         int(kp_step), points.data_ptr(), C.c_void_p(stream) if stream else None))
+        return points
+
+    def tracks_download(self, node_rows, nodes, rows_cap, prev, track, age, min_len, dst, kps=None, kp_first=0, kp_step=1, stream=None):
+        """brisk_hip_tracks_download: list + points + transfer of what link_tracks returned into `dst` (HostTrackList) queued on
+        `stream` (the stream link_tracks ran on); prev / track / age and the keypoints may be overwritten by the next batch in
+        stream order.  kps / kp_first / kp_step as in track_points.  Returns the ticket."""
+        ptr, stride = self._node_rows(node_rows)
+        if kps is None:
+            kps = self.batch_kp_set()
+        t = C.c_uint()
+        self.check(self._L.brisk_hip_tracks_download(self._h, ptr, stride, int(nodes), int(rows_cap), prev.data_ptr(), track.data_ptr(),
+                                                     age.data_ptr(), int(min_len), C.byref(kps), int(kp_first), int(kp_step),
+                                                     C.byref(dst.struct), C.c_void_p(stream) if stream else None, C.byref(t)))
+        return t.value
+
+    def tracks_wait(self, ticket, check=True):
+        """completes transfer `ticket`; returns 1 when the list was cut, else 0 (check=False: (rc, cut) instead of raising)"""
+        n = C.c_int()
+        rc = self._L.brisk_hip_tracks_wait(self._h, ticket, C.byref(n))
+        if not check:
+            return rc, n.value
+        self.check(rc)
+        return n.value
 
     def match_radius_device(self, d_query, nq, q_pitch, d_train, nt, t_pitch, dim_bytes, max_distance, cap_per_query, d_out, d_out_count,
                             stream=None):

@@ -36,6 +36,13 @@ struct brisk_hip_pattern {
   void* blob;           // single device allocation backing dev.*
 };
 
+// what a transfer of brisk_hip_tracks_download keeps of its arrays: the destination struct, and the summary's flags word as the int
+// array of one entry transfer_finish reads (the low half of summary[3]: the flags fit 32 bits, the host is little-endian)
+struct TrackTransfer {
+  brisk_hip_host_tracks a;
+  const int* flags;
+};
+
 struct brisk_hip_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -140,6 +147,7 @@ struct brisk_hip_ctx {
   // the two exits to host memory: each keeps two transfers in flight and issues its own tickets (brisk_transfer.h)
   TransferRing<brisk_hip_batch_host_results> ex;  // brisk_hip_batch_download_all
   TransferRing<brisk_hip_pair_host_matches> mx;   // brisk_hip_pair_matches_download
+  TransferRing<TrackTransfer> tx;                 // brisk_hip_tracks_download
   hipStream_t egress = nullptr;
   DeviceBuf d_select;  // brisk_hip_select_pair_matches_device / _pair_matches_download: the per-workgroup sums of the selection passes
   DeviceBuf d_track;   // brisk_hip_link_tracks_device / _list_tracks_device: claim words, forward pointers, piece words, workgroup sums
@@ -492,6 +500,7 @@ void brisk_hip_destroy(brisk_hip_ctx* c) {
   if (c->copy_stream) hipStreamDestroy(c->copy_stream);
   c->ex.destroy_events();
   c->mx.destroy_events();
+  c->tx.destroy_events();
   if (c->egress) hipStreamDestroy(c->egress);
   brisk_prof_destroy(&c->prof);
   if (c->side) { hipStreamDestroy(c->side); hipEventDestroy(c->side_fork); hipEventDestroy(c->side_join); }
@@ -2190,6 +2199,26 @@ int brisk_hip_link_tracks_device(brisk_hip_ctx* ctx, const int* d_node_rows, int
   return BRISK_HIP_OK;
 }
 
+// the six kernels of the list call on st (checked arguments, the workspace acquired): the context's scratch grown to the call's size
+static int list_launch(brisk_hip_ctx* ctx, const int* d_node_rows, int node_rows_stride, int nodes, int rows_cap, const int* d_prev,
+                       const long long* d_track, const int* d_age, int min_len, long long tracks_cap, long long obs_cap,
+                       long long* d_list_track, int* d_list_len, long long* d_list_offsets, void* d_list_obs, long long* d_summary,
+                       hipStream_t st) {
+  const size_t cells = (size_t)nodes * (size_t)rows_cap, nblk = (size_t)nodes * (size_t)brisk_track_blocks_per_node(rows_cap);
+  TrackScratch L;
+  const size_t at_piece = L.add(cells * 8), at_next = L.add(cells * 4), at_len = L.add(cells * 4), at_bp = L.add(nblk * 8),
+               at_bo = L.add(nblk * 8), at_words = L.add(16);
+  if (int rc = track_scratch_grow(ctx, L.bytes)) return rc;
+  char* base = ctx->d_track.as<char>();
+  brisk_launch_track_list(d_node_rows, node_rows_stride, nodes, rows_cap, d_prev, d_track, d_age, min_len, tracks_cap, obs_cap,
+                          reinterpret_cast<int*>(base + at_next), reinterpret_cast<int*>(base + at_len),
+                          reinterpret_cast<long long*>(base + at_piece), reinterpret_cast<long long*>(base + at_bp),
+                          reinterpret_cast<long long*>(base + at_bo), reinterpret_cast<long long*>(base + at_words), d_list_track, d_list_len,
+                          d_list_offsets, d_list_obs, d_summary, st);
+  HIPCHK(ctx, hipGetLastError());
+  return BRISK_HIP_OK;
+}
+
 int brisk_hip_list_tracks_device(brisk_hip_ctx* ctx, const int* d_node_rows, int node_rows_stride, int nodes, int rows_cap,
                                  const int* d_prev, const long long* d_track, const int* d_age, int min_len, long long tracks_cap,
                                  long long obs_cap, long long* d_list_track, int* d_list_len, long long* d_list_offsets,
@@ -2206,20 +2235,11 @@ int brisk_hip_list_tracks_device(brisk_hip_ctx* ctx, const int* d_node_rows, int
     return fail(ctx, BRISK_HIP_ERR_ARG, "list_tracks: the long long arrays and d_list_obs must be 8-byte aligned, the int arrays 4-byte");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-  const size_t cells = (size_t)nodes * (size_t)rows_cap, nblk = (size_t)nodes * (size_t)brisk_track_blocks_per_node(rows_cap);
-  TrackScratch L;
-  const size_t at_piece = L.add(cells * 8), at_next = L.add(cells * 4), at_len = L.add(cells * 4), at_bp = L.add(nblk * 8),
-               at_bo = L.add(nblk * 8), at_words = L.add(16);
   if (workspace_acquire(ctx, st)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
   WorkspaceGuard guard(ctx, st);
-  if (int rc = track_scratch_grow(ctx, L.bytes)) return rc;
-  char* base = ctx->d_track.as<char>();
-  brisk_launch_track_list(d_node_rows, node_rows_stride, nodes, rows_cap, d_prev, d_track, d_age, min_len, tracks_cap, obs_cap,
-                          reinterpret_cast<int*>(base + at_next), reinterpret_cast<int*>(base + at_len),
-                          reinterpret_cast<long long*>(base + at_piece), reinterpret_cast<long long*>(base + at_bp),
-                          reinterpret_cast<long long*>(base + at_bo), reinterpret_cast<long long*>(base + at_words), d_list_track, d_list_len,
-                          d_list_offsets, d_list_obs, d_summary, st);
-  HIPCHK(ctx, hipGetLastError());
+  if (int rc = list_launch(ctx, d_node_rows, node_rows_stride, nodes, rows_cap, d_prev, d_track, d_age, min_len, tracks_cap, obs_cap,
+                           d_list_track, d_list_len, d_list_offsets, d_list_obs, d_summary, st))
+    return rc;
   if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
   return BRISK_HIP_OK;
 }
@@ -2323,6 +2343,152 @@ int brisk_hip_pair_matches_wait(brisk_hip_ctx* ctx, unsigned ticket, int* pairs_
   if (!ctx) return BRISK_HIP_ERR_ARG;
   std::unique_lock<std::mutex> lk(ctx->mu);
   return ctx->mx.wait(ctx->device, ctx->err, lk, ticket, pairs_flagged, matches_finish, "brisk_hip_pair_matches_wait");
+}
+
+// ---- the tracker's exit: the listed tracks with their keypoints (kernels: brisk_track_export.hip) ------------------------------
+static_assert(sizeof(brisk_hip_track_point) == 36 && alignof(brisk_hip_track_point) == 4 && sizeof(brisk_hip_track_point) == 4 * BRISK_TRACK_POINT_WORDS,
+              "track point layout");
+
+// what both forms check of the keypoints a chain's observations name, before anything is launched
+static const char* track_kps_check(const brisk_hip_kp_set* kps, int nodes, int kp_first, int kp_step) {
+  if (!kps) return "track points: null kps";
+  if (!kps->d_kps || ((uintptr_t)kps->d_kps & 3) || kps->frame_pitch < 0 || kps->frame_pitch % 4)
+    return "track points: d_kps null or not 4-byte aligned, or a frame_pitch that is negative or no multiple of 4";
+  if (kp_first < 0 || (long long)kp_first + (long long)(nodes - 1) * (long long)kp_step < 0)
+    return "track points: kp_first or kp_first + (nodes - 1) * kp_step below 0";
+  return nullptr;
+}
+
+int brisk_hip_track_points_device(brisk_hip_ctx* ctx, const int* d_node_rows, int node_rows_stride, int nodes, int rows_cap,
+                                  const long long* d_list_offsets, const brisk_hip_track_obs* d_list_obs, const long long* d_list_summary,
+                                  long long obs_cap, const brisk_hip_kp_set* kps, int kp_first, int kp_step, brisk_hip_track_point* d_points,
+                                  void* stream) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (const char* msg = track_chain_check(d_node_rows, node_rows_stride, nodes, rows_cap)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
+  if (obs_cap < 0) return fail(ctx, BRISK_HIP_ERR_ARG, "track_points: a negative capacity");
+  if (!d_list_offsets || !d_list_summary || (obs_cap > 0 && (!d_list_obs || !d_points)))
+    return fail(ctx, BRISK_HIP_ERR_ARG, "track_points: null list or point array");
+  if ((((uintptr_t)d_list_offsets | (uintptr_t)d_list_obs | (uintptr_t)d_list_summary) & 7) || ((uintptr_t)d_points & 3))
+    return fail(ctx, BRISK_HIP_ERR_ARG, "track_points: the d_list arrays must be 8-byte aligned, d_points 4-byte");
+  if (const char* msg = track_kps_check(kps, nodes, kp_first, kp_step)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  brisk_launch_tracklist_points(d_node_rows, node_rows_stride, nodes, rows_cap, d_list_offsets, d_list_obs, d_list_summary, obs_cap, kps->d_kps,
+                                kps->frame_pitch, kp_first, kp_step, d_points, st);
+  HIPCHK(ctx, hipGetLastError());
+  return BRISK_HIP_OK;
+}
+
+using TrackSlot = TransferRing<TrackTransfer>::Slot;
+
+// the five arrays of a list of `tracks` pieces and `points` points, in the order a slab and a bounce buffer hold them; a slab holds
+// the list's observations behind them
+static SlabLayout tracks_layout(long long tracks, long long points, bool with_obs) {
+  SlabLayout LY;
+  LY.add(sizeof(long long) * 4);                              // summary
+  LY.add(sizeof(long long) * (size_t)tracks);                 // track
+  LY.add(sizeof(int) * (size_t)tracks);                       // len
+  LY.add(sizeof(long long) * ((size_t)tracks + 1));           // offsets
+  LY.add(sizeof(brisk_hip_track_point) * (size_t)points);     // points
+  if (with_obs) LY.add(sizeof(brisk_hip_track_obs) * (size_t)points);
+  return LY;
+}
+static TrackTransfer tracks_at(const SlabLayout& LY, uint8_t* base, long long tracks, long long points) {
+  TrackTransfer T{{tracks, points, LY.at<long long>(base, 0), LY.at<long long>(base, 1), LY.at<int>(base, 2), LY.at<long long>(base, 3),
+                   LY.at<brisk_hip_track_point>(base, 4)},
+                  nullptr};
+  T.flags = reinterpret_cast<const int*>(T.a.summary + 3);
+  return T;
+}
+
+// what transfer_finish leaves to this exit: the copy out of the bounce buffer (a pageable destination) ...
+static void tracks_copy_out(TrackSlot& E) {
+  const brisk_hip_host_tracks& W = E.wr.a;
+  const long long stored = W.summary[2], n = W.offsets[stored];
+  memcpy(E.dst.a.summary, W.summary, sizeof(long long) * 4);
+  if (stored > 0) {
+    memcpy(E.dst.a.track, W.track, sizeof(long long) * (size_t)stored);
+    memcpy(E.dst.a.len, W.len, sizeof(int) * (size_t)stored);
+  }
+  memcpy(E.dst.a.offsets, W.offsets, sizeof(long long) * ((size_t)stored + 1));
+  if (n > 0) memcpy(E.dst.a.points, W.points, sizeof(brisk_hip_track_point) * (size_t)n);
+}
+// ... and the status of a transfer whose flags word is set: a cut list is the one error
+static void tracks_status(TrackSlot& E, int orf) {
+  if (!(orf & BRISK_HIP_TRACKS_CUT)) return;
+  char msg[200];
+  snprintf(msg, sizeof msg, "the list did not fit the destination's tracks_cap / points_cap: %lld of %lld pieces are stored (BRISK_HIP_TRACKS_CUT)",
+           E.wr.a.summary[2], E.wr.a.summary[0]);
+  E.rc = BRISK_HIP_ERR_CAPACITY;
+  E.msg = msg;
+}
+static void tracks_finish(TrackSlot& E) { transfer_finish(E, tracks_copy_out, tracks_status); }
+
+int brisk_hip_tracks_download(brisk_hip_ctx* ctx, const int* d_node_rows, int node_rows_stride, int nodes, int rows_cap,
+                              const int* d_prev, const long long* d_track, const int* d_age, int min_len, const brisk_hip_kp_set* kps,
+                              int kp_first, int kp_step, const brisk_hip_host_tracks* dst, void* stream, unsigned* ticket) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (ticket) *ticket = 0;  // (no ticket is issued by a call that fails, a NULL destination included)
+  if (!dst || !ticket) return fail(ctx, BRISK_HIP_ERR_ARG, "tracks_download: null destination / ticket");
+  if (const char* msg = track_chain_check(d_node_rows, node_rows_stride, nodes, rows_cap)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
+  const long long tcap = dst->tracks_cap, pcap = dst->points_cap;
+  if (min_len < 1 || tcap < 0 || pcap < 0) return fail(ctx, BRISK_HIP_ERR_ARG, "tracks_download: min_len below 1, or a negative capacity");
+  if (!d_prev || !d_track || !d_age) return fail(ctx, BRISK_HIP_ERR_ARG, "tracks_download: null track arrays");
+  if (((uintptr_t)d_track & 7) || (((uintptr_t)d_prev | (uintptr_t)d_age) & 3))
+    return fail(ctx, BRISK_HIP_ERR_ARG, "tracks_download: d_track must be 8-byte aligned, d_prev and d_age 4-byte");
+  if (const char* msg = track_kps_check(kps, nodes, kp_first, kp_step)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
+  if (!dst->summary || !dst->offsets || (tcap > 0 && (!dst->track || !dst->len)) || (pcap > 0 && !dst->points))
+    return fail(ctx, BRISK_HIP_ERR_ARG, "tracks_download: a null summary / track / len / offsets / points array");
+  if ((((uintptr_t)dst->summary | (uintptr_t)dst->track | (uintptr_t)dst->offsets) & 7) || (((uintptr_t)dst->len | (uintptr_t)dst->points) & 3))
+    return fail(ctx, BRISK_HIP_ERR_ARG, "tracks_download: summary, track and offsets must be 8-byte aligned, len and points 4-byte");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream, es = nullptr;
+  if (int rc = egress_stream(ctx, &es)) return rc;
+  const SlabLayout LY = tracks_layout(tcap, pcap, true), LB = tracks_layout(tcap, pcap, false);
+  TrackSlot* slot = nullptr;
+  if (int rc = ctx->tx.open(LY.bytes(), ctx->err, tracks_finish, &slot)) return rc;
+  TrackSlot& E = *slot;
+  // where the egress kernel writes: the caller's arrays when the device can reach all of them, else the bounce buffer
+  HostDst dv[5] = {{dst->summary, true}, {dst->track, tcap != 0}, {dst->len, tcap != 0}, {dst->offsets, true}, {dst->points, pcap != 0}};
+  const bool direct = device_can_write_all(dv);
+  TrackTransfer D{*dst, reinterpret_cast<const int*>(dst->summary + 3)};
+  TrackTransfer W = D, H = D;  // W: device-side addresses for the kernel, H: what the host reads at the wait
+  if (direct) {
+    W.a.summary = static_cast<long long*>(dv[0].p); W.a.track = static_cast<long long*>(dv[1].p); W.a.len = static_cast<int*>(dv[2].p);
+    W.a.offsets = static_cast<long long*>(dv[3].p); W.a.points = static_cast<brisk_hip_track_point*>(dv[4].p);
+  } else {
+    HIPCHK(ctx, E.bounce.grow(LB.bytes()));
+    W = H = tracks_at(LB, E.bounce.as<uint8_t>(), tcap, pcap);
+  }
+  uint8_t* sl = E.slab.as<uint8_t>();
+  const brisk_hip_host_tracks S = tracks_at(LY, sl, tcap, pcap).a;
+  brisk_hip_track_obs* s_obs = LY.at<brisk_hip_track_obs>(sl, 5);
+  if (workspace_acquire(ctx, s)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
+  WorkspaceGuard guard(ctx, s);
+  if (E.done_valid) HIPCHK(ctx, hipStreamWaitEvent(s, E.done, 0));  // the slab's previous transfer
+  if (int rc = list_launch(ctx, d_node_rows, node_rows_stride, nodes, rows_cap, d_prev, d_track, d_age, min_len, tcap, pcap, S.track, S.len,
+                           S.offsets, s_obs, S.summary, s))
+    return rc;
+  brisk_launch_tracklist_points(d_node_rows, node_rows_stride, nodes, rows_cap, S.offsets, s_obs, S.summary, pcap, kps->d_kps, kps->frame_pitch,
+                                kp_first, kp_step, S.points, s);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipEventRecord(E.packed, s));
+  if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
+  HIPCHK(ctx, hipStreamWaitEvent(es, E.packed, 0));
+  brisk_launch_tracklist_egress(S.summary, S.track, S.len, S.offsets, S.points, tcap, pcap, W.a.summary, W.a.track, W.a.len, W.a.offsets,
+                                W.a.points, es);
+  HIPCHK(ctx, hipGetLastError());
+  E.dst = D;
+  E.wr = H;
+  return ctx->tx.close(E, es, !direct, 1, ctx->err, ticket);
+}
+
+int brisk_hip_tracks_wait(brisk_hip_ctx* ctx, unsigned ticket, int* cut) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::unique_lock<std::mutex> lk(ctx->mu);
+  return ctx->tx.wait(ctx->device, ctx->err, lk, ticket, cut, tracks_finish, "brisk_hip_tracks_wait");
 }
 
 int brisk_hip_match_radius_device(brisk_hip_ctx* ctx, const uint8_t* d_query, int nq, int q_pitch, const uint8_t* d_train, int nt,

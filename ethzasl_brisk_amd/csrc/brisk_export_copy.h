@@ -1,5 +1,5 @@
-// The dword copy of the egress kernels (brisk_export.hip: keypoints and descriptors; brisk_match_export.hip: matches): packed device
-// slab -> host memory the device can write, over the link.
+// The dword copy of the egress kernels (brisk_export.hip: keypoints and descriptors; brisk_match_export.hip: matches;
+// brisk_track_export.hip: tracks): packed device slab -> host memory the device can write, over the link.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

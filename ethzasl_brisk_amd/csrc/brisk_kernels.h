@@ -6,6 +6,7 @@
 #include "brisk_match_gate.h"
 #include "brisk_match_select.h"
 #include "brisk_track_link.h"
+#include "brisk_track_points.h"
 
 #define BRISK_DETECT_TILE_W 64
 #ifndef BRISK_DETECT_ROWS_PER_THREAD
@@ -222,6 +223,18 @@ void brisk_launch_track_list(const int* node_rows, long long stride, int nodes, 
                              const int* age, int min_len, long long tracks_cap, long long obs_cap, int* next, int* len, long long* piece,
                              long long* blk_pieces, long long* blk_obs, long long* words, long long* list_track, int* list_len,
                              long long* list_offsets, void* list_obs, long long* summary, hipStream_t s);
+
+// ---- the tracker's exit: the listed tracks with their keypoints (brisk_track_export.hip; the rule: brisk_track_points.h) ----
+// list_offsets / list_obs / list_summary: what brisk_launch_track_list wrote with this obs_cap.  kps: frame f's record r (28 bytes) at
+// kps + f * frame_pitch + r * 28, node i = frame kp_first + i * kp_step.  points [obs_cap] x 36 bytes: {node, row, keypoint}; only
+// the points of the stored observations are written
+void brisk_launch_tracklist_points(const int* node_rows, long long stride, int nodes, int rows_cap, const long long* list_offsets,
+                                   const void* list_obs, const long long* list_summary, long long obs_cap, const void* kps, long long frame_pitch,
+                                   int kp_first, int kp_step, void* points, hipStream_t s);
+// packed lists (each array 16-byte aligned) -> host memory the device can write: the summary and the stored prefixes only
+void brisk_launch_tracklist_egress(const long long* s_summary, const long long* s_track, const int* s_len, const long long* s_offsets,
+                                   const void* s_points, long long tracks_cap, long long points_cap, long long* h_summary, long long* h_track,
+                                   int* h_len, long long* h_offsets, void* h_points, hipStream_t s);
 
 // ---- uniformity enforcement / keypoint bucketing (brisk_uniformity.hip): optional post-filters of the detector's keypoints ----
 void brisk_launch_bucketing(BriskKeyPoint* kp, BriskFrameCounters* counters, int* order, BriskKeyPoint* tmp, int kp_cap, int rows,

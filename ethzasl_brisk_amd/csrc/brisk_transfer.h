@@ -1,5 +1,6 @@
-// brisk_transfer.h - host code only: the asynchronous transfers to host memory behind brisk_hip_batch_download_all and
-// brisk_hip_pair_matches_download - the slot of one transfer, the ring of two an exit keeps in flight, tickets and waits.
+// brisk_transfer.h - host code only: the asynchronous transfers to host memory behind brisk_hip_batch_download_all,
+// brisk_hip_pair_matches_download and brisk_hip_tracks_download - the slot of one transfer, the ring of two an exit keeps in flight,
+// tickets and waits.
 // (No device compiler output depends on this file: build.kernel_revision() leaves it out, like brisk_capi.hip.)
 // A context is not known here: the calls are given its device, its error string and its lock.
 #pragma once
@@ -53,7 +54,8 @@ static bool device_can_write_all(HostDst (&d)[N], bool known_pinned = false) {
 
 // One transfer: pack kernels fill `slab` on the batch's stream (`packed` behind them), an egress kernel on a second stream moves
 // the exact bytes to the host (`done` behind it).  Arrays: the exit's destination struct (brisk_hip_batch_host_results,
-// brisk_hip_pair_host_matches); its int array `flags` has one entry per frame / pair, nonzero = flagged.
+// brisk_hip_pair_host_matches) or a struct around it (the tracks exit's TrackTransfer); its int array `flags` has one entry per
+// frame / pair / list, nonzero = flagged.
 template <class Arrays>
 struct TransferSlot {
   DeviceBuf slab;
@@ -87,8 +89,8 @@ static void transfer_finish(Slot& E, CopyOut copy_out, Status status) {
 }
 
 // The two slots of one exit and its ticket sequence.  Two, so that a stream keeps two batches in flight: the transfer of one runs
-// beside the kernels of the next.  Each exit has its own ring (a stream that downloads rows AND matches still keeps two batches in
-// flight) and its own tickets.  Every call is made with the context's lock held; finish(slot) is the exit's transfer_finish.
+// beside the kernels of the next.  Each exit has its own ring (a stream that downloads rows, matches AND tracks still keeps two
+// batches in flight) and its own tickets.  Every call is made with the context's lock held; finish(slot) is the exit's transfer_finish.
 template <class Arrays>
 struct TransferRing {
   using Slot = TransferSlot<Arrays>;

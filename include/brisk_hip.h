@@ -644,6 +644,62 @@ int brisk_hip_list_tracks_device(brisk_hip_ctx* ctx, const int* d_node_rows, int
                                  long long obs_cap, long long* d_list_track, int* d_list_len, long long* d_list_offsets,
                                  brisk_hip_track_obs* d_list_obs, long long* d_summary, void* stream);
 
+/* ---- the tracker's exit: the listed tracks with their keypoints, on the device or in HOST memory -----------------------------
+ * What a host consumer of tracks needs per track - its number, its length, the image positions it was seen at - and nothing else:
+ * the observations of a list are resolved to their keypoints on the device, and only the listed tracks cross the link.
+ * csrc/brisk_track_points.h is the one definition of the rule.  Point i of a list is observation i of d_list_obs; its kp is the 28
+ * bytes at
+ *   (const char*)kps->d_kps + (size_t)(kp_first + node * kp_step) * kps->frame_pitch + (size_t)row * 28
+ * copied as dwords (NaN payloads and every bit of class_id survive; all address arithmetic is 64-bit).  An observation with node
+ * outside [0, nodes) or row outside [0, lim_node) gets 28 zero bytes, and nothing is read from kps for it.  The caller vouches that
+ * the frames kp_first + i * kp_step, 0 <= i < nodes, exist in kps and hold lim_i records each (a brisk_hip_kp_set carries no frame
+ * count).  With the chain of a descriptor set's frames first + i * step and brisk_hip_batch_kp_set: kp_first = first, kp_step =
+ * step. */
+typedef struct brisk_hip_track_point { /* 36 bytes, 4-byte aligned */
+  int node, row;                       /* the observation, as brisk_hip_track_obs */
+  brisk_hip_keypoint kp;               /* byte-identical to the source record */
+} brisk_hip_track_point;
+/* Device form: the points of a list that brisk_hip_list_tracks_device wrote with this obs_cap.  Writes d_points[0 ..
+ * d_list_offsets[stored]), stored = d_list_summary[2] read on the device, nothing behind it; asynchronous on `stream`, no scratch,
+ * no allocation.  BRISK_HIP_ERR_ARG, before anything is launched: the chain's errors, obs_cap < 0, a NULL d_list_offsets /
+ * d_list_summary, a NULL d_list_obs / d_points with obs_cap > 0, d_list_* arrays that are not 8-byte aligned, a d_points that is not
+ * 4-byte aligned, NULL kps, a NULL or misaligned d_kps, a frame_pitch that is negative or no multiple of 4, kp_first < 0 or
+ * kp_first + (nodes - 1) * kp_step < 0. */
+int brisk_hip_track_points_device(brisk_hip_ctx* ctx, const int* d_node_rows, int node_rows_stride, int nodes, int rows_cap,
+                                  const long long* d_list_offsets, const brisk_hip_track_obs* d_list_obs, const long long* d_list_summary,
+                                  long long obs_cap, const brisk_hip_kp_set* kps, int kp_first, int kp_step, brisk_hip_track_point* d_points,
+                                  void* stream);
+/* The listed tracks in HOST memory, the way brisk_hip_pair_matches_download delivers matches.  The caller fills in the capacities and
+ * the five destination pointers (summary, track and offsets 8-byte aligned, len and points 4-byte; track and len may be NULL when
+ * tracks_cap == 0, points when points_cap == 0). */
+typedef struct brisk_hip_host_tracks {
+  long long tracks_cap, points_cap;
+  long long* summary;            /* [4]: pieces listed, their observations, pieces stored, flags (as list_tracks' d_summary) */
+  long long* track;              /* [tracks_cap] */
+  int* len;                      /* [tracks_cap] */
+  long long* offsets;            /* [tracks_cap + 1] */
+  brisk_hip_track_point* points; /* [points_cap] */
+} brisk_hip_host_tracks;
+/* Queues list + points + transfer and returns: the six kernels of brisk_hip_list_tracks_device (tracks_cap, obs_cap = points_cap)
+ * and the points kernel run on `stream` (the stream brisk_hip_link_tracks_device ran on; NULL = the context's) into a slab the
+ * context owns - d_prev / d_track / d_age and the keypoints may be overwritten by the next batch in stream order -, the transfer
+ * runs on the context's second stream.  The exact bytes that cross: summary[0 .. 4), track / len [0, stored), offsets [0, stored],
+ * points [0, offsets[stored]); nothing behind them in the caller's arrays is written.  Pinned / registered / managed / device
+ * destinations are written by the device directly; pageable ones go through a pinned buffer of the context and a host copy inside
+ * brisk_hip_tracks_wait.  *ticket names the transfer.  Two transfers of tracks are in flight per context at most - slots of their
+ * own, beside those of brisk_hip_batch_download_all and brisk_hip_pair_matches_download: a stream that downloads rows, matches AND
+ * tracks of every batch keeps two batches in flight -, a third call first completes the oldest.  `dst` (the struct) is copied; its
+ * arrays must stay valid until the ticket has been waited for.  BRISK_HIP_ERR_ARG, before anything is launched (*ticket = 0): the
+ * errors of brisk_hip_list_tracks_device (capacities: dst's) and of the device form's kps / kp_first / kp_step, NULL dst or
+ * ticket, a NULL or misaligned destination array. */
+int brisk_hip_tracks_download(brisk_hip_ctx* ctx, const int* d_node_rows, int node_rows_stride, int nodes, int rows_cap,
+                              const int* d_prev, const long long* d_track, const int* d_age, int min_len, const brisk_hip_kp_set* kps,
+                              int kp_first, int kp_step, const brisk_hip_host_tracks* dst, void* stream, unsigned* ticket);
+/* Blocks until transfer `ticket` (and every earlier one of tracks) is complete; the context's lock is not held while waiting.
+ * *cut (may be NULL) = 1 when the list was cut, else 0.  BRISK_HIP_OK, or - with every stored piece in place -
+ * BRISK_HIP_ERR_CAPACITY when the summary's flags carry BRISK_HIP_TRACKS_CUT.  An unknown ticket: BRISK_HIP_ERR_ARG. */
+int brisk_hip_tracks_wait(brisk_hip_ctx* ctx, unsigned ticket, int* cut);
+
 /* ---- per-stage timing: HIP events recorded on the launch stream around every kernel of the batch path ---- */
 int brisk_hip_profile_enable(brisk_hip_ctx* ctx, int enable);       /* resets the accumulated calls */
 int brisk_hip_profile_stages(void);                                 /* number of stages */

@@ -39,6 +39,16 @@ With --tracks (k-NN only, profiles/track_pairs.json) what linking the matches in
 plus the HIP-event time of the link call and of the list call (six launches each; a `rocprofv3 --kernel-trace --stats` pass
 around --tracks --stats-pass gives the single kernels: profiles/track_pairs_kernel_stats.csv), tracks and links per batch, and
 whether the device's arrays equal a host restatement of the rule on the downloaded lists of one batch.
+With --tracks-download (k-NN only, profiles/track_download.json) what getting the listed tracks to the HOST costs, three windows:
+  T  --tracks' window T: detect + describe + match + select + link + list, the lists stay in HBM
+  D  T with brisk_hip_tracks_download (min_len 3) into pinned memory in place of the list call, two destinations alternating, a
+     ticket waited for one batch later
+  P  what a caller had to do before that exit, with the other entry points only: T, a synchronisation to read the list's summary,
+     one hipMemcpy per list array (the stored prefixes) and brisk_hip_batch_download_all of the batch's keypoints, waited for at
+     once; the join of (node, row) against those keypoints on the host is NOT timed
+plus D / T, D / P, the spread of T's windows, the bytes that cross the link per batch in D and in P, and whether D's arrays equal
+the list call's arrays joined with batch_download_all's keypoints on the host (--stats-pass: D iterations only, for the kernel
+trace behind profiles/track_download_kernel_stats.csv).
 Usage: python tools/bench_match_pairs.py [--repeats 5] [--window 0.4] [--rows-cap 2048] [--radius R [--cap N]] [--gate ...] [--out FILE]
        --stats-pass: warm-up + a few B iterations (with --gate: B, G and I) only, nothing written (the run a
        `rocprofv3 --kernel-trace --stats` pass wraps; its kernel statistics are kept as profiles/match_pairs_kernel_stats.csv)"""
@@ -315,6 +325,154 @@ def tracks_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
     ctx.close()
 
 
+def tracks_download_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
+    """--tracks-download: windows T, D and P (see the module's text); writes a.out"""
+    st = work.cuda_stream
+    select = B.MatchSelect(float("inf"), 0.8, 1)
+    L, h = ctx._L, ctx._h
+    mcap = (n - 1) * cap                                            # (one match per row at the most)
+    sel = (torch.zeros((mcap, 4), dtype=torch.int32, device=dev), torch.zeros(n - 1, dtype=torch.int32, device=dev),
+           torch.zeros(n - 1, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int64, device=dev))
+    prev, age = (torch.zeros((n, cap), dtype=torch.int32, device=dev) for _ in range(2))
+    track = torch.zeros((n, cap), dtype=torch.int64, device=dev)
+    summary = torch.zeros(8, dtype=torch.int64, device=dev)
+    tcap, ocap = n * cap // 4, n * cap
+    lists = (torch.zeros(tcap, dtype=torch.int64, device=dev), torch.zeros(tcap, dtype=torch.int32, device=dev),
+             torch.zeros(tcap + 1, dtype=torch.int64, device=dev), torch.zeros((ocap, 2), dtype=torch.int32, device=dev),
+             torch.zeros(4, dtype=torch.int64, device=dev))
+    seed = B.TrackSeed(None, None, 0, summary.data_ptr())           # numbered on from the call before
+    m, cnt, rows = outs["B"]
+    dst = [B.HostTrackList(tcap, ocap, pinned=True) for _ in range(2)]
+    tickets = []
+    # P's destinations: pinned, as large as the device arrays; the keypoints of every frame
+    plists = tuple(torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in lists)
+    prow = B.HostResults(n, n * cap, 0, pinned=True)
+    last = {}
+
+    def run_link():
+        run_b0()
+        ctx.check(L.brisk_hip_select_pair_matches_device(h, m.data_ptr(), cnt.data_ptr(), rows.data_ptr(), n - 1, cap, k, C.byref(select), mcap,
+                                                         sel[1].data_ptr(), sel[2].data_ptr(), sel[3].data_ptr(), sel[0].data_ptr(), st))
+        dset, _ = ctx.batch_desc_set()
+        ptr, stride = ctx._node_rows((dset, 0, 1))
+        ctx.check(L.brisk_hip_link_tracks_device(h, ptr, stride, n, cap, sel[3].data_ptr(), sel[0].data_ptr(), C.byref(seed), prev.data_ptr(),
+                                                 track.data_ptr(), age.data_ptr(), summary.data_ptr(), st))
+        return dset, ptr, stride
+
+    def run_t():
+        _, ptr, stride = run_link()
+        ctx.check(L.brisk_hip_list_tracks_device(h, ptr, stride, n, cap, prev.data_ptr(), track.data_ptr(), age.data_ptr(), 3, tcap, ocap,
+                                                 lists[0].data_ptr(), lists[1].data_ptr(), lists[2].data_ptr(), lists[3].data_ptr(),
+                                                 lists[4].data_ptr(), st))
+
+    def run_d():
+        dset, _, _ = run_link()
+        tickets.append(ctx.tracks_download((dset, 0, 1), n, cap, prev, track, age, 3, dst[len(tickets) % 2], stream=st))
+        if len(tickets) >= 2:                                      # the batch before: its destination is the next one to be reused
+            ctx.tracks_wait(tickets[-2])
+
+    def drain_d():
+        if tickets:
+            ctx.tracks_wait(tickets[-1])
+        del tickets[:]
+
+    def run_p():
+        run_t()
+        work.synchronize()                                         # the summary says how much there is to copy
+        plists[4].copy_(lists[4])
+        stored = int(plists[4][2])
+        plists[2][:stored + 1].copy_(lists[2][:stored + 1])
+        nobs = int(plists[2][stored])
+        plists[0][:stored].copy_(lists[0][:stored])
+        plists[1][:stored].copy_(lists[1][:stored])
+        plists[3][:nobs].copy_(lists[3][:nobs])
+        ctx.batch_download_wait(ctx.batch_download_all(prow, stream=st))
+        last["stored"], last["nobs"] = stored, nobs
+
+    runs = {"T": run_t, "D": run_d, "P": run_p}
+    ends = {"T": lambda: None, "D": drain_d, "P": lambda: None}
+    order = "TDP"
+    for v in order + "TD":                                         # warm-up: buffers sized, scratch and slabs grown
+        runs[v]()
+        ends[v]()
+        torch.cuda.synchronize()
+    if a.stats_pass:
+        for _ in range(8):
+            run_d()
+        drain_d()
+        torch.cuda.synchronize()
+        return
+
+    # what D delivers against what P delivers, joined on the host (the same batch content in every call; numbers apart: every
+    # batch is numbered on from the one before)
+    run_d()
+    drain_d()
+    run_p()
+    torch.cuda.synchronize()
+    d = dst[0]
+    stored, nobs = last["stored"], last["nobs"]
+    obs = plists[3][:nobs].numpy()
+    joined = np.stack([prow.kps[int(prow.offsets[f]) + r] for f, r in obs]) if nobs else np.zeros(0, B.KEYPOINT)
+    pw = d.points[:nobs].view(np.uint32).reshape(-1, 9)
+    identical = bool(d.summary.tolist() == plists[4].tolist() and d.len[:stored].tobytes() == plists[1][:stored].numpy().tobytes() and
+                     d.offsets[:stored + 1].tobytes() == plists[2][:stored + 1].numpy().tobytes() and
+                     np.array_equal(np.diff(d.track[:stored]), np.diff(plists[0][:stored].numpy())) and
+                     pw[:, :2].tobytes() == obs.tobytes() and pw[:, 2:].tobytes() == joined.tobytes())
+    nrows = int(prow.offsets[n])
+    bytes_d = 32 + 8 * stored + 4 * stored + 8 * (stored + 1) + 36 * nobs
+    bytes_p = 32 + 8 * stored + 4 * stored + 8 * (stored + 1) + 8 * nobs + 4 * n + 4 * n + 8 * (n + 1) + 28 * nrows
+
+    fps = {v: [] for v in order}
+    for _ in range(a.repeats):
+        for v in order:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            calls = 0
+            while True:
+                runs[v]()
+                calls += 1
+                if time.perf_counter() - t0 >= a.window:
+                    break
+            ends[v]()
+            torch.cuda.synchronize()
+            fps[v].append(calls * n / (time.perf_counter() - t0))
+    med = {v: float(np.median(fps[v])) for v in order}
+    ms = {v: 1e3 * n / med[v] for v in order}
+    spread = {v: (max(fps[v]) - min(fps[v])) / med[v] for v in order}
+    res = {
+        "workload": "bench.py's stream: %dx%d, threshold %d, %d octaves, %d frames per batch (%d distinct) in HBM; frame-to-previous-frame, "
+                    "k = %d, rows_cap %d, ratio 0.8, one match per row; tracks of min_len 3, tracks_cap %d, points_cap %d"
+                    % (W, H, THRESHOLD, OCTAVES, n, nd, k, cap, tcap, ocap),
+        "kernel_revision": ctx.kernel_revision(),
+        "device": torch.cuda.get_device_name(0),
+        "windows": {"repeats": a.repeats, "seconds_each": a.window,
+                    "order": ", ".join(order) + " alternating; every window ends with its transfers complete and a synchronise"},
+        "frames_per_s": {v: round(med[v], 1) for v in order},
+        "frames_per_s_all": {v: [round(x, 1) for x in fps[v]] for v in order},
+        "spread_rel": {v: round(spread[v], 4) for v in order},
+        "ms_per_batch": {v: round(ms[v], 4) for v in order},
+        "D_over_T_frames_per_s": round(med["D"] / med["T"], 4),
+        "D_over_P_frames_per_s": round(med["D"] / med["P"], 4),
+        "bar": {"D_not_slower_than_P_by_more_than_T_spread": bool(med["D"] >= med["P"] * (1.0 - spread["T"])), "T_spread_rel": round(spread["T"], 4)},
+        "bytes_per_batch": {"D": bytes_d, "P": bytes_p},
+        "per_batch": {"nodes": n, "rows": nrows, "tracks_listed_min_len_3": int(d.summary[0]), "their_observations": int(d.summary[1]),
+                      "tracks_stored": stored, "points_stored": nobs, "share_of_rows_listed": round(nobs / max(nrows, 1), 4),
+                      "list_cut": bool(d.summary[3])},
+        "D_equals_P_joined_on_the_host": identical,
+        "legend": {"T": "detect_describe_batch + match_knn_pairs + select + brisk_hip_link_tracks_device + brisk_hip_list_tracks_device on one stream",
+                   "D": "T with brisk_hip_tracks_download into pinned memory in place of the list call, waited for one batch later",
+                   "P": "T, synchronise, hipMemcpy of the summary and the four list arrays' stored prefixes, brisk_hip_batch_download_all of the "
+                        "keypoints and its wait; the host join is not timed"},
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+    ext.close()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=512)
@@ -331,6 +489,8 @@ def main():
     ap.add_argument("--stats-pass", action="store_true")
     ap.add_argument("--export", action="store_true", help="windows B, E (packed, selected matches to the host) and D (padded arrays to the host)")
     ap.add_argument("--tracks", action="store_true", help="windows B (match + select) and T (B + link_tracks + list_tracks)")
+    ap.add_argument("--tracks-download", action="store_true",
+                    help="windows T (--tracks' T), D (tracks_download in place of the list call) and P (list, synchronise, copies, batch_download_all)")
     a = ap.parse_args()
 
     radius = a.radius
@@ -348,6 +508,11 @@ def main():
             ap.error("--tracks measures the k-NN pair call: without --radius / --gate / --export")
         if a.out is None:
             a.out = os.path.join(ROOT, "profiles", "track_pairs.json")
+    if a.tracks_download:
+        if radius is not None or gate or a.export or a.tracks:
+            ap.error("--tracks-download measures the k-NN pair call: without --radius / --gate / --export / --tracks")
+        if a.out is None:
+            a.out = os.path.join(ROOT, "profiles", "track_download.json")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", ("match_radius_pairs" if radius is not None else "match_pairs") +
                              ("_gated" if gate else "") + ".json")
@@ -398,6 +563,9 @@ def main():
         return
     if a.tracks:
         tracks_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b)
+        return
+    if a.tracks_download:
+        tracks_download_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b)
         return
 
     vp = C.c_void_p
