@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "brisk_hip_match_radius_pairs_device", "brisk_hip_match_radius_device",
     "brisk_hip_batch_kp_set", "brisk_hip_match_knn_pairs_gated_device", "brisk_hip_match_radius_pairs_gated_device",
     "brisk_hip_select_pair_matches_device", "brisk_hip_pair_matches_download", "brisk_hip_pair_matches_wait",
+    "brisk_hip_verify_pair_matches_device",
     "brisk_hip_link_tracks_device", "brisk_hip_list_tracks_device",
     "brisk_hip_track_points_device", "brisk_hip_tracks_download", "brisk_hip_tracks_wait",
 ]
@@ -114,6 +115,19 @@ class PairHostMatches(C.Structure):
                 ("flags", C.c_void_p), ("offsets", C.c_void_p), ("matches", C.c_void_p)]
 
 
+class PairVerify(C.Structure):
+    """brisk_hip_pair_verify: a record is an inlier of a hypothesis iff its transfer error is at most max_error pixels (train frame);
+    `hypotheses` four-record samples per pair (1 ... 4096), a model needs min_inliers (>= 4) inliers; keep_unverified: what a pair
+    without an accepted model keeps (0 = nothing, else its usable records); seed: of the sampler"""
+    _fields_ = [("max_error", C.c_float), ("hypotheses", C.c_int), ("min_inliers", C.c_int), ("keep_unverified", C.c_int),
+                ("seed", C.c_uint)]
+
+
+# brisk_hip_pair_model: the winner's normalised H and the pair's counts
+PAIR_MODEL = np.dtype([("h", "<f8", (9,)), ("records", "<i4"), ("usable", "<i4"), ("inliers", "<i4"), ("hypothesis", "<i4"),
+                       ("valid", "<i4"), ("flags", "<i4")])
+
+
 class TrackSeed(C.Structure):
     """brisk_hip_track_seed: d_track / d_age [rows_cap] device arrays (row r of node 0 continues track d_track[r] >= 0 at age
     d_age[r]; both None = no seeds), first_new = the first number the call may give - read from the device word d_first_new when
@@ -135,6 +149,7 @@ class HostTracks(C.Structure):
 
 # flags of a pair in the selected lists (ROWS_CUT: the pair and every pair behind it did not fit matches_cap)
 PAIR_ROWS_CUT, PAIR_BAD, PAIR_ENTRIES_CUT = 1, 2, 4
+PAIR_NO_MODEL = 8   # verify_pair_matches: the pair has no accepted model
 
 
 def _host_array(n, dtype, pinned, keep):
@@ -318,6 +333,9 @@ def load_library():
     L.brisk_hip_pair_matches_download.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(MatchSelect),
                                                   C.POINTER(PairHostMatches), vp, C.POINTER(C.c_uint)]
     L.brisk_hip_pair_matches_wait.argtypes = [vp, C.c_uint, ip]
+    L.brisk_hip_verify_pair_matches_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
+                                                       C.POINTER(PairSpec), C.c_int, vp, vp, C.c_longlong, C.POINTER(PairVerify),
+                                                       C.c_longlong, vp, vp, vp, vp, vp, vp]
     L.brisk_hip_link_tracks_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(TrackSeed), vp, vp, vp, vp, vp]
     L.brisk_hip_list_tracks_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_longlong, C.c_longlong,
                                                vp, vp, vp, vp, vp, vp]
@@ -731,6 +749,34 @@ class Context:
             return rc, n.value
         self.check(rc)
         return n.value
+
+    # -- a batch's pair matches checked against a homography --
+    def verify_pair_matches(self, query, train, pairs, rows_cap, offsets, matches, verify, out_cap=None, query_kps=None, train_kps=None,
+                            stream=None):
+        """brisk_hip_verify_pair_matches_device on what select_pair_matches returned for these pairs (offsets [npairs + 1], matches
+        [in_cap, 4]: in_cap = the selection's matches_cap).  query / train: DescSet (the row counts); pairs: PairSpec; verify: a
+        PairVerify; query_kps / train_kps: KpSet (None = the last batch's); out_cap None = in_cap.  Returns the device tensors
+        (matches [out_cap, 4] int32 - the kept DMATCH records, in order -, counts [npairs], flags [npairs], offsets [npairs + 1]
+        int64, models [npairs, 12] int64 - PAIR_MODEL records); the first four are what link_tracks and the exits take.
+        Asynchronous on `stream`."""
+        import torch
+        n, in_cap = int(pairs.npairs), int(matches.shape[0])
+        if out_cap is None:
+            out_cap = in_cap
+        if query_kps is None or train_kps is None:
+            own = self.batch_kp_set()
+            query_kps = own if query_kps is None else query_kps
+            train_kps = own if train_kps is None else train_kps
+        dev = matches.device
+        res = (torch.empty((max(int(out_cap), 0), 4), dtype=torch.int32, device=dev), torch.empty(max(n, 0), dtype=torch.int32, device=dev),
+               torch.empty(max(n, 0), dtype=torch.int32, device=dev), torch.empty(max(n, 0) + 1, dtype=torch.int64, device=dev),
+               torch.empty((max(n, 0), 12), dtype=torch.int64, device=dev))
+        self.check(self._L.brisk_hip_verify_pair_matches_device(self._h, C.byref(query), C.byref(train), C.byref(query_kps), C.byref(train_kps),
+                                                                C.byref(pairs), int(rows_cap), offsets.data_ptr(), matches.data_ptr(), in_cap,
+                                                                C.byref(verify), int(out_cap), res[4].data_ptr(), res[1].data_ptr(),
+                                                                res[2].data_ptr(), res[3].data_ptr(), res[0].data_ptr(),
+                                                                C.c_void_p(stream) if stream else None))
+        return res
 
     # -- a batch's pair matches linked into feature tracks --
     @staticmethod

@@ -8,7 +8,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbrisk_hip.so")                  # tests / tools / bench.py: built with -DBRISK_HIP_TUNING
 LIB_RELEASE = os.path.join(HERE, "libbrisk_hip_release.so")  # what a maintainer links: no env knobs, no debug bits, no brisk_hip_debug_*
 TUNING = ["-DBRISK_HIP_TUNING"]
-SOURCES = ["brisk_kernels.hip", "brisk_describe.hip", "brisk_export.hip", "brisk_image16.hip", "brisk_match.hip", "brisk_match_export.hip", "brisk_track.hip", "brisk_track_export.hip", "brisk_uniformity.hip", "brisk_comm.hip", "brisk_capi.hip", "brisk_pattern.cpp"]
+SOURCES = ["brisk_kernels.hip", "brisk_describe.hip", "brisk_export.hip", "brisk_image16.hip", "brisk_match.hip", "brisk_match_export.hip", "brisk_pair_verify.hip", "brisk_track.hip", "brisk_track_export.hip", "brisk_uniformity.hip", "brisk_comm.hip", "brisk_capi.hip", "brisk_pattern.cpp"]
 # -ffp-contract=off: the reference binary has no FMA contraction (built with -mssse3 only); the
 # sub-pixel / sub-scale float expressions must round after every operation to stay bit-exact.
 # -simplifycfg-sink-common=false: sinking the common tails of the per-layer-class branches of the refinement code

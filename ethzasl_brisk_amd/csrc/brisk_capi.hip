@@ -150,6 +150,7 @@ struct brisk_hip_ctx {
   TransferRing<TrackTransfer> tx;                 // brisk_hip_tracks_download
   hipStream_t egress = nullptr;
   DeviceBuf d_select;  // brisk_hip_select_pair_matches_device / _pair_matches_download: the per-workgroup sums of the selection passes
+  DeviceBuf d_verify;  // brisk_hip_verify_pair_matches_device: a keep byte per input record, the pairs' kept counts
   DeviceBuf d_track;   // brisk_hip_link_tracks_device / _list_tracks_device: claim words, forward pointers, piece words, workgroup sums
   int last_strings = 0;  // descriptor bytes of the pattern the last describing call used
 };
@@ -2137,6 +2138,78 @@ int brisk_hip_select_pair_matches_device(brisk_hip_ctx* ctx, const brisk_hip_dma
   if (int rc = select_launch(ctx, d_out, d_out_count, d_pair_rows, npairs, rows_cap, per_row, select, matches_cap, d_counts, d_flags, d_offsets,
                              d_matches, nullptr, st))
     return rc;
+  if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
+  return BRISK_HIP_OK;
+}
+
+// ---- a batch's pair matches checked against a homography (kernels: brisk_pair_verify.hip) ----------------------------------------
+static_assert(sizeof(brisk_hip_pair_verify) == 20 && sizeof(BriskPairVerify) == 20 && sizeof(brisk_hip_pair_model) == 96 &&
+              sizeof(BriskPairModel) == 96 && BRISK_PAIR_NO_MODEL == BRISK_HIP_PAIR_NO_MODEL, "pair verify / model layout");
+
+int brisk_hip_verify_pair_matches_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                         const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                         const brisk_hip_pair_spec* pairs, int rows_cap, const long long* d_offsets,
+                                         const brisk_hip_dmatch* d_matches, long long in_cap, const brisk_hip_pair_verify* verify,
+                                         long long out_cap, brisk_hip_pair_model* d_models, int* d_out_counts, int* d_out_flags,
+                                         long long* d_out_offsets, brisk_hip_dmatch* d_out_matches, void* stream) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (!pairs || !verify) return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: null pairs or verify");
+  const int np = pairs->npairs;
+  if (np < 0 || rows_cap < 1 || in_cap < 0 || out_cap < 0)
+    return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: npairs / in_cap / out_cap negative, or rows_cap below 1");
+  if (verify->hypotheses < 1 || verify->hypotheses > BRISK_VERIFY_MAX_HYPOTHESES || verify->min_inliers < BRISK_VERIFY_MIN_SAMPLE)
+    return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: hypotheses outside 1 ... 4096, or min_inliers below 4");
+  if (((((uintptr_t)d_matches | (uintptr_t)d_out_matches) & 15)) || (((uintptr_t)d_offsets | (uintptr_t)d_out_offsets | (uintptr_t)d_models) & 7) ||
+      (((uintptr_t)d_out_counts | (uintptr_t)d_out_flags | (uintptr_t)pairs->d_pairs) & 3))
+    return fail(ctx, BRISK_HIP_ERR_ARG,
+                "verify_pair_matches: the match arrays must be 16-byte aligned, offsets and models 8-byte, counts, flags and d_pairs 4-byte");
+  if (np > 0) {
+    if (!query || !train) return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: null descriptor set");
+    for (const brisk_hip_desc_set* s : {query, train})
+      if (!s->d_counts || ((uintptr_t)s->d_counts & 3) || s->frames <= 0 || s->count_stride <= 0)
+        return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: a descriptor set without counts, or with frames / count_stride below 1");
+    if (!query_kps || !train_kps) return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: null keypoint set");
+    for (const brisk_hip_kp_set* s : {query_kps, train_kps}) {
+      if (!s->d_kps) return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: a keypoint set without records");
+      if (s->frame_pitch < 0 || (((uintptr_t)s->d_kps | (unsigned long)s->frame_pitch) & 3))
+        return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: bad keypoint set geometry");
+    }
+    if (!d_offsets || (in_cap > 0 && !d_matches)) return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: null match lists");
+    if (!d_models || !d_out_counts || !d_out_flags || !d_out_offsets || (out_cap > 0 && !d_out_matches))
+      return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: null output array");
+    if (!pairs->d_pairs) {  // (a list on the device is checked there: the pair is flagged bad)
+      const long q0 = pairs->query_first, q1 = q0 + (long)(np - 1) * pairs->query_step;
+      const long t0 = pairs->train_first, t1 = t0 + (long)(np - 1) * pairs->train_step;
+      if (q0 < 0 || q0 >= query->frames || q1 < 0 || q1 >= query->frames || t0 < 0 || t0 >= train->frames || t1 < 0 || t1 >= train->frames)
+        return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: a pair names a frame outside its set");
+    }
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  if (np == 0) {
+    if (d_out_offsets) HIPCHK(ctx, hipMemsetAsync(d_out_offsets, 0, sizeof(long long), st));
+    return BRISK_HIP_OK;
+  }
+  // the context's scratch is written: the stream is ordered behind the previous call's work, the next call behind this one
+  if (workspace_acquire(ctx, st)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
+  WorkspaceGuard guard(ctx, st);
+  const size_t at_kept = ((size_t)in_cap + 15) & ~(size_t)15, bytes = at_kept + (size_t)np * sizeof(long long);
+  if (ctx->d_verify.cap < bytes) {
+    HIPCHK(ctx, wait_own_work(ctx));  // (every user of the scratch is a workspace call)
+    HIPCHK(ctx, ctx->d_verify.grow(bytes));
+  }
+  unsigned char* base = ctx->d_verify.as<unsigned char>();
+  const BriskDescSet Q{query->d_desc, query->d_counts, query->count_stride, query->frame_pitch, query->row_pitch, query->frames};
+  const BriskDescSet T{train->d_desc, train->d_counts, train->count_stride, train->frame_pitch, train->row_pitch, train->frames};
+  const BriskPairSpec P{np, pairs->query_first, pairs->query_step, pairs->train_first, pairs->train_step, pairs->d_pairs};
+  const BriskKpSet QK{reinterpret_cast<const char*>(query_kps->d_kps), query_kps->frame_pitch};
+  const BriskKpSet TK{reinterpret_cast<const char*>(train_kps->d_kps), train_kps->frame_pitch};
+  const BriskPairVerify V{verify->max_error, verify->hypotheses, verify->min_inliers, verify->keep_unverified, verify->seed};
+  brisk_launch_pair_verify(Q, T, QK, TK, P, rows_cap, d_offsets, reinterpret_cast<const BriskDMatch*>(d_matches), in_cap, V, base,
+                           reinterpret_cast<long long*>(base + at_kept), out_cap, reinterpret_cast<BriskPairModel*>(d_models), d_out_counts,
+                           d_out_flags, d_out_offsets, reinterpret_cast<BriskDMatch*>(d_out_matches), st);
+  HIPCHK(ctx, hipGetLastError());
   if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
   return BRISK_HIP_OK;
 }

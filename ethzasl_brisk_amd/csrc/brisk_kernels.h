@@ -5,6 +5,7 @@
 #include "brisk_common.h"
 #include "brisk_match_gate.h"
 #include "brisk_match_select.h"
+#include "brisk_pair_verify.h"
 #include "brisk_track_link.h"
 #include "brisk_track_points.h"
 
@@ -191,7 +192,7 @@ bool brisk_launch_match_radius_pairs_gated(const BriskDescSet& Q, const BriskDes
 
 // ---- the pair matchers' exit: selected matches, packed (brisk_match_export.hip; the rule: brisk_match_select.h) ----
 // flags of a pair (mirror BRISK_HIP_PAIR_* / BRISK_HIP_ROWS_CUT of brisk_hip.h)
-enum { BRISK_PAIR_ROWS_CUT = 1, BRISK_PAIR_BAD = 2, BRISK_PAIR_ENTRIES_CUT = 4, BRISK_PAIR_MATCHES_CUT = 0x100 };
+enum { BRISK_PAIR_ROWS_CUT = 1, BRISK_PAIR_BAD = 2, BRISK_PAIR_ENTRIES_CUT = 4, BRISK_PAIR_NO_MODEL = 8, BRISK_PAIR_MATCHES_CUT = 0x100 };
 int brisk_match_export_blocks_per_pair(int rows_cap);
 // out / out_count / pair_rows: what a pair matcher wrote.  blk [npairs * blocks_per_pair] long long and blk_over (ints, as many):
 // scratch.  counts / flags [npairs], offsets [npairs + 1], matches [matches_cap] (16-byte aligned, like out); rows_copy: NULL or
@@ -203,6 +204,15 @@ void brisk_launch_pair_select(const BriskDMatch* out, const int* out_count, cons
 void brisk_launch_pair_select_egress(const int* s_rows, const int* s_counts, const int* s_flags, const long long* s_offsets,
                                      const BriskDMatch* s_matches, int npairs, int* h_rows, int* h_counts, int* h_flags, long long* h_offsets,
                                      void* h_matches, hipStream_t s);
+
+// ---- a batch's pair matches checked against a homography (brisk_pair_verify.hip; the rule: brisk_pair_verify.h) ----
+// offsets [npairs + 1] / matches [in_cap]: the packed lists of the selection; pair p as the pair matchers resolve P.  Scratch: keep
+// [in_cap] bytes (one per input record), kept [npairs] long long.  models / counts / flags [npairs], out_offsets [npairs + 1], out
+// [out_cap] (16-byte aligned, like matches).  BRISK_PAIR_NO_MODEL: a pair without an accepted model
+void brisk_launch_pair_verify(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK, const BriskPairSpec& P,
+                              int rows_cap, const long long* offsets, const BriskDMatch* matches, long long in_cap, const BriskPairVerify& V,
+                              unsigned char* keep, long long* kept, long long out_cap, BriskPairModel* models, int* counts, int* flags,
+                              long long* out_offsets, BriskDMatch* out, hipStream_t s);
 
 // ---- a batch's pair matches linked into feature tracks (brisk_track.hip; the rule: brisk_track_link.h) ----
 enum { BRISK_TRACK_C_LINKS = 0, BRISK_TRACK_C_LOST = 1, BRISK_TRACK_C_IGNORED = 2, BRISK_TRACK_COUNTERS = 4 };  // the link call's counters

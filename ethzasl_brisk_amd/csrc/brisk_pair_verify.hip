@@ -1,0 +1,349 @@
+// brisk_pair_verify.hip - a batch's pair matches checked against a homography (brisk_hip_verify_pair_matches_device).
+//
+// Between the selection and the linker: the packed lists brisk_hip_select_pair_matches_device leaves in HBM hold whatever survived
+// a descriptor test.  brisk_pair_verify.h is the one definition of the rule that decides which of a pair's records agree with ONE
+// homography estimated from the records themselves; the output has the selection's format, so the linker and both exits read it
+// unchanged.
+//   k_verify_ransac   one workgroup per pair, a lane = a hypothesis: the lane builds its H in registers from its four sampled
+//                     records, the workgroup streams the pair's records through LDS ({x, y, x', y'} floats, VF_CHUNK a chunk;
+//                     every lane reads the SAME LDS address per step: a broadcast, no cross-lane traffic in the loop).  The
+//                     winner = the largest key count << 32 | ~h, reduced by wave shuffles and one LDS step.  A last sweep, lane =
+//                     record, writes a keep byte per record and the pair's kept count; then the model record.
+//                     LOOP ORDER: the pass over 256 hypotheses is the OUTER loop, the chunk the inner one.  A lane then carries
+//                     one H and one count at a time (with the chunk outside, every lane would have to carry - or rebuild per
+//                     chunk - the models of all its up to 16 passes).  A pair of one chunk (m <= VF_CHUNK, the usual case: the
+//                     lists hold a few dozen records a pair) is staged ONCE and stays in LDS for every pass and for the last
+//                     sweep; only a longer pair restages its chunks per pass: 1 024 record resolutions against 256 x 1 024 scores.
+//   k_verify_offsets  one workgroup: exclusive prefix sums of the kept counts, counts / flags / offsets, the cut at out_cap (the
+//                     chunked scan and the cut of k_pair_select_offsets, brisk_match_export.hip)
+//   k_verify_scatter  one workgroup per pair: stable compaction of the kept records in chunks of 256 - a ballot per wave, the wave
+//                     totals in LDS, 16-byte loads and stores, no atomics
+#include <hip/hip_runtime.h>
+
+#include "brisk_common.h"
+#include "brisk_kernels.h"
+#include "brisk_track_link.h"
+
+#define VF_THREADS 256
+#define VF_WAVES (VF_THREADS / 64)
+#define VF_CHUNK 1024          // records staged in LDS at a time (16 bytes each)
+#define VF_OFF_THREADS 1024    // the offsets workgroup
+
+// a pair's records: [begin, begin + m) of the packed list.  false: the offsets do not describe a range inside [0, in_cap] of at
+// most 2^31 - 1 records - the pair is BAD, nothing of it is read
+__device__ __forceinline__ bool vf_range(const long long* __restrict__ offsets, int p, long long in_cap, long long& begin, int& m) {
+  const long long b = offsets[p], e = offsets[p + 1];
+  begin = b;
+  m = 0;
+  if (b < 0 || e < b || e > in_cap || e - b > 0x7FFFFFFFll) return false;
+  m = (int)(e - b);
+  return true;
+}
+
+__device__ __forceinline__ const float* vf_kp(const char* kps, int r) {
+  return reinterpret_cast<const float*>(kps + (long)r * (long)sizeof(BriskKeyPoint));  // x, y lead the record
+}
+
+// record j of the list -> its point pair; false = unusable (nothing is read from the keypoint sets then)
+__device__ __forceinline__ bool vf_resolve(const BriskDMatch* __restrict__ matches, long long j, const char* qk, const char* tk, int lim_a,
+                                           int lim_b, float4& pt) {
+  const int4 rec = *reinterpret_cast<const int4*>(matches + j);  // {queryIdx, trainIdx, imgIdx, distance}
+  if (!brisk_verify_index_ok(rec.x, rec.y, lim_a, lim_b)) return false;
+  const float* q = vf_kp(qk, rec.x);
+  const float* t = vf_kp(tk, rec.y);
+  pt = make_float4(q[0], q[1], t[0], t[1]);
+  return brisk_verify_coords_ok(pt.x, pt.y, pt.z, pt.w);
+}
+
+__device__ __forceinline__ BriskVerifyPoints vf_points(const float4& pt) {
+  return BriskVerifyPoints{(double)pt.x, (double)pt.y, (double)pt.z, (double)pt.w};
+}
+
+// the model of hypothesis h of a pair with m >= 4 records, and z_ref; false = invalid
+__device__ __forceinline__ bool vf_hypothesis(const BriskDMatch* __restrict__ matches, long long begin, int m, uint32_t pair_seed, int h,
+                                              const char* qk, const char* tk, int lim_a, int lim_b, BriskHomography& H, double& z_ref) {
+  int i0, i1, i2, i3;
+  brisk_verify_sample(pair_seed, h, m, i0, i1, i2, i3);
+  float4 a, b, c, d;
+  // (every index is below m by construction; a draw that is not - it cannot happen - would make the hypothesis invalid, not a read)
+  if ((unsigned)i0 >= (unsigned)m || (unsigned)i1 >= (unsigned)m || (unsigned)i2 >= (unsigned)m || (unsigned)i3 >= (unsigned)m) return false;
+  bool ok = vf_resolve(matches, begin + i0, qk, tk, lim_a, lim_b, a);
+  ok = ok && vf_resolve(matches, begin + i1, qk, tk, lim_a, lim_b, b);
+  ok = ok && vf_resolve(matches, begin + i2, qk, tk, lim_a, lim_b, c);
+  ok = ok && vf_resolve(matches, begin + i3, qk, tk, lim_a, lim_b, d);
+  if (!ok) return false;
+  ok = brisk_verify_model(vf_points(a), vf_points(b), vf_points(c), vf_points(d), H);
+  z_ref = brisk_verify_z(H, (double)a.x, (double)a.y);
+  return ok;
+}
+
+// chunk c of the pair -> LDS, resolved once by coalesced lanes; an unusable record is marked by a NaN x
+__device__ __forceinline__ void vf_stage(float4* __restrict__ lds, const BriskDMatch* __restrict__ matches, long long begin, int m, int c,
+                                         const char* qk, const char* tk, int lim_a, int lim_b) {
+  const int n = min(VF_CHUNK, m - c * VF_CHUNK);
+  for (int i = threadIdx.x; i < n; i += VF_THREADS) {
+    float4 pt;
+    if (!vf_resolve(matches, begin + (long long)c * VF_CHUNK + i, qk, tk, lim_a, lim_b, pt)) pt = make_float4(__builtin_nanf(""), 0.f, 0.f, 0.f);
+    lds[i] = pt;
+  }
+}
+
+__global__ void __launch_bounds__(VF_THREADS) k_verify_ransac(BriskDescSet Q, BriskDescSet T, BriskKpSet QK, BriskKpSet TK, BriskPairSpec P,
+                                                              int rows_cap, const long long* __restrict__ offsets,
+                                                              const BriskDMatch* __restrict__ matches, long long in_cap, BriskPairVerify V,
+                                                              unsigned char* __restrict__ keep, long long* __restrict__ kept,
+                                                              BriskPairModel* __restrict__ models) {
+  __shared__ float4 pts[VF_CHUNK];
+  __shared__ unsigned long long wkey[VF_WAVES];
+  __shared__ double win[10];  // the winner's H and z_ref
+  __shared__ int wsum[2][VF_WAVES];
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+  // the pair, as the pair matchers resolve it
+  int fa, fb;
+  if (P.pairs) {
+    fa = P.pairs[2 * (long)p];
+    fb = P.pairs[2 * (long)p + 1];
+  } else {
+    fa = P.query_first + p * P.query_step;
+    fb = P.train_first + p * P.train_step;
+  }
+  long long begin;
+  int m;
+  const bool range_ok = vf_range(offsets, p, in_cap, begin, m);
+  const bool frames_ok = fa >= 0 && fa < Q.frames && fb >= 0 && fb < T.frames;
+  if (!range_ok || !frames_ok) {  // nothing is kept, nothing of the pair is read
+    if (tid == 0) {
+      kept[p] = 0;
+      BriskPairModel M;
+      for (int i = 0; i < 9; ++i) M.h[i] = 0.0;
+      M.records = m;
+      M.usable = 0;
+      M.inliers = 0;
+      M.hypothesis = -1;
+      M.valid = 0;
+      M.flags = BRISK_PAIR_BAD | BRISK_PAIR_NO_MODEL;
+      models[p] = M;
+    }
+    return;
+  }
+  const int lim_a = brisk_track_lim(Q.counts[(long)fa * Q.count_stride], rows_cap);
+  const int lim_b = brisk_track_lim(T.counts[(long)fb * T.count_stride], rows_cap);
+  const char* qk = QK.kps + (long)fa * QK.frame_pitch;
+  const char* tk = TK.kps + (long)fb * TK.frame_pitch;
+  const int nchunks = (m + VF_CHUNK - 1) / VF_CHUNK;
+  const uint32_t pair_seed = brisk_verify_pair_seed(V.seed, p);
+  const bool thr_on = brisk_verify_threshold_on(V.max_error);
+  const double thr2 = brisk_verify_thr2(V.max_error);
+
+  if (nchunks == 1) vf_stage(pts, matches, begin, m, 0, qk, tk, lim_a, lim_b);  // stays for every pass and the last sweep
+  __syncthreads();
+
+  // ---- the hypotheses: passes of 256 outside, chunks inside ----
+  unsigned long long best = 0ull;
+  int nvalid = 0;
+  if (m >= BRISK_VERIFY_MIN_SAMPLE) {
+    const int npass = (V.hypotheses + VF_THREADS - 1) / VF_THREADS;
+    for (int pass = 0; pass < npass; ++pass) {
+      const int h = pass * VF_THREADS + tid;
+      BriskHomography H;
+      double z_ref = 0.0;
+      bool valid = false;
+      if (h < V.hypotheses) valid = vf_hypothesis(matches, begin, m, pair_seed, h, qk, tk, lim_a, lim_b, H, z_ref);
+      if (!valid) H = BriskHomography{0., 0., 0., 0., 0., 0., 0., 0., 0.};
+      const bool score = valid && thr_on;
+      int count = 0;
+      for (int c = 0; c < nchunks; ++c) {
+        if (nchunks > 1) {
+          __syncthreads();  // (the chunk before is read)
+          vf_stage(pts, matches, begin, m, c, qk, tk, lim_a, lim_b);
+          __syncthreads();
+        }
+        const int n = min(VF_CHUNK, m - c * VF_CHUNK);
+        if (score)
+          for (int i = 0; i < n; ++i) {
+            const float4 r = pts[i];  // one address for the whole wave: a broadcast
+            count += brisk_verify_inlier(H, z_ref, thr2, (double)r.x, (double)r.y, (double)r.z, (double)r.w) ? 1 : 0;
+          }
+      }
+      const unsigned long long key = brisk_verify_key(valid, count, h);
+      best = key > best ? key : best;
+      nvalid += valid ? 1 : 0;
+    }
+  }
+  // ---- the winner: wave shuffles, one LDS step; the number of valid hypotheses rides along ----
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_xor(best, off, 64);
+    best = o > best ? o : best;
+    nvalid += __shfl_xor(nvalid, off, 64);
+  }
+  if (lane == 0) { wkey[wave] = best; wsum[0][wave] = nvalid; }
+  __syncthreads();
+  best = 0ull;
+  nvalid = 0;
+#pragma unroll
+  for (int w = 0; w < VF_WAVES; ++w) {
+    const unsigned long long o = wkey[w];
+    best = o > best ? o : best;
+    nvalid += wsum[0][w];
+  }
+  const bool accepted = brisk_verify_accepted(best, V.min_inliers);
+  const int hwin = brisk_verify_key_hypothesis(best);
+  __syncthreads();  // (wsum is written again below)
+  if (tid == 0) {
+    BriskHomography H{0., 0., 0., 0., 0., 0., 0., 0., 0.};
+    double z_ref = 0.0;
+    if (hwin >= 0) vf_hypothesis(matches, begin, m, pair_seed, hwin, qk, tk, lim_a, lim_b, H, z_ref);  // the same arithmetic again
+    win[0] = H.h0; win[1] = H.h1; win[2] = H.h2; win[3] = H.h3; win[4] = H.h4; win[5] = H.h5; win[6] = H.h6; win[7] = H.h7; win[8] = H.h8;
+    win[9] = z_ref;
+  }
+  __syncthreads();
+  const BriskHomography W{win[0], win[1], win[2], win[3], win[4], win[5], win[6], win[7], win[8]};
+  const double w_ref = win[9];
+
+  // ---- the last sweep: lane = record ----
+  int nkept = 0, nusable = 0;
+  for (int c = 0; c < nchunks; ++c) {
+    if (nchunks > 1) {
+      __syncthreads();
+      vf_stage(pts, matches, begin, m, c, qk, tk, lim_a, lim_b);
+      __syncthreads();
+    }
+    const int n = min(VF_CHUNK, m - c * VF_CHUNK);
+    for (int i = tid; i < n; i += VF_THREADS) {
+      const float4 r = pts[i];
+      const bool usable = r.x == r.x;
+      const bool inl = accepted && usable && brisk_verify_inlier(W, w_ref, thr2, (double)r.x, (double)r.y, (double)r.z, (double)r.w);
+      const bool k = brisk_verify_keeps(accepted, usable, inl, V.keep_unverified);
+      keep[begin + (long long)c * VF_CHUNK + i] = k ? 1 : 0;
+      nkept += k ? 1 : 0;
+      nusable += usable ? 1 : 0;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    nkept += __shfl_xor(nkept, off, 64);
+    nusable += __shfl_xor(nusable, off, 64);
+  }
+  if (lane == 0) { wsum[0][wave] = nkept; wsum[1][wave] = nusable; }
+  __syncthreads();
+  if (tid == 0) {
+    nkept = nusable = 0;
+#pragma unroll
+    for (int w = 0; w < VF_WAVES; ++w) { nkept += wsum[0][w]; nusable += wsum[1][w]; }
+    kept[p] = nkept;
+    BriskPairModel M;
+    if (hwin >= 0) {
+      brisk_verify_report(W, M.h);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 9; ++i) M.h[i] = 0.0;
+    }
+    M.records = m;
+    M.usable = nusable;
+    M.inliers = brisk_verify_key_count(best);
+    M.hypothesis = hwin;
+    M.valid = nvalid;
+    M.flags = accepted ? 0 : BRISK_PAIR_NO_MODEL;
+    models[p] = M;
+  }
+}
+
+// kept[p] (the pairs' kept counts) -> exclusive prefix sums in place; per pair: count, flags (the model record's too), offset.  The
+// first pair with records that does not fit out_cap and every pair behind it are cut: their counts are reported, their offsets
+// stay at the total stored.
+__global__ void __launch_bounds__(VF_OFF_THREADS) k_verify_offsets(long long* kept, int npairs, long long out_cap, BriskPairModel* models,
+                                                                  int* __restrict__ counts, int* __restrict__ flags,
+                                                                  long long* __restrict__ offsets) {
+  __shared__ long long part[VF_OFF_THREADS / 64];
+  __shared__ int red[VF_OFF_THREADS / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long n = npairs;
+  const long long per = (n + VF_OFF_THREADS - 1) / VF_OFF_THREADS;
+  const long long i0 = min(tid * per, n), i1 = min(i0 + per, n);
+  long long sum = 0;
+  for (long long i = i0; i < i1; ++i) sum += kept[i];
+  // exclusive scan of the threads' sums: inside the wave, then over the 16 wave totals
+  long long incl = sum;
+  for (int off = 1; off < 64; off <<= 1) {
+    const long long v = __shfl_up(incl, off, 64);
+    if (lane >= off) incl += v;
+  }
+  if (lane == 63) part[wave] = incl;
+  __syncthreads();
+  long long base = incl - sum, total = 0;
+  for (int w = 0; w < VF_OFF_THREADS / 64; ++w) {
+    const long long v = part[w];
+    base += w < wave ? v : 0;
+    total += v;
+  }
+  for (long long i = i0; i < i1; ++i) {
+    const long long v = kept[i];
+    kept[i] = base;
+    base += v;
+  }
+  __syncthreads();  // (the prefixes of all pairs are in place)
+  auto first_of = [&](int p) { return p < npairs ? kept[p] : total; };
+  int cutp = npairs;
+  for (int p = tid; p < npairs; p += VF_OFF_THREADS) {
+    const long long o = first_of(p), c = first_of(p + 1) - o;
+    if (c > 0 && o + c > out_cap) cutp = min(cutp, p);
+  }
+  for (int off = 32; off > 0; off >>= 1) cutp = min(cutp, __shfl_xor(cutp, off, 64));
+  if (lane == 0) red[wave] = cutp;
+  __syncthreads();
+  for (int w = 0; w < VF_OFF_THREADS / 64; ++w) cutp = min(cutp, red[w]);
+  const long long stop = first_of(cutp);
+  for (int p = tid; p < npairs; p += VF_OFF_THREADS) {
+    const long long o = first_of(p), c = first_of(p + 1) - o;
+    const int fl = models[p].flags | (p >= cutp ? BRISK_PAIR_MATCHES_CUT : 0);
+    models[p].flags = fl;
+    counts[p] = (int)c;  // (a pair has fewer than 2^31 records)
+    flags[p] = fl;
+    offsets[p] = p >= cutp ? stop : o;
+  }
+  if (tid == 0) offsets[npairs] = stop;
+}
+
+__global__ void __launch_bounds__(VF_THREADS) k_verify_scatter(const long long* __restrict__ offsets, const BriskDMatch* __restrict__ matches,
+                                                               long long in_cap, const unsigned char* __restrict__ keep,
+                                                               const int* __restrict__ counts, const int* __restrict__ flags,
+                                                               const long long* __restrict__ out_offsets, long long out_cap,
+                                                               BriskDMatch* __restrict__ out) {
+  __shared__ int part[2][VF_WAVES];
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (counts[p] == 0 || (flags[p] & (BRISK_PAIR_MATCHES_CUT | BRISK_PAIR_BAD))) return;  // (a bad pair has no keep bytes)
+  long long begin;
+  int m;
+  if (!vf_range(offsets, p, in_cap, begin, m)) return;
+  const uint4* src = reinterpret_cast<const uint4*>(matches);
+  uint4* dst = reinterpret_cast<uint4*>(out);
+  long long pos = out_offsets[p];
+  for (int c0 = 0, it = 0; c0 < m; c0 += VF_THREADS, ++it) {
+    const int i = c0 + tid;
+    const bool k = i < m && keep[begin + i] != 0;
+    const unsigned long long b = __ballot(k);
+    if (lane == 0) part[it & 1][wave] = __popcll(b);
+    __syncthreads();  // (one barrier a chunk: the totals alternate between two rows)
+    int before = __popcll(b & ((1ull << lane) - 1ull)), all = 0;
+#pragma unroll
+    for (int w = 0; w < VF_WAVES; ++w) {
+      const int v = part[it & 1][w];
+      before += w < wave ? v : 0;
+      all += v;
+    }
+    if (k && pos + before < out_cap) dst[pos + before] = src[begin + i];  // (always inside while the arrays did not change between the passes)
+    pos += all;
+  }
+}
+
+void brisk_launch_pair_verify(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK, const BriskPairSpec& P,
+                              int rows_cap, const long long* offsets, const BriskDMatch* matches, long long in_cap, const BriskPairVerify& V,
+                              unsigned char* keep, long long* kept, long long out_cap, BriskPairModel* models, int* counts, int* flags,
+                              long long* out_offsets, BriskDMatch* out, hipStream_t s) {
+  const int np = P.npairs;
+  hipLaunchKernelGGL(k_verify_ransac, dim3(np), dim3(VF_THREADS), 0, s, Q, T, QK, TK, P, rows_cap, offsets, matches, in_cap, V, keep, kept,
+                     models);
+  hipLaunchKernelGGL(k_verify_offsets, dim3(1), dim3(VF_OFF_THREADS), 0, s, kept, np, out_cap, models, counts, flags, out_offsets);
+  hipLaunchKernelGGL(k_verify_scatter, dim3(np), dim3(VF_THREADS), 0, s, offsets, matches, in_cap, keep, counts, flags, out_offsets, out_cap,
+                     out);
+}

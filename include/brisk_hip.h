@@ -575,6 +575,70 @@ int brisk_hip_pair_matches_download(brisk_hip_ctx* ctx, const brisk_hip_dmatch* 
  * BRISK_HIP_ERR_CAPACITY when a pair carries BRISK_HIP_ROWS_CUT (the other flags are information, not errors). */
 int brisk_hip_pair_matches_wait(brisk_hip_ctx* ctx, unsigned ticket, int* pairs_flagged);
 
+/* ---- a batch's pair matches checked against a homography, on the device ---------------------------------------------------------
+ * What survives the selection passed a descriptor test only; nothing says that a pair's matches agree with each other
+ * geometrically, and one wrong match that wins a train row starts a wrong track AND takes the row from the right match (a loser
+ * never falls back).  The reference judges matches by their transfer error under a homography (brisk/src/test/test-match.cc:49-126);
+ * this call does it with a model estimated from the pair's own records - one call between brisk_hip_select_pair_matches_device and
+ * brisk_hip_link_tracks_device, packed lists in, packed lists of the same format out.  csrc/brisk_pair_verify.h is the one
+ * definition of the rule; all of its arithmetic is IEEE fp64 + - x in a fixed order, so the kept lists are reproducible bit for bit.
+ * PAIRS AND RECORDS.  Pair p = (a, b) of `pairs` as the pair matchers resolve it (both forms); query / train give the frames' row
+ * counts (their descriptors are not read), query_kps / train_kps the keypoints.  Its records are d_matches[d_offsets[p] ..
+ * d_offsets[p + 1]), m of them.  Record j is USABLE iff 0 <= queryIdx < lim_a, 0 <= trainIdx < lim_b (lim = min(max(count, 0),
+ * rows_cap), the rows that exist for the linker) and the x and y of both keypoints are finite; nothing is read from the keypoint
+ * sets for any other record, which is never an inlier and never kept.
+ * THE RULE.  Hypothesis h (0 <= h < hypotheses) samples four distinct records from a hash of (seed, p, h) and builds the
+ * homography H, query -> train, that maps its four query points on its four train points - without a division, from the two
+ * projective bases; it is INVALID if m < 4, if a sampled record is unusable or if three of the four points of a side are collinear.
+ * A usable record (x, y) -> (x', y') is an INLIER iff z = (H6 x + H7 y) + H8 has the sign of the sample's first point and
+ * |H (x, y, 1) - z (x', y', 1)|^2 <= max_error^2 z^2: a transfer error of at most max_error pixels in the train frame.  max_error
+ * <= 0 or NaN: nothing is an inlier.  The WINNER is the valid hypothesis with the most inliers, ties to the smallest h; the model is
+ * ACCEPTED iff there is one and it has at least min_inliers inliers.
+ * KEPT, in the order of the input: the winner's inliers of an accepted pair; of any other pair the usable records if
+ * keep_unverified != 0, else nothing.  A pair whose d_pairs entry lies outside its sets, or whose offsets are no range inside
+ * [0, in_cap] (or span 2^31 records or more), is BAD: nothing of it is read or kept.
+ * Not done here: a refit of the model to all inliers, fundamental or essential matrices, adaptive stopping. */
+typedef struct brisk_hip_pair_verify {
+  float max_error;     /* pixels, in the train frame */
+  int hypotheses;      /* 1 ... 4096 */
+  int min_inliers;     /* >= 4 */
+  int keep_unverified; /* pairs without an accepted model: 0 = keep nothing, else keep their usable records */
+  unsigned seed;
+} brisk_hip_pair_verify;
+typedef struct brisk_hip_pair_model { /* 96 bytes, 8-byte aligned */
+  double h[9];                        /* the winner's H, every element divided by the one of largest magnitude (the first on a tie);
+                                         nine zeros without a valid hypothesis */
+  int records, usable, inliers;       /* m, the usable ones, the winner's inliers */
+  int hypothesis;                     /* the winner, -1: none valid */
+  int valid;                          /* valid hypotheses */
+  int flags;                          /* as d_out_flags[p] */
+} brisk_hip_pair_model;
+#define BRISK_HIP_PAIR_NO_MODEL 0x8 /* the pair has no accepted model (a BAD pair has none either) */
+/* d_offsets [npairs + 1] / d_matches: the lists a selection with matches_cap = in_cap wrote for these npairs = pairs->npairs pairs
+ * and this rows_cap; in_cap bounds the INPUT (d_matches holds in_cap records, no offset lies beyond it), out_cap the output.
+ * Outputs, all in caller-provided DEVICE memory:
+ *   d_models      [npairs]      the pairs' models
+ *   d_out_counts  [npairs]      records kept for pair p
+ *   d_out_flags   [npairs]      BRISK_HIP_PAIR_BAD, BRISK_HIP_PAIR_NO_MODEL; BRISK_HIP_ROWS_CUT = this pair and every pair behind it
+ *                               did not fit out_cap: their counts are still reported, nothing of them is stored, their offsets stay
+ *                               at the total (the cut of brisk_hip_select_pair_matches_device)
+ *   d_out_offsets [npairs + 1]  exclusive prefix sums of the stored counts; d_out_offsets[npairs] = records stored
+ *   d_out_matches [out_cap]     the kept records, byte-identical to the source records; nothing behind d_out_offsets[npairs] is
+ *                               written.  It must not overlap d_matches.
+ * Asynchronous on `stream` (hipStream_t, NULL = the context's stream), no host synchronisation, no allocation per call once the
+ * context's scratch has grown to the call's size (in_cap bytes - one per input record - and npairs sums).
+ * BRISK_HIP_ERR_ARG, before anything is launched: NULL pairs or verify, npairs < 0, rows_cap < 1, in_cap < 0, out_cap < 0, hypotheses
+ * outside 1 ... 4096, min_inliers < 4, and - with npairs > 0 - a NULL set, a descriptor set without counts or with frames /
+ * count_stride < 1, an arithmetic-form frame outside its set, the keypoint-set errors of the gated matchers, a NULL or misaligned
+ * array (d_matches / d_out_matches 16-byte and NULL allowed when their capacity is 0, d_offsets / d_out_offsets / d_models 8-byte, the
+ * int arrays 4-byte).  npairs == 0: BRISK_HIP_OK, d_out_offsets[0] = 0 (d_out_offsets NULL is then allowed too). */
+int brisk_hip_verify_pair_matches_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                         const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                         const brisk_hip_pair_spec* pairs, int rows_cap, const long long* d_offsets,
+                                         const brisk_hip_dmatch* d_matches, long long in_cap, const brisk_hip_pair_verify* verify,
+                                         long long out_cap, brisk_hip_pair_model* d_models, int* d_out_counts, int* d_out_flags,
+                                         long long* d_out_offsets, brisk_hip_dmatch* d_out_matches, void* stream);
+
 /* ---- a batch's pair matches linked into feature tracks, on the device ----------------------------------------------------------
  * What every consumer of a frame-to-previous-frame matcher does next: "row q of frame i matched row t of frame i - 1" becomes
  * tracks - which keypoints are the same point seen again, since when, which tracks are long enough to use.  An integer problem

@@ -49,6 +49,13 @@ With --tracks-download (k-NN only, profiles/track_download.json) what getting th
 plus D / T, D / P, the spread of T's windows, the bytes that cross the link per batch in D and in P, and whether D's arrays equal
 the list call's arrays joined with batch_download_all's keypoints on the host (--stats-pass: D iterations only, for the kernel
 trace behind profiles/track_download_kernel_stats.csv).
+With --verify (k-NN only, profiles/verify_pairs.json) what checking the matches against a homography adds, two windows:
+  T  --tracks' window T: detect + describe + match + select + link + list
+  V  T with brisk_hip_verify_pair_matches_device (--hypotheses 256, --max-error 3, --min-inliers 8, pairs without a model keep their
+     usable records) between select and link: the linker reads the verified lists
+plus V / T beside the spread of both windows, the HIP-event time of the verify call (three launches; a `rocprofv3 --kernel-trace
+--stats` pass around --verify --stats-pass gives the single kernels), the records per pair that go in and come out, the pairs with
+an accepted model, and whether the device's arrays equal the NumPy restatement of the rule on one batch's downloaded lists.
 Usage: python tools/bench_match_pairs.py [--repeats 5] [--window 0.4] [--rows-cap 2048] [--radius R [--cap N]] [--gate ...] [--out FILE]
        --stats-pass: warm-up + a few B iterations (with --gate: B, G and I) only, nothing written (the run a
        `rocprofv3 --kernel-trace --stats` pass wraps; its kernel statistics are kept as profiles/match_pairs_kernel_stats.csv)"""
@@ -325,6 +332,142 @@ def tracks_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
     ctx.close()
 
 
+def verify_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
+    """--verify: windows T and V (see the module's text); writes a.out"""
+    from test_abi_verify import restated_verify
+    st = work.cuda_stream
+    select = B.MatchSelect(float("inf"), 0.8, 1)
+    verify = B.PairVerify(a.max_error, a.hypotheses, a.min_inliers, 1, 2024)
+    spec = B.PairSpec(n - 1, 1, 1, 0, 1, None)
+    L, h = ctx._L, ctx._h
+    mcap = (n - 1) * cap                                            # (one match per row at the most)
+
+    def lists_of():
+        return (torch.zeros((mcap, 4), dtype=torch.int32, device=dev), torch.zeros(n - 1, dtype=torch.int32, device=dev),
+                torch.zeros(n - 1, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int64, device=dev))
+
+    sel, ver = lists_of(), lists_of()
+    models = torch.zeros((n - 1, 12), dtype=torch.int64, device=dev)
+    prev, age = (torch.zeros((n, cap), dtype=torch.int32, device=dev) for _ in range(2))
+    track = torch.zeros((n, cap), dtype=torch.int64, device=dev)
+    summary = torch.zeros(8, dtype=torch.int64, device=dev)
+    tcap, ocap = n * cap // 4, n * cap
+    lists = (torch.zeros(tcap, dtype=torch.int64, device=dev), torch.zeros(tcap, dtype=torch.int32, device=dev),
+             torch.zeros(tcap + 1, dtype=torch.int64, device=dev), torch.zeros((ocap, 2), dtype=torch.int32, device=dev),
+             torch.zeros(4, dtype=torch.int64, device=dev))
+    seed = B.TrackSeed(None, None, 0, summary.data_ptr())
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    m, cnt, rows = outs["B"]
+
+    def run(verified, timed=False):
+        run_b0()
+        ctx.check(L.brisk_hip_select_pair_matches_device(h, m.data_ptr(), cnt.data_ptr(), rows.data_ptr(), n - 1, cap, k, C.byref(select), mcap,
+                                                         sel[1].data_ptr(), sel[2].data_ptr(), sel[3].data_ptr(), sel[0].data_ptr(), st))
+        dset, _ = ctx.batch_desc_set()
+        src = sel
+        if verified:
+            kps = ctx.batch_kp_set()
+            if timed:
+                ev[0].record(work)
+            ctx.check(L.brisk_hip_verify_pair_matches_device(h, C.byref(dset), C.byref(dset), C.byref(kps), C.byref(kps), C.byref(spec), cap,
+                                                             sel[3].data_ptr(), sel[0].data_ptr(), mcap, C.byref(verify), mcap,
+                                                             models.data_ptr(), ver[1].data_ptr(), ver[2].data_ptr(), ver[3].data_ptr(),
+                                                             ver[0].data_ptr(), st))
+            if timed:
+                ev[1].record(work)
+            src = ver
+        ptr, stride = ctx._node_rows((dset, 0, 1))
+        ctx.check(L.brisk_hip_link_tracks_device(h, ptr, stride, n, cap, src[3].data_ptr(), src[0].data_ptr(), C.byref(seed), prev.data_ptr(),
+                                                 track.data_ptr(), age.data_ptr(), summary.data_ptr(), st))
+        ctx.check(L.brisk_hip_list_tracks_device(h, ptr, stride, n, cap, prev.data_ptr(), track.data_ptr(), age.data_ptr(), 3, tcap, ocap,
+                                                 lists[0].data_ptr(), lists[1].data_ptr(), lists[2].data_ptr(), lists[3].data_ptr(),
+                                                 lists[4].data_ptr(), st))
+
+    runs = {"T": lambda: run(False), "V": lambda: run(True)}
+    order = "TV"
+    for v in order + "TV":                                          # warm-up: buffers sized, scratch grown
+        runs[v]()
+        torch.cuda.synchronize()
+    if a.stats_pass:
+        for _ in range(8):
+            runs["V"]()
+        torch.cuda.synchronize()
+        return
+
+    # one batch against the restatement of the rule on its downloaded lists and keypoints
+    runs["V"]()
+    torch.cuda.synchronize()
+    dset, dim = ctx.batch_desc_set()
+    ints = dset.count_stride
+    node_rows = torch.as_tensor(DeviceInts(dset.d_counts, (n - 1) * ints + 1), device=dev)[::ints].cpu().numpy()
+    xy = []
+    for f in range(n):
+        kp = ctx.batch_download(f, True, strings=dim)[0]
+        xy.append(np.stack([kp["x"], kp["y"]], axis=1).astype(np.float32).reshape(-1, 2))
+    so, sm = sel[3].cpu().numpy(), sel[0].cpu().numpy().view(B.DMATCH).reshape(-1)
+    want = restated_verify([(p + 1, p) for p in range(n - 1)], node_rows, node_rows, cap, xy, xy, so, sm[:int(so[-1])],
+                           (a.max_error, a.hypotheses, a.min_inliers, 1, 2024), mcap, mcap)
+    got_models = models.cpu().numpy().reshape(-1).view(B.PAIR_MODEL)
+    stored = int(want[3][-1])
+    identical = bool(got_models.tobytes() == want[0].tobytes() and ver[1].cpu().numpy().tobytes() == want[1].tobytes() and
+                     ver[2].cpu().numpy().tobytes() == want[2].tobytes() and ver[3].cpu().numpy().tobytes() == want[3].tobytes() and
+                     ver[0].cpu().numpy()[:stored].tobytes() == want[4].tobytes())
+
+    call_ms = []
+    for _ in range(max(a.repeats, 5)):
+        run(True, timed=True)
+        torch.cuda.synchronize()
+        call_ms.append(ev[0].elapsed_time(ev[1]))
+
+    fps = {v: [] for v in order}
+    for _ in range(a.repeats):
+        for v in order:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            calls = 0
+            while True:
+                runs[v]()
+                calls += 1
+                if time.perf_counter() - t0 >= a.window:
+                    break
+            torch.cuda.synchronize()
+            fps[v].append(calls * n / (time.perf_counter() - t0))
+    med = {v: float(np.median(fps[v])) for v in order}
+    ms = {v: 1e3 * n / med[v] for v in order}
+    spread = {v: (max(fps[v]) - min(fps[v])) / med[v] for v in order}
+    mod = want[0]
+    res = {
+        "workload": "bench.py's stream: %dx%d, threshold %d, %d octaves, %d frames per batch (%d distinct) in HBM; frame-to-previous-frame, "
+                    "k = %d, rows_cap %d, ratio 0.8, one match per row; verify: %d hypotheses, max_error %g, min_inliers %d, "
+                    "keep_unverified 1; tracks of min_len 3" % (W, H, THRESHOLD, OCTAVES, n, nd, k, cap, a.hypotheses, a.max_error, a.min_inliers),
+        "kernel_revision": ctx.kernel_revision(),
+        "device": torch.cuda.get_device_name(0),
+        "windows": {"repeats": a.repeats, "seconds_each": a.window, "order": ", ".join(order) + " alternating; every window ends in a synchronise"},
+        "frames_per_s": {v: round(med[v], 1) for v in order},
+        "frames_per_s_all": {v: [round(x, 1) for x in fps[v]] for v in order},
+        "spread_rel": {v: round(spread[v], 4) for v in order},
+        "ms_per_batch": {v: round(ms[v], 4) for v in order},
+        "verify_ms_per_batch": {"V_minus_T": round(ms["V"] - ms["T"], 4)},
+        "V_over_T_frames_per_s": round(med["V"] / med["T"], 4),
+        "hip_event_ms": {"verify_call_3_launches": {"median": round(float(np.median(call_ms)), 4), "all": [round(x, 4) for x in call_ms]}},
+        "per_batch": {"pairs": n - 1, "hypotheses": a.hypotheses, "records_per_pair_mean": round(float(mod["records"].mean()), 2),
+                      "records_per_pair_max": int(mod["records"].max()), "usable_per_pair_mean": round(float(mod["usable"].mean()), 2),
+                      "kept_per_pair_mean": round(float(want[1].mean()), 2), "pairs_with_a_model": int((mod["flags"] & B.PAIR_NO_MODEL == 0).sum()),
+                      "inliers_per_model_mean": round(float(mod["inliers"][mod["flags"] & B.PAIR_NO_MODEL == 0].mean()), 2)
+                      if (mod["flags"] & B.PAIR_NO_MODEL == 0).any() else 0.0},
+        "V_equals_the_restated_rule": identical,
+        "legend": {"T": "detect_describe_batch + match_knn_pairs + select + brisk_hip_link_tracks_device + brisk_hip_list_tracks_device on one stream",
+                   "V": "T with brisk_hip_verify_pair_matches_device between select and link"},
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+    ext.close()
+    ctx.close()
+
+
 def tracks_download_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
     """--tracks-download: windows T, D and P (see the module's text); writes a.out"""
     st = work.cuda_stream
@@ -491,6 +634,10 @@ def main():
     ap.add_argument("--tracks", action="store_true", help="windows B (match + select) and T (B + link_tracks + list_tracks)")
     ap.add_argument("--tracks-download", action="store_true",
                     help="windows T (--tracks' T), D (tracks_download in place of the list call) and P (list, synchronise, copies, batch_download_all)")
+    ap.add_argument("--verify", action="store_true", help="windows T (--tracks' T) and V (T with verify_pair_matches between select and link)")
+    ap.add_argument("--hypotheses", type=int, default=256, help="--verify: hypotheses per pair")
+    ap.add_argument("--max-error", type=float, default=3.0, help="--verify: the inlier threshold in pixels")
+    ap.add_argument("--min-inliers", type=int, default=8, help="--verify: inliers an accepted model needs")
     a = ap.parse_args()
 
     radius = a.radius
@@ -513,6 +660,11 @@ def main():
             ap.error("--tracks-download measures the k-NN pair call: without --radius / --gate / --export / --tracks")
         if a.out is None:
             a.out = os.path.join(ROOT, "profiles", "track_download.json")
+    if a.verify:
+        if radius is not None or gate or a.export or a.tracks or a.tracks_download:
+            ap.error("--verify measures the k-NN pair call: without --radius / --gate / --export / --tracks / --tracks-download")
+        if a.out is None:
+            a.out = os.path.join(ROOT, "profiles", "verify_pairs.json")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", ("match_radius_pairs" if radius is not None else "match_pairs") +
                              ("_gated" if gate else "") + ".json")
@@ -566,6 +718,9 @@ def main():
         return
     if a.tracks_download:
         tracks_download_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b)
+        return
+    if a.verify:
+        verify_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b)
         return
 
     vp = C.c_void_p
