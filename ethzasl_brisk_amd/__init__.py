@@ -832,7 +832,9 @@ class Context:
     def track_points(self, node_rows, nodes, rows_cap, list_offsets, list_obs, list_summary, kps=None, kp_first=0, kp_step=1, stream=None):
         """brisk_hip_track_points_device on what list_tracks returned (list_offsets, list_obs, list_summary).  kps: a KpSet (None =
         the last batch's); node i's keypoints are frame kp_first + i * kp_step of it.  Returns the device tensor points [obs_cap, 9]
-        int32 - TRACK_POINT records -; only the points of the stored observations are written.  Asynchronous on `stream`."""
+        int32 - TRACK_POINT records -; only the points of the stored observations are written.  Asynchronous on `stream`, ordered
+        behind the context's previous call and in front of its next (the next batch overwrites the keypoints), whichever streams
+        those use."""
         import torch
         ptr, stride = self._node_rows(node_rows)
         if kps is None:

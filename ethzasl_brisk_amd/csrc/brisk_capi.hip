@@ -2447,9 +2447,14 @@ int brisk_hip_track_points_device(brisk_hip_ctx* ctx, const int* d_node_rows, in
   if (const char* msg = track_kps_check(kps, nodes, kp_first, kp_step)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  // no workspace of the context is written, but the keypoints usually ARE the last batch's result buffer (and the node rows its
+  // counts): the stream is ordered behind that batch, and the next batch (which overwrites them) behind this call
+  if (workspace_acquire(ctx, st)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
+  WorkspaceGuard guard(ctx, st);
   brisk_launch_tracklist_points(d_node_rows, node_rows_stride, nodes, rows_cap, d_list_offsets, d_list_obs, d_list_summary, obs_cap, kps->d_kps,
                                 kps->frame_pitch, kp_first, kp_step, d_points, st);
   HIPCHK(ctx, hipGetLastError());
+  if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
   return BRISK_HIP_OK;
 }
 

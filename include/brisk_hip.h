@@ -725,7 +725,9 @@ typedef struct brisk_hip_track_point { /* 36 bytes, 4-byte aligned */
 } brisk_hip_track_point;
 /* Device form: the points of a list that brisk_hip_list_tracks_device wrote with this obs_cap.  Writes d_points[0 ..
  * d_list_offsets[stored]), stored = d_list_summary[2] read on the device, nothing behind it; asynchronous on `stream`, no scratch,
- * no allocation.  BRISK_HIP_ERR_ARG, before anything is launched: the chain's errors, obs_cap < 0, a NULL d_list_offsets /
+ * no allocation.  Like every call of the context it is ordered behind the context's previous call and in front of its next,
+ * whichever streams those use: the keypoints and the node rows usually are the last batch's buffers, which the next batch
+ * overwrites.  BRISK_HIP_ERR_ARG, before anything is launched: the chain's errors, obs_cap < 0, a NULL d_list_offsets /
  * d_list_summary, a NULL d_list_obs / d_points with obs_cap > 0, d_list_* arrays that are not 8-byte aligned, a d_points that is not
  * 4-byte aligned, NULL kps, a NULL or misaligned d_kps, a frame_pitch that is negative or no multiple of 4, kp_first < 0 or
  * kp_first + (nodes - 1) * kp_step < 0. */
