@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "brisk_hip_batch_kp_set", "brisk_hip_match_knn_pairs_gated_device", "brisk_hip_match_radius_pairs_gated_device",
     "brisk_hip_select_pair_matches_device", "brisk_hip_pair_matches_download", "brisk_hip_pair_matches_wait",
     "brisk_hip_verify_pair_matches_device",
+    "brisk_hip_match_knn_pairs_guided_device", "brisk_hip_match_radius_pairs_guided_device",
     "brisk_hip_link_tracks_device", "brisk_hip_list_tracks_device",
     "brisk_hip_track_points_device", "brisk_hip_tracks_download", "brisk_hip_tracks_wait",
 ]
@@ -97,6 +98,18 @@ class MatchGate(C.Structure):
     @classmethod
     def all_pass(cls):
         return cls(-float("inf"), float("inf"), -float("inf"), float("inf"), -1)
+
+
+class MatchGuide(C.Structure):
+    """brisk_hip_match_guide: the gate's window around the centre C = H_p(Q) the pair's model gives query keypoint Q (bounds on T - C,
+    max_octave_diff between Q and T); fallback: a pair without a usable model - 0 = its rows match nothing, else C = Q"""
+    _fields_ = [("window", MatchGate), ("fallback", C.c_int)]
+
+    @classmethod
+    def around(cls, radius, max_octave_diff=-1, fallback=0):
+        """a square window of +-radius pixels"""
+        r = float(radius)
+        return cls(MatchGate(-r, r, -r, r, int(max_octave_diff)), int(fallback))
 
 
 class MatchSelect(C.Structure):
@@ -336,6 +349,12 @@ def load_library():
     L.brisk_hip_verify_pair_matches_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
                                                        C.POINTER(PairSpec), C.c_int, vp, vp, C.c_longlong, C.POINTER(PairVerify),
                                                        C.c_longlong, vp, vp, vp, vp, vp, vp]
+    L.brisk_hip_match_knn_pairs_guided_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
+                                                          C.POINTER(PairSpec), vp, C.POINTER(MatchGuide), C.c_int, C.c_int, C.c_int,
+                                                          vp, vp, vp, vp]
+    L.brisk_hip_match_radius_pairs_guided_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
+                                                             C.POINTER(PairSpec), vp, C.POINTER(MatchGuide), C.c_int, C.c_float, C.c_int,
+                                                             C.c_int, vp, vp, vp, vp]
     L.brisk_hip_link_tracks_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(TrackSeed), vp, vp, vp, vp, vp]
     L.brisk_hip_list_tracks_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_longlong, C.c_longlong,
                                                vp, vp, vp, vp, vp, vp]
@@ -674,12 +693,7 @@ class Context:
             self.check(self._L.brisk_hip_match_knn_pairs_device(self._h, C.byref(query), C.byref(train), C.byref(pairs), int(dim_bytes), int(k),
                                                                 int(bool(cross_check)), int(rows_cap), m.data_ptr(), cnt.data_ptr(),
                                                                 rows.data_ptr(), C.c_void_p(stream) if stream else None))
-        if not download:
-            return out
-        torch.cuda.synchronize(self.device)
-        hm = m.cpu().numpy().view(DMATCH).reshape(n, rows_cap, max(k, 1))
-        hc, hr = cnt.cpu().numpy(), rows.cpu().numpy()
-        return [[hm[p, q, :hc[p, q]].copy() for q in range(min(max(int(hr[p]), 0), rows_cap))] for p in range(n)]
+        return self._knn_rows(out, n, rows_cap, k) if download else out
 
     def match_radius_pairs(self, query, train, pairs, max_distance, cap_per_query, rows_cap=None, stream=None, dim_bytes=None, out=None,
                            download=False, gate=None, query_kps=None, train_kps=None):
@@ -702,14 +716,65 @@ class Context:
             self.check(self._L.brisk_hip_match_radius_pairs_device(self._h, C.byref(query), C.byref(train), C.byref(pairs), int(dim_bytes),
                                                                    float(max_distance), cpq, int(rows_cap), m.data_ptr(), cnt.data_ptr(),
                                                                    rows.data_ptr(), C.c_void_p(stream) if stream else None))
-        if not download:
-            return out
+        return self._radius_rows(out, n, rows_cap, cpq) if download else out
+
+    def _knn_rows(self, out, n, rows_cap, k):
+        """download=True of the k-NN pair matchers: synchronises; per pair the list of per-query DMATCH arrays"""
+        import torch
+        m, cnt, rows = out
+        torch.cuda.synchronize(self.device)
+        hm = m.cpu().numpy().view(DMATCH).reshape(n, rows_cap, max(k, 1))
+        hc, hr = cnt.cpu().numpy(), rows.cpu().numpy()
+        return [[hm[p, q, :hc[p, q]].copy() for q in range(min(max(int(hr[p]), 0), rows_cap))] for p in range(n)]
+
+    def _radius_rows(self, out, n, rows_cap, cpq):
+        """download=True of the radius pair matchers: synchronises; (rows, counts)"""
+        import torch
+        m, cnt, rows = out
         torch.cuda.synchronize(self.device)
         hm = m.cpu().numpy().view(DMATCH).reshape(n, rows_cap, cpq)
         hc, hr = cnt.cpu().numpy(), rows.cpu().numpy()
         nrows = [min(max(int(hr[p]), 0), rows_cap) for p in range(n)]
         return ([[hm[p, q, :min(int(hc[p, q]), cpq)].copy() for q in range(nrows[p])] for p in range(n)],
                 [hc[p, :nrows[p]].copy() for p in range(n)])
+
+    # -- the pairs matched again inside a window around each pair's model --
+    def _guide_args(self, models, guide, query_kps, train_kps):
+        """keypoint sets left out = the last batch's; models: the tensor verify_pair_matches returns, or a device pointer"""
+        if query_kps is None or train_kps is None:
+            own = self.batch_kp_set()
+            query_kps = own if query_kps is None else query_kps
+            train_kps = own if train_kps is None else train_kps
+        ptr = models.data_ptr() if hasattr(models, "data_ptr") else models
+        return C.byref(query_kps), C.byref(train_kps), (C.c_void_p(int(ptr)) if ptr else None), C.byref(guide)
+
+    def match_knn_pairs_guided(self, query, train, pairs, k, models, guide, rows_cap=None, query_kps=None, train_kps=None, stream=None,
+                               dim_bytes=None, out=None, download=False):
+        """brisk_hip_match_knn_pairs_guided_device: match_knn_pairs behind the window of `guide` (a MatchGuide) centred where pair
+        p's model models[p] puts each query keypoint.  models: the tensor verify_pair_matches returns ([npairs, 12] int64, PAIR_MODEL
+        records), or any device pointer to npairs records.  No cross check.  Everything else, and what is returned, as match_knn_pairs
+        with a gate."""
+        n = pairs.npairs
+        dim_bytes, rows_cap, out = self._pairs_prologue(pairs, dim_bytes, rows_cap, k, out)
+        m, cnt, rows = out
+        qk, tk, mp, gp = self._guide_args(models, guide, query_kps, train_kps)
+        self.check(self._L.brisk_hip_match_knn_pairs_guided_device(self._h, C.byref(query), C.byref(train), qk, tk, C.byref(pairs), mp, gp,
+                                                                   int(dim_bytes), int(k), int(rows_cap), m.data_ptr(), cnt.data_ptr(),
+                                                                   rows.data_ptr(), C.c_void_p(stream) if stream else None))
+        return self._knn_rows(out, n, rows_cap, k) if download else out
+
+    def match_radius_pairs_guided(self, query, train, pairs, max_distance, cap_per_query, models, guide, rows_cap=None, query_kps=None,
+                                  train_kps=None, stream=None, dim_bytes=None, out=None, download=False):
+        """brisk_hip_match_radius_pairs_guided_device: match_radius_pairs behind the guide; the conventions of
+        match_knn_pairs_guided, and what is returned as match_radius_pairs."""
+        n, cpq = pairs.npairs, int(cap_per_query)
+        dim_bytes, rows_cap, out = self._pairs_prologue(pairs, dim_bytes, rows_cap, cpq, out)
+        m, cnt, rows = out
+        qk, tk, mp, gp = self._guide_args(models, guide, query_kps, train_kps)
+        self.check(self._L.brisk_hip_match_radius_pairs_guided_device(self._h, C.byref(query), C.byref(train), qk, tk, C.byref(pairs), mp, gp,
+                                                                      int(dim_bytes), float(max_distance), cpq, int(rows_cap), m.data_ptr(),
+                                                                      cnt.data_ptr(), rows.data_ptr(), C.c_void_p(stream) if stream else None))
+        return self._radius_rows(out, n, rows_cap, cpq) if download else out
 
     # -- the pair matchers' exit: selected matches, packed --
     def select_pair_matches(self, out_triple, per_row, select, matches_cap=None, stream=None):

@@ -4,6 +4,7 @@
 
 #include "brisk_common.h"
 #include "brisk_match_gate.h"
+#include "brisk_match_guide.h"
 #include "brisk_match_select.h"
 #include "brisk_pair_verify.h"
 #include "brisk_track_link.h"
@@ -189,6 +190,16 @@ bool brisk_launch_match_knn_pairs_gated(const BriskDescSet& Q, const BriskDescSe
 bool brisk_launch_match_radius_pairs_gated(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
                                            const BriskMatchGate& gate, const BriskPairSpec& P, int words32, float max_distance, int cap,
                                            int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s);
+
+// the gated matchers with the window centred where pair p's model models[p] puts the query keypoint (brisk_match_guide.h): k-NN
+// without the cross check, and radius.  models: device, [npairs], indexed by PAIR
+bool brisk_launch_match_knn_pairs_guided(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
+                                         const BriskPairModel* models, const BriskMatchGuide& guide, const BriskPairSpec& P, int words32, int k,
+                                         int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s);
+bool brisk_launch_match_radius_pairs_guided(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
+                                            const BriskPairModel* models, const BriskMatchGuide& guide, const BriskPairSpec& P, int words32,
+                                            float max_distance, int cap, int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows,
+                                            hipStream_t s);
 
 // ---- the pair matchers' exit: selected matches, packed (brisk_match_export.hip; the rule: brisk_match_select.h) ----
 // flags of a pair (mirror BRISK_HIP_PAIR_* / BRISK_HIP_ROWS_CUT of brisk_hip.h)

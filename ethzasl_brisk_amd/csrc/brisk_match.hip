@@ -22,6 +22,9 @@
 //   k_match_knn_fused           k <= 2, one query set against one train set, 16 waves per workgroup
 //   k_match_knn_pairs[_gated]   k <= 2 for the frame pairs of a batch in one launch (mp_body), with the cross check fused;
 //                               gated: only rows whose keypoints pass brisk_match_gate.h's predicate, no top-up entry
+//   k_guided_knn_pairs          the gated k-NN kernel (no cross check) with the window centred where the pair's model puts the
+//                               lane's query keypoint (brisk_match_guide.h): a per-lane fp64 prologue in front of the same scan
+//   k_guided_radius_pairs       the gated radius kernel, guided the same way
 //   k_match_radius_pairs[_gated], k_match_radius_pairs_one
 //                               radius matching in the same shape (mrp_body): hits collected in a short LDS list per
 //                               query and ranked; a query with more hits than the list holds is redone by one wave
@@ -390,6 +393,17 @@ struct MpGate {
 __device__ __forceinline__ const BriskKeyPoint* mp_kp(const char* kps, int r) {
   return reinterpret_cast<const BriskKeyPoint*>(kps + (long)r * (long)sizeof(BriskKeyPoint));
 }
+// The guide (brisk_match_guide.h): the lane of query keypoint kp in a pair whose model record is *M - the gate's lane with the position
+// replaced by the centre H(kp).  A workgroup is one pair, so M is wave-uniform (scalar loads, once per workgroup); the fp64 work is
+// per lane and done before the scan, which keeps the lane alone: the nine model words and the temporaries are dead in the row loop.
+// false: the row has no centre.
+__device__ __forceinline__ bool mpu_lane(const BriskPairModel* __restrict__ M, bool guided, const BriskMatchGate& window, int fallback,
+                                         const BriskKeyPoint* kp, BriskGateLane& L) {
+  const BriskHomography H{M->h[0], M->h[1], M->h[2], M->h[3], M->h[4], M->h[5], M->h[6], M->h[7], M->h[8]};
+  const BriskMatchGuide U{window, fallback};
+  return brisk_guide_lane(U, guided, H, kp->x, kp->y, kp->octave, L);
+}
+
 // The gated scans.  The keypoint of the wave-uniform row comes through the same scalar loads as the row itself, MPG_CHUNK records
 // ahead of the rows they belong to (one wait for the chunk, not one per row); the predicate is a handful of VALU compares whose
 // result lives in a lane mask.  A row that NO lane of the wave may match is left without its descriptor loads and popcounts: a
@@ -430,15 +444,15 @@ __device__ __forceinline__ void mpg_scan(const unsigned (&qv)[W32], const uint8_
 }
 
 // this wave's slice of the n rows of one frame against the lane's descriptor: the two smallest keys.  GATE: `self` is the lane's
-// own keypoint, kps the records of the rows passing by
+// own keypoint, kps the records of the rows passing by; `guided` (the guided kernels): the lane as mpu_lane made it, instead of self's
 template <int W32, bool GATE, bool SWAP>
 __device__ __forceinline__ void mp_scan_slice(const unsigned (&v)[W32], const uint8_t* rows, int pitch, bool aligned, int n, int wave,
                                               const BriskMatchGate& g, const BriskKeyPoint* self, bool on, const char* kps, unsigned& b1,
-                                              unsigned& b2) {
+                                              unsigned& b2, const BriskGateLane* guided = nullptr) {
   const int per = (n + MP_WAVES - 1) / MP_WAVES;
   const int t0 = __builtin_amdgcn_readfirstlane(wave * per), t1 = min(n, t0 + per);
   if (GATE) {
-    const BriskGateLane L = brisk_gate_lane(g, self->x, self->y, self->octave);
+    const BriskGateLane L = guided ? *guided : brisk_gate_lane(g, self->x, self->y, self->octave);
     if (aligned) mpg_scan<W32, true, SWAP>(v, rows, pitch, t0, t1, g, L, on, kps, b1, b2);
     else mpg_scan<W32, false, SWAP>(v, rows, pitch, t0, t1, g, L, on, kps, b1, b2);
   } else {
@@ -454,10 +468,13 @@ __device__ __forceinline__ void mp_scan_slice(const unsigned (&v)[W32], const ui
 // between workgroups.
 // GATE: a lane the gate forbids keeps MF_NO_KEY, so a row holds min(k, allowed rows) REAL matches and is never topped up; in the
 // cross check a lane without a forward match takes no part.
-template <int W32, bool CROSS, bool GATE>
+// GUIDE (with GATE, without CROSS): `gate` is the guide's window, centred by models[p] (mpu_lane); a lane whose row has no centre
+// takes no part, and a pair without a usable model and without the fallback has empty rows.
+template <int W32, bool CROSS, bool GATE, bool GUIDE = false>
 __device__ __forceinline__ void mp_body(const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, int pair0, int k, int rows_cap,
                                         BriskDMatch* __restrict__ out, int* __restrict__ out_count, int* __restrict__ pair_rows,
-                                        const BriskKpSet& QK, const BriskKpSet& TK, const BriskMatchGate& gate) {
+                                        const BriskKpSet& QK, const BriskKpSet& TK, const BriskMatchGate& gate,
+                                        const BriskPairModel* __restrict__ models = nullptr, int fallback = 0) {
   __shared__ unsigned part[MP_WAVES][2][64];
   __shared__ unsigned fwd[64];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -467,7 +484,8 @@ __device__ __forceinline__ void mp_body(const BriskDescSet& Q, const BriskDescSe
   const int q = blockIdx.x * 64 + lane;
   BriskDMatch* orow = out + ((long)p * rows_cap + q) * k;
   int* ocnt = out_count + (long)p * rows_cap + q;
-  if (R.n_b == 0) {  // nothing to match against: empty rows (the reference tops up only when some train image has rows)
+  const bool guided = GUIDE && brisk_guide_guided(models[p].hypothesis, models[p].flags);  // (wave-uniform)
+  if (R.n_b == 0 || (GUIDE && !guided && fallback == 0)) {  // nothing to match against: empty rows (the reference tops up only when some train image has rows)
     if (wave == 0 && q < R.rows) *ocnt = 0;
     return;
   }
@@ -479,8 +497,14 @@ __device__ __forceinline__ void mp_body(const BriskDescSet& Q, const BriskDescSe
   {
     unsigned qv[W32];
     mp_load_row<W32>(qrows + (long)min(q, R.rows - 1) * Q.row_pitch, R.q_aligned, qv);
-    mp_scan_slice<W32, GATE, false>(qv, trows, T.row_pitch, R.t_aligned, R.n_b, wave, gate, GATE ? mp_kp(qk, min(q, R.rows - 1)) : nullptr,
-                                    q < R.rows, tk, b1, b2);
+    if (GUIDE) {
+      BriskGateLane L;
+      const bool has = mpu_lane(models + p, guided, gate, fallback, mp_kp(qk, min(q, R.rows - 1)), L);
+      mp_scan_slice<W32, GATE, false>(qv, trows, T.row_pitch, R.t_aligned, R.n_b, wave, gate, nullptr, q < R.rows && has, tk, b1, b2, &L);
+    } else {
+      mp_scan_slice<W32, GATE, false>(qv, trows, T.row_pitch, R.t_aligned, R.n_b, wave, gate, GATE ? mp_kp(qk, min(q, R.rows - 1)) : nullptr,
+                                      q < R.rows, tk, b1, b2);
+    }
   }
   part[wave][0][lane] = b1;
   part[wave][1][lane] = b2;
@@ -543,6 +567,14 @@ __global__ void __launch_bounds__(MP_WAVES * 64) k_match_knn_pairs_gated(const B
                                                                           BriskDMatch* __restrict__ out, int* __restrict__ out_count,
                                                                           int* __restrict__ pair_rows) {
   mp_body<W32, CROSS, true>(Q, T, P, pair0, k, rows_cap, out, out_count, pair_rows, QK, TK, gate);
+}
+template <int W32>
+__global__ void __launch_bounds__(MP_WAVES * 64) k_guided_knn_pairs(const BriskDescSet Q, const BriskDescSet T, const BriskKpSet QK,
+                                                                     const BriskKpSet TK, const BriskPairModel* __restrict__ models,
+                                                                     const BriskMatchGuide guide, const BriskPairSpec P, int pair0, int k,
+                                                                     int rows_cap, BriskDMatch* __restrict__ out, int* __restrict__ out_count,
+                                                                     int* __restrict__ pair_rows) {
+  mp_body<W32, false, true, true>(Q, T, P, pair0, k, rows_cap, out, out_count, pair_rows, QK, TK, guide.window, models, guide.fallback);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -672,10 +704,12 @@ __device__ __forceinline__ void mrp_dense(int* bins, const unsigned (&uq)[W32], 
 }
 
 // the workgroup's 64 query rows [blockIdx.x * 64, ...) of `rows` against the n_b train rows; out / out_count: row 0 of this query set
-template <int W32, bool GATE = false>
+// GUIDE (with GATE): G.g is the guide's window, centred by the pair's model record *model (mpu_lane)
+template <int W32, bool GATE = false, bool GUIDE = false>
 __device__ __forceinline__ void mrp_body(const uint8_t* qrows, int q_pitch, bool q_aligned, int rows, const uint8_t* trows, int t_pitch,
                                          bool t_aligned, int n_b, float max_distance, int cap, int img, BriskDMatch* __restrict__ out,
-                                         int* __restrict__ out_count, const MpGate& G = MpGate()) {
+                                         int* __restrict__ out_count, const MpGate& G = MpGate(),
+                                         const BriskPairModel* __restrict__ model = nullptr, bool guided = false, int fallback = 0) {
   __shared__ int cnt[64];
   __shared__ unsigned list[MRP_LIST][64];
   __shared__ int bins[MP_WAVES][MRP_BINS + 3];
@@ -698,9 +732,12 @@ __device__ __forceinline__ void mrp_body(const uint8_t* qrows, int q_pitch, bool
     const int t0 = wave * per, t1 = min(n_b, t0 + per);
     if (GATE) {
       const BriskKeyPoint* kp = mp_kp(G.qk, min(q, rows - 1));
-      const BriskGateLane L = brisk_gate_lane(G.g, kp->x, kp->y, kp->octave);
-      if (t_aligned) mrpg_scan<W32, true>(qv, trows, t_pitch, t0, t1, thr, G.g, L, q < rows, G.tk, cnt, list, lane);
-      else mrpg_scan<W32, false>(qv, trows, t_pitch, t0, t1, thr, G.g, L, q < rows, G.tk, cnt, list, lane);
+      BriskGateLane L;
+      bool on = q < rows;
+      if (GUIDE) on = mpu_lane(model, guided, G.g, fallback, kp, L) && on;
+      else L = brisk_gate_lane(G.g, kp->x, kp->y, kp->octave);
+      if (t_aligned) mrpg_scan<W32, true>(qv, trows, t_pitch, t0, t1, thr, G.g, L, on, G.tk, cnt, list, lane);
+      else mrpg_scan<W32, false>(qv, trows, t_pitch, t0, t1, thr, G.g, L, on, G.tk, cnt, list, lane);
     } else {
       if (t_aligned) mrp_scan<W32, true>(qv, trows, t_pitch, t0, t1, thr_lane, cnt, list, lane);
       else mrp_scan<W32, false>(qv, trows, t_pitch, t0, t1, thr_lane, cnt, list, lane);
@@ -737,7 +774,11 @@ __device__ __forceinline__ void mrp_body(const uint8_t* qrows, int q_pitch, bool
     BriskGateLane QL = {};
     if (GATE) {
       const BriskKeyPoint* kp = mp_kp(G.qk, qq);  // (wave-uniform)
-      QL = brisk_gate_lane(G.g, kp->x, kp->y, kp->octave);
+      if (GUIDE) {  // (the model is read again: a rare path, and nothing of it stays live across the scan)
+        if (!mpu_lane(model, guided, G.g, fallback, kp, QL)) continue;  // (cannot be: a row without a centre has no hits)
+      } else {
+        QL = brisk_gate_lane(G.g, kp->x, kp->y, kp->octave);
+      }
     }
     if (t_aligned) mrp_dense<W32, true, GATE>(bins[wave], uq, trows, t_pitch, n_b, thr, cap, lane, qq, img, out + (long)qq * cap, G, QL);
     else mrp_dense<W32, false, GATE>(bins[wave], uq, trows, t_pitch, n_b, thr, cap, lane, qq, img, out + (long)qq * cap, G, QL);
@@ -767,6 +808,22 @@ __global__ void __launch_bounds__(MP_WAVES * 64) k_match_radius_pairs_gated(cons
   const MpGate G{gate, QK.kps + (long)R.a * QK.frame_pitch, TK.kps + (long)R.b * TK.frame_pitch};
   mrp_body<W32, true>(mp_frame(Q, R.a), Q.row_pitch, R.q_aligned, R.rows, mp_frame(T, R.b), T.row_pitch, R.t_aligned, R.n_b, max_distance, cap, R.b,
                       out + (long)p * rows_cap * cap, out_count + (long)p * rows_cap, G);
+}
+template <int W32>
+__global__ void __launch_bounds__(MP_WAVES * 64) k_guided_radius_pairs(const BriskDescSet Q, const BriskDescSet T, const BriskKpSet QK,
+                                                                        const BriskKpSet TK, const BriskPairModel* __restrict__ models,
+                                                                        const BriskMatchGuide guide, const BriskPairSpec P, int pair0,
+                                                                        float max_distance, int cap, int rows_cap,
+                                                                        BriskDMatch* __restrict__ out, int* __restrict__ out_count,
+                                                                        int* __restrict__ pair_rows) {
+  const int p = pair0 + blockIdx.y;
+  MpPair R;
+  if (!mp_resolve(Q, T, P, p, false, rows_cap, pair_rows, R)) return;
+  const bool guided = brisk_guide_guided(models[p].hypothesis, models[p].flags);  // (wave-uniform)
+  const int n_b = guided || guide.fallback != 0 ? R.n_b : 0;  // a pair without a usable model and without the fallback: empty rows
+  const MpGate G{guide.window, QK.kps + (long)R.a * QK.frame_pitch, TK.kps + (long)R.b * TK.frame_pitch};
+  mrp_body<W32, true, true>(mp_frame(Q, R.a), Q.row_pitch, R.q_aligned, R.rows, mp_frame(T, R.b), T.row_pitch, R.t_aligned, n_b, max_distance, cap,
+                            R.b, out + (long)p * rows_cap * cap, out_count + (long)p * rows_cap, G, models + p, guided, guide.fallback);
 }
 // one query set against one train set, counts from the host (brisk_hip_match_radius_device); grid ceil(nq / 64)
 template <int W32>
@@ -847,6 +904,27 @@ bool brisk_launch_match_radius_pairs_gated(const BriskDescSet& Q, const BriskDes
     mp_launch_pairs(P.npairs, rows_cap, [&](dim3 grid, int p0) {
       hipLaunchKernelGGL(k_match_radius_pairs_gated<decltype(W)::value>, grid, dim3(MP_WAVES * 64), 0, s, Q, T, QK, TK, gate, P, p0, max_distance, cap,
                          rows_cap, out, out_count, pair_rows);
+    });
+  });
+}
+bool brisk_launch_match_knn_pairs_guided(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
+                                         const BriskPairModel* models, const BriskMatchGuide& guide, const BriskPairSpec& P, int words32, int k,
+                                         int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s) {
+  return m_dispatch_words(words32, [&](auto W) {
+    mp_launch_pairs(P.npairs, rows_cap, [&](dim3 grid, int p0) {
+      hipLaunchKernelGGL(k_guided_knn_pairs<decltype(W)::value>, grid, dim3(MP_WAVES * 64), 0, s, Q, T, QK, TK, models, guide, P, p0, k, rows_cap, out,
+                         out_count, pair_rows);
+    });
+  });
+}
+bool brisk_launch_match_radius_pairs_guided(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
+                                            const BriskPairModel* models, const BriskMatchGuide& guide, const BriskPairSpec& P, int words32,
+                                            float max_distance, int cap, int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows,
+                                            hipStream_t s) {
+  return m_dispatch_words(words32, [&](auto W) {
+    mp_launch_pairs(P.npairs, rows_cap, [&](dim3 grid, int p0) {
+      hipLaunchKernelGGL(k_guided_radius_pairs<decltype(W)::value>, grid, dim3(MP_WAVES * 64), 0, s, Q, T, QK, TK, models, guide, P, p0, max_distance,
+                         cap, rows_cap, out, out_count, pair_rows);
     });
   });
 }

@@ -639,6 +639,51 @@ int brisk_hip_verify_pair_matches_device(brisk_hip_ctx* ctx, const brisk_hip_des
                                          long long out_cap, brisk_hip_pair_model* d_models, int* d_out_counts, int* d_out_flags,
                                          long long* d_out_offsets, brisk_hip_dmatch* d_out_matches, void* stream);
 
+/* ---- a batch's pairs matched again inside a window around each pair's model ----------------------------------------------------
+ * What reaches the linker after the verification is the part of the first pass that survived the descriptor test (Lowe's ratio
+ * rejects true matches on repetitive texture) AND was an inlier.  Once a pair's model is known the usual second pass is the guided
+ * (by-projection) one: each query keypoint is matched again, only against the train keypoints within a few pixels of where the
+ * model puts it - the position does the work the ratio test did.  These two calls are the gated matchers with the window centred at
+ * H_p(Q) instead of Q; they read the verifier's d_models in place, and their output goes through the selection, the verification,
+ * the linker and both exits like any pair matcher's.  csrc/brisk_match_guide.h is the one definition of the rule.
+ * d_models: a DEVICE array [npairs], 8-byte aligned, indexed by PAIR p (not by frame: the keyframe form train_step = 0 has a model
+ * per pair).  Only h[0..8], hypothesis and flags of a record are read; the records may be what brisk_hip_verify_pair_matches_device
+ * wrote for these pairs, an earlier batch's, or the caller's own.
+ * GUIDED: pair p iff d_models[p].hypothesis >= 0 and (flags & (BRISK_HIP_PAIR_BAD | BRISK_HIP_PAIR_NO_MODEL)) == 0.
+ * THE CENTRE of query row q, keypoint (x, y, octave), in a guided pair: x and y converted to double, then
+ *   z = (h6 x + h7 y) + h8   u = (h0 x + h1 y) + h2   v = (h3 x + h4 y) + h5   (IEEE fp64, this order, no contraction)
+ *   cx = (float)(u / z)      cy = (float)(v / z)      (one correctly rounded fp64 division each, then round-to-nearest to fp32)
+ * In an unguided pair with fallback != 0: cx = x, cy = y (the plain gated matcher).  The row HAS A CENTRE iff cx and cy are finite:
+ * z == 0, a NaN model element, a NaN coordinate, an overflow of the conversion and an infinite model element (unless both quotients
+ * stay finite) give none, and a row of an unguided pair with fallback == 0 has none.
+ * THE MASK: M[q][t] = has_centre(q) and window.dx_min <= T.x - cx <= window.dx_max and window.dy_min <= T.y - cy <= window.dy_max
+ * (fp32, as the gate) and the gate's octave rule between Q's and T's octaves.  The identity model gives the gated matcher's mask.
+ * DEVIATION FROM THE VERIFIER, on purpose: no test of the sign of z.  The verifier's inlier rule demands that z has the sign of its
+ * sample's first point; the reported model was divided by its element of largest magnitude, so that sign is lost.  The centre is
+ * H's image of the point, whatever the sign of z. */
+typedef struct brisk_hip_match_guide {
+  brisk_hip_match_gate window; /* bounds on T - C, C the centre; max_octave_diff between Q and T as in the gate */
+  int fallback;                /* a pair without a usable model: 0 = its rows match nothing, else C = Q (the plain gated matcher) */
+} brisk_hip_match_guide;
+/* Everything not named here is exactly as in the gated call of the same kind with the mask M above: both pair forms, d_pair_rows
+ * (true counts; -1 for a bad d_pairs entry or a train count of 2^22 or more), rows_cap, memory that is never written, k-NN rows
+ * holding min(k, allowed) real entries and never topped up (k = 1, 2), radius counts = matches found, descriptor sizes, error codes
+ * (all checked before anything is launched), asynchronous on `stream`.  Additional BRISK_HIP_ERR_ARG with npairs > 0: a NULL or
+ * misaligned d_models, a NULL guide, the gated calls' keypoint-set errors.  npairs == 0 is BRISK_HIP_OK.
+ * NO CROSS CHECK in the guided form: its backward scan would need the centre of every passing query row.  The linker's claim rule
+ * settles rows that compete for a train row; a caller who wants mutual matches runs the guided pass with k = 1 and lets
+ * brisk_hip_link_tracks_device decide. */
+int brisk_hip_match_knn_pairs_guided_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                            const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                            const brisk_hip_pair_spec* pairs, const brisk_hip_pair_model* d_models,
+                                            const brisk_hip_match_guide* guide, int dim_bytes, int k, int rows_cap, brisk_hip_dmatch* d_out,
+                                            int* d_out_count, int* d_pair_rows, void* stream);
+int brisk_hip_match_radius_pairs_guided_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                               const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                               const brisk_hip_pair_spec* pairs, const brisk_hip_pair_model* d_models,
+                                               const brisk_hip_match_guide* guide, int dim_bytes, float max_distance, int cap_per_query,
+                                               int rows_cap, brisk_hip_dmatch* d_out, int* d_out_count, int* d_pair_rows, void* stream);
+
 /* ---- a batch's pair matches linked into feature tracks, on the device ----------------------------------------------------------
  * What every consumer of a frame-to-previous-frame matcher does next: "row q of frame i matched row t of frame i - 1" becomes
  * tracks - which keypoints are the same point seen again, since when, which tracks are long enough to use.  An integer problem

@@ -56,6 +56,15 @@ With --verify (k-NN only, profiles/verify_pairs.json) what checking the matches 
 plus V / T beside the spread of both windows, the HIP-event time of the verify call (three launches; a `rocprofv3 --kernel-trace
 --stats` pass around --verify --stats-pass gives the single kernels), the records per pair that go in and come out, the pairs with
 an accepted model, and whether the device's arrays equal the NumPy restatement of the rule on one batch's downloaded lists.
+With --guided (k-NN only, profiles/guided_pairs.json) what matching again under the pairs' models adds, two windows:
+  V  --verify's window V: detect + describe + match + select + verify + link + list
+  G  V followed by brisk_hip_match_knn_pairs_guided_device (k = 1, window +-6 px, octave difference 1, fallback 0) reading the verifier's
+     models in place, brisk_hip_select_pair_matches_device (distance bound only, keep 1) and brisk_hip_link_tracks_device on the
+     guided lists
+plus G / V beside the spread of both windows, the HIP-event time of the guided call (one launch; a `rocprofv3 --kernel-trace --stats`
+pass around --guided --stats-pass gives the guided kernel - under identity models, so that every pair is guided and the same rows pass -
+beside the gated k-NN kernel at the same window, shapes and build: profiles/guided_pairs_kernel_stats.csv), the records per pair that reach the linker and the links it makes in V and in G, and
+whether every guided record lies inside the window around its restated centre.
 Usage: python tools/bench_match_pairs.py [--repeats 5] [--window 0.4] [--rows-cap 2048] [--radius R [--cap N]] [--gate ...] [--out FILE]
        --stats-pass: warm-up + a few B iterations (with --gate: B, G and I) only, nothing written (the run a
        `rocprofv3 --kernel-trace --stats` pass wraps; its kernel statistics are kept as profiles/match_pairs_kernel_stats.csv)"""
@@ -468,6 +477,176 @@ def verify_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
     ctx.close()
 
 
+def guided_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
+    """--guided: windows V and G (see the module's text); writes a.out"""
+    from test_abi_match_guided import restated_centres
+    st = work.cuda_stream
+    select = B.MatchSelect(float("inf"), 0.8, 1)
+    reselect = B.MatchSelect(float("inf"), 0.0, 1)                  # the guided lists: the distance bound only, one entry per row
+    verify = B.PairVerify(a.max_error, a.hypotheses, a.min_inliers, 1, 2024)
+    radius, octaves = 6.0, 1
+    guide = B.MatchGuide.around(radius, max_octave_diff=octaves, fallback=0)
+    spec = B.PairSpec(n - 1, 1, 1, 0, 1, None)
+    L, h = ctx._L, ctx._h
+    mcap = (n - 1) * cap                                            # (one match per row at the most)
+
+    def lists_of():
+        return (torch.zeros((mcap, 4), dtype=torch.int32, device=dev), torch.zeros(n - 1, dtype=torch.int32, device=dev),
+                torch.zeros(n - 1, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int64, device=dev))
+
+    def link_of():
+        return (torch.zeros((n, cap), dtype=torch.int32, device=dev), torch.zeros((n, cap), dtype=torch.int64, device=dev),
+                torch.zeros((n, cap), dtype=torch.int32, device=dev), torch.zeros(8, dtype=torch.int64, device=dev))
+
+    sel, ver, gsel = lists_of(), lists_of(), lists_of()
+    models = torch.zeros((n - 1, 12), dtype=torch.int64, device=dev)
+    link_v, link_g = link_of(), link_of()
+    tcap, ocap = n * cap // 4, n * cap
+    lists = (torch.zeros(tcap, dtype=torch.int64, device=dev), torch.zeros(tcap, dtype=torch.int32, device=dev),
+             torch.zeros(tcap + 1, dtype=torch.int64, device=dev), torch.zeros((ocap, 2), dtype=torch.int32, device=dev),
+             torch.zeros(4, dtype=torch.int64, device=dev))
+    seeds = {id(lk): B.TrackSeed(None, None, 0, lk[3].data_ptr()) for lk in (link_v, link_g)}   # numbered on from the call before
+    guided = (torch.zeros((n - 1, cap, 1, 4), dtype=torch.int32, device=dev), torch.zeros((n - 1, cap), dtype=torch.int32, device=dev),
+              torch.zeros(n - 1, dtype=torch.int32, device=dev))
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    m, cnt, rows = outs["B"]
+
+    def link(dset, src, lk):
+        ptr, stride = ctx._node_rows((dset, 0, 1))
+        ctx.check(L.brisk_hip_link_tracks_device(h, ptr, stride, n, cap, src[3].data_ptr(), src[0].data_ptr(), C.byref(seeds[id(lk)]),
+                                                 lk[0].data_ptr(), lk[1].data_ptr(), lk[2].data_ptr(), lk[3].data_ptr(), st))
+        return ptr, stride
+
+    def run_v():
+        run_b0()
+        ctx.check(L.brisk_hip_select_pair_matches_device(h, m.data_ptr(), cnt.data_ptr(), rows.data_ptr(), n - 1, cap, k, C.byref(select), mcap,
+                                                         sel[1].data_ptr(), sel[2].data_ptr(), sel[3].data_ptr(), sel[0].data_ptr(), st))
+        dset, dim = ctx.batch_desc_set()
+        kps = ctx.batch_kp_set()
+        ctx.check(L.brisk_hip_verify_pair_matches_device(h, C.byref(dset), C.byref(dset), C.byref(kps), C.byref(kps), C.byref(spec), cap,
+                                                         sel[3].data_ptr(), sel[0].data_ptr(), mcap, C.byref(verify), mcap, models.data_ptr(),
+                                                         ver[1].data_ptr(), ver[2].data_ptr(), ver[3].data_ptr(), ver[0].data_ptr(), st))
+        ptr, stride = link(dset, ver, link_v)
+        ctx.check(L.brisk_hip_list_tracks_device(h, ptr, stride, n, cap, link_v[0].data_ptr(), link_v[1].data_ptr(), link_v[2].data_ptr(), 3,
+                                                 tcap, ocap, lists[0].data_ptr(), lists[1].data_ptr(), lists[2].data_ptr(), lists[3].data_ptr(),
+                                                 lists[4].data_ptr(), st))
+        return dset, dim, kps
+
+    def run_g(timed=False):
+        dset, dim, kps = run_v()
+        if timed:
+            ev[0].record(work)
+        ctx.check(L.brisk_hip_match_knn_pairs_guided_device(h, C.byref(dset), C.byref(dset), C.byref(kps), C.byref(kps), C.byref(spec),
+                                                            models.data_ptr(), C.byref(guide), dim, 1, cap, guided[0].data_ptr(),
+                                                            guided[1].data_ptr(), guided[2].data_ptr(), st))
+        if timed:
+            ev[1].record(work)
+        ctx.check(L.brisk_hip_select_pair_matches_device(h, guided[0].data_ptr(), guided[1].data_ptr(), guided[2].data_ptr(), n - 1, cap, 1,
+                                                         C.byref(reselect), mcap, gsel[1].data_ptr(), gsel[2].data_ptr(), gsel[3].data_ptr(),
+                                                         gsel[0].data_ptr(), st))
+        link(dset, gsel, link_g)
+
+    identity = np.zeros(n - 1, B.PAIR_MODEL)
+    identity["h"] = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0)
+    identity = torch.from_numpy(identity.view(np.int64).reshape(n - 1, 12).copy()).to(dev)
+
+    def run_yardstick():
+        """the kernel trace's pair: the guided k-NN call with EVERY pair guided (identity models: the gated call's mask, so the same
+        rows pass) and the gated k-NN call at the same window, k and shapes - the guided kernel's yardstick"""
+        dset, dim = ctx.batch_desc_set()
+        kps = ctx.batch_kp_set()
+        ctx.match_knn_pairs_guided(dset, dset, spec, 1, identity, guide, rows_cap=cap, query_kps=kps, train_kps=kps, stream=st, dim_bytes=dim,
+                                   out=guided)
+        ctx.match_knn_pairs(dset, dset, spec, 1, rows_cap=cap, stream=st, dim_bytes=dim, out=guided, gate=guide.window, query_kps=kps,
+                            train_kps=kps)
+
+    runs = {"V": run_v, "G": run_g}
+    order = "VG"
+    if a.stats_pass:                                                # (no G: every launch of the guided kernel in the trace is the yardstick's)
+        for _ in range(2 + 8):
+            run_v()
+            run_yardstick()
+            torch.cuda.synchronize()
+        return
+    for v in order + "VG":                                          # warm-up: buffers sized, scratch grown
+        runs[v]()
+        torch.cuda.synchronize()
+
+    # one batch: what reaches the linker and what it makes of it, in V and in G; every guided record inside its window
+    run_g()
+    torch.cuda.synchronize()
+    dset, dim = ctx.batch_desc_set()
+    mod = models.cpu().numpy().reshape(-1).view(B.PAIR_MODEL)
+    has_model = (mod["hypothesis"] >= 0) & ((mod["flags"] & (B.PAIR_NO_MODEL | B.PAIR_BAD)) == 0)
+    vcounts, gcounts = ver[1].cpu().numpy(), gsel[1].cpu().numpy()
+    sum_v, sum_g = link_v[3].cpu().numpy(), link_g[3].cpu().numpy()
+    goffs, grec = gsel[3].cpu().numpy(), gsel[0].cpu().numpy().view(B.DMATCH).reshape(-1)
+    kps = [ctx.batch_download(f, True, strings=dim)[0] for f in range(n)]
+    inside = True
+    for p in range(n - 1):
+        rec = grec[int(goffs[p]):int(goffs[p + 1])]
+        if not has_model[p]:
+            inside = inside and len(rec) == 0
+            continue
+        kq, kt = kps[p + 1][rec["queryIdx"]], kps[p][rec["trainIdx"]]
+        cx, cy, has = restated_centres(mod["h"][p], mod["hypothesis"][p], mod["flags"][p], 0, kq["x"], kq["y"])
+        inside = bool(inside and has.all() and (np.abs(kt["x"] - cx) <= np.float32(radius)).all() and
+                      (np.abs(kt["y"] - cy) <= np.float32(radius)).all() and (np.abs(kt["octave"] - kq["octave"]) <= octaves).all())
+
+    call_ms = []
+    for _ in range(max(a.repeats, 5)):
+        run_g(timed=True)
+        torch.cuda.synchronize()
+        call_ms.append(ev[0].elapsed_time(ev[1]))
+
+    fps = {v: [] for v in order}
+    for _ in range(a.repeats):
+        for v in order:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            calls = 0
+            while True:
+                runs[v]()
+                calls += 1
+                if time.perf_counter() - t0 >= a.window:
+                    break
+            torch.cuda.synchronize()
+            fps[v].append(calls * n / (time.perf_counter() - t0))
+    med = {v: float(np.median(fps[v])) for v in order}
+    ms = {v: 1e3 * n / med[v] for v in order}
+    spread = {v: (max(fps[v]) - min(fps[v])) / med[v] for v in order}
+    res = {
+        "workload": "bench.py's stream: %dx%d, threshold %d, %d octaves, %d frames per batch (%d distinct) in HBM; frame-to-previous-frame, "
+                    "k = %d, rows_cap %d, ratio 0.8, one match per row; verify: %d hypotheses, max_error %g, min_inliers %d, "
+                    "keep_unverified 1; guided: k = 1, window +-%g px, octave difference %d, fallback 0, then keep 1 without a ratio; "
+                    "tracks of min_len 3" % (W, H, THRESHOLD, OCTAVES, n, nd, k, cap, a.hypotheses, a.max_error, a.min_inliers, radius, octaves),
+        "kernel_revision": ctx.kernel_revision(),
+        "device": torch.cuda.get_device_name(0),
+        "windows": {"repeats": a.repeats, "seconds_each": a.window, "order": ", ".join(order) + " alternating; every window ends in a synchronise"},
+        "frames_per_s": {v: round(med[v], 1) for v in order},
+        "frames_per_s_all": {v: [round(x, 1) for x in fps[v]] for v in order},
+        "spread_rel": {v: round(spread[v], 4) for v in order},
+        "ms_per_batch": {v: round(ms[v], 4) for v in order},
+        "guided_ms_per_batch": {"G_minus_V": round(ms["G"] - ms["V"], 4)},
+        "G_over_V_frames_per_s": round(med["G"] / med["V"], 4),
+        "hip_event_ms": {"guided_call_1_launch": {"median": round(float(np.median(call_ms)), 4), "all": [round(x, 4) for x in call_ms]}},
+        "per_batch": {"pairs": n - 1, "pairs_with_a_model": int(has_model.sum()),
+                      "records_per_pair_to_the_linker": {"V": round(float(vcounts.mean()), 2), "G": round(float(gcounts.mean()), 2)},
+                      "links": {"V": int(sum_v[2]), "G": int(sum_g[2])},
+                      "proposals_lost": {"V": int(sum_v[3]), "G": int(sum_g[3])}},
+        "G_records_inside_their_windows": inside,
+        "legend": {"V": "detect_describe_batch + match_knn_pairs + select + brisk_hip_verify_pair_matches_device + link + list on one stream",
+                   "G": "V + brisk_hip_match_knn_pairs_guided_device on the verifier's models + select (keep 1) + link on the guided lists"},
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+    ext.close()
+    ctx.close()
+
+
 def tracks_download_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
     """--tracks-download: windows T, D and P (see the module's text); writes a.out"""
     st = work.cuda_stream
@@ -635,6 +814,8 @@ def main():
     ap.add_argument("--tracks-download", action="store_true",
                     help="windows T (--tracks' T), D (tracks_download in place of the list call) and P (list, synchronise, copies, batch_download_all)")
     ap.add_argument("--verify", action="store_true", help="windows T (--tracks' T) and V (T with verify_pair_matches between select and link)")
+    ap.add_argument("--guided", action="store_true",
+                    help="windows V (--verify's V) and G (V + match_knn_pairs_guided on the verifier's models + select + link)")
     ap.add_argument("--hypotheses", type=int, default=256, help="--verify: hypotheses per pair")
     ap.add_argument("--max-error", type=float, default=3.0, help="--verify: the inlier threshold in pixels")
     ap.add_argument("--min-inliers", type=int, default=8, help="--verify: inliers an accepted model needs")
@@ -665,6 +846,11 @@ def main():
             ap.error("--verify measures the k-NN pair call: without --radius / --gate / --export / --tracks / --tracks-download")
         if a.out is None:
             a.out = os.path.join(ROOT, "profiles", "verify_pairs.json")
+    if a.guided:
+        if radius is not None or gate or a.export or a.tracks or a.tracks_download or a.verify:
+            ap.error("--guided measures the k-NN pair call: without --radius / --gate / --export / --tracks / --tracks-download / --verify")
+        if a.out is None:
+            a.out = os.path.join(ROOT, "profiles", "guided_pairs.json")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", ("match_radius_pairs" if radius is not None else "match_pairs") +
                              ("_gated" if gate else "") + ".json")
@@ -721,6 +907,9 @@ def main():
         return
     if a.verify:
         verify_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b)
+        return
+    if a.guided:
+        guided_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b)
         return
 
     vp = C.c_void_p
