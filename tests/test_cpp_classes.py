@@ -9,11 +9,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "tests", "cpp", "test_binary_equal")
 
 
-def build_binary(name="test_binary_equal", hip_runtime=False, defines=(), extra_flags=()):
+def build_binary(name="test_binary_equal", hip_runtime=False, defines=(), extra_flags=(), lib="brisk_hip"):
+    """tests/cpp/<name>.cc linked with -l<lib>: brisk_hip (the tuning build, what the suite runs) or brisk_hip_release (the link
+    line INTEGRATION.md prints; that binary is tests/cpp/<name>_release, so the two builds do not overwrite each other)"""
     from ethzasl_brisk_amd import build
-    build.build()
+    assert lib in ("brisk_hip", "brisk_hip_release"), lib
+    build.build() if lib == "brisk_hip" else build.build_release()
     src = os.path.join(ROOT, "tests", "cpp", name + ".cc")
-    out = os.path.join(ROOT, "tests", "cpp", name)
+    out = os.path.join(ROOT, "tests", "cpp", name + ("" if lib == "brisk_hip" else "_release"))
     hdrs = [os.path.join(d, f) for d, _, fs in os.walk(os.path.join(ROOT, "include")) for f in fs]
     hdrs.append(os.path.join(ROOT, "tests", "cpp", "set_serialization.h"))
     hdrs.append(os.path.join(ROOT, "tests", "cpp", "synthetic_frame.h"))
@@ -22,7 +25,7 @@ def build_binary(name="test_binary_equal", hip_runtime=False, defines=(), extra_
         hip = ["-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-L/opt/rocm/lib", "-lamdhip64"] if hip_runtime else []
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-pthread", "-I" + os.path.join(ROOT, "include")] +
                               ["-D" + d for d in defines] + ["-o", out, src] + list(extra_flags) +
-                              ["-L" + os.path.join(ROOT, "ethzasl_brisk_amd"), "-lbrisk_hip"] + hip +
+                              ["-L" + os.path.join(ROOT, "ethzasl_brisk_amd"), "-l" + lib] + hip +
                               ["-Wl,-rpath," + os.path.join(ROOT, "ethzasl_brisk_amd"), "-Wl,-rpath,/opt/rocm/lib"])
     return out
 

@@ -246,9 +246,11 @@ def test_one_frame_results_beyond_the_pinned_buffer(B):
 @pytest.mark.gpu
 @pytest.mark.parametrize("n", [8, 31, 32])
 def test_1080p_batches_around_the_small_tie_kernel_threshold(B, n):
-    """batches below 32 frames run k_tie_resolve_small (precomputed act / not-self masks in the static step of the cache
-    replay; per-XCD tickets from 8 frames on), 32 and more the plain form: every slot against the oracle, twice (dirty
-    workspace)"""
+    """8, 31 and 32 frames around the threshold between k_tie_resolve_small (below 32 frames: precomputed act / not-self masks in
+    the static step of the cache replay; per-XCD tickets from 8 frames on) and the plain form - a threshold that only holds
+    under the A / B knob BRISK_TR_PAIR=0: with the default BRISK_TR_PAIR = 1 every call of up to 64 frames, these three included,
+    takes k_tie_resolve_pair, so the small form runs in no default configuration and never in the release library.  Every slot
+    against the oracle, twice (dirty workspace)"""
     distinct = [synth.frame_1080p(500 + s) for s in range(4)]
     total = _run_batch_and_compare(B, distinct, n, 80, 4, 1920, 1080)
     assert total > 3000

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Fuzzers of the engine against the oracle (GPU box; test infrastructure, not part of the test suite except where
-tests/test_gpu_round3.py runs a few hundred cases of three of them).  One entry point, one sub-command per suite:
+"""Fuzzers of the engine against the oracle (GPU box; test infrastructure).  The test suite runs slices of them:
+tests/test_gpu_round3.py a few hundred cases of callspace, options and matcher and tests/test_gpu_round6.py the threads suite, on
+the tuning library; tests/test_gpu_release.py slices of callspace, options, matcher, hostpaths and large and all of describe and
+ordered on the release library (through tests/release_run.py).  frames runs in no test.  One entry point, one sub-command per suite:
 
   python3 tools/soak.py frames    [frames per configuration]   random frames of seven size / threshold / octave configurations, batch path
   python3 tools/soak.py describe                               descriptor-only calls (all scales, borders, angles, both patterns, flags), dense detection, 4K
