@@ -44,7 +44,7 @@ ABI_SYMBOLS = [
     "brisk_hip_match_radius_pairs_device", "brisk_hip_match_radius_device",
     "brisk_hip_batch_kp_set", "brisk_hip_match_knn_pairs_gated_device", "brisk_hip_match_radius_pairs_gated_device",
     "brisk_hip_select_pair_matches_device", "brisk_hip_pair_matches_download", "brisk_hip_pair_matches_wait",
-    "brisk_hip_verify_pair_matches_device",
+    "brisk_hip_verify_pair_matches_device", "brisk_hip_refit_pair_models_device",
     "brisk_hip_match_knn_pairs_guided_device", "brisk_hip_match_radius_pairs_guided_device",
     "brisk_hip_link_tracks_device", "brisk_hip_list_tracks_device",
     "brisk_hip_track_points_device", "brisk_hip_tracks_download", "brisk_hip_tracks_wait",
@@ -136,6 +136,12 @@ class PairVerify(C.Structure):
                 ("seed", C.c_uint)]
 
 
+class PairRefit(C.Structure):
+    """brisk_hip_pair_refit: max_error - the verifier's inlier threshold, pixels in the train frame; rounds (1 ... 8) of fit and
+    recount; a model needs min_inliers (>= 4) inliers; keep_unverified: as PairVerify"""
+    _fields_ = [("max_error", C.c_float), ("rounds", C.c_int), ("min_inliers", C.c_int), ("keep_unverified", C.c_int)]
+
+
 # brisk_hip_pair_model: the winner's normalised H and the pair's counts
 PAIR_MODEL = np.dtype([("h", "<f8", (9,)), ("records", "<i4"), ("usable", "<i4"), ("inliers", "<i4"), ("hypothesis", "<i4"),
                        ("valid", "<i4"), ("flags", "<i4")])
@@ -163,6 +169,7 @@ class HostTracks(C.Structure):
 # flags of a pair in the selected lists (ROWS_CUT: the pair and every pair behind it did not fit matches_cap)
 PAIR_ROWS_CUT, PAIR_BAD, PAIR_ENTRIES_CUT = 1, 2, 4
 PAIR_NO_MODEL = 8   # verify_pair_matches: the pair has no accepted model
+PAIR_REFIT = 0x10   # refit_pair_models: at least one round replaced the input model
 
 
 def _host_array(n, dtype, pinned, keep):
@@ -349,6 +356,9 @@ def load_library():
     L.brisk_hip_verify_pair_matches_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
                                                        C.POINTER(PairSpec), C.c_int, vp, vp, C.c_longlong, C.POINTER(PairVerify),
                                                        C.c_longlong, vp, vp, vp, vp, vp, vp]
+    L.brisk_hip_refit_pair_models_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
+                                                     C.POINTER(PairSpec), C.c_int, vp, vp, C.c_longlong, vp, C.POINTER(PairRefit),
+                                                     C.c_longlong, vp, vp, vp, vp, vp, vp]
     L.brisk_hip_match_knn_pairs_guided_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
                                                           C.POINTER(PairSpec), vp, C.POINTER(MatchGuide), C.c_int, C.c_int, C.c_int,
                                                           vp, vp, vp, vp]
@@ -841,6 +851,33 @@ class Context:
                                                                 C.byref(verify), int(out_cap), res[4].data_ptr(), res[1].data_ptr(),
                                                                 res[2].data_ptr(), res[3].data_ptr(), res[0].data_ptr(),
                                                                 C.c_void_p(stream) if stream else None))
+        return res
+
+    # -- each pair's homography fitted again to all its inliers --
+    def refit_pair_models(self, query, train, pairs, rows_cap, offsets, matches, models, refit, out_cap=None, query_kps=None, train_kps=None,
+                          stream=None):
+        """brisk_hip_refit_pair_models_device behind verify_pair_matches.  offsets / matches: what the VERIFIER was given (the
+        selection's output), not what it returned; models: the models tensor it returned ([npairs, 12] int64, PAIR_MODEL records) or
+        a device pointer to npairs records; refit: a PairRefit.  Everything else, and what is returned (matches, counts, flags,
+        offsets, models), as verify_pair_matches.  Asynchronous on `stream`."""
+        import torch
+        n, in_cap = int(pairs.npairs), int(matches.shape[0])
+        if out_cap is None:
+            out_cap = in_cap
+        if query_kps is None or train_kps is None:
+            own = self.batch_kp_set()
+            query_kps = own if query_kps is None else query_kps
+            train_kps = own if train_kps is None else train_kps
+        dev = matches.device
+        ptr = models.data_ptr() if hasattr(models, "data_ptr") else models
+        res = (torch.empty((max(int(out_cap), 0), 4), dtype=torch.int32, device=dev), torch.empty(max(n, 0), dtype=torch.int32, device=dev),
+               torch.empty(max(n, 0), dtype=torch.int32, device=dev), torch.empty(max(n, 0) + 1, dtype=torch.int64, device=dev),
+               torch.empty((max(n, 0), 12), dtype=torch.int64, device=dev))
+        self.check(self._L.brisk_hip_refit_pair_models_device(self._h, C.byref(query), C.byref(train), C.byref(query_kps), C.byref(train_kps),
+                                                              C.byref(pairs), int(rows_cap), offsets.data_ptr(), matches.data_ptr(), in_cap,
+                                                              C.c_void_p(int(ptr)) if ptr else None, C.byref(refit), int(out_cap),
+                                                              res[4].data_ptr(), res[1].data_ptr(), res[2].data_ptr(), res[3].data_ptr(),
+                                                              res[0].data_ptr(), C.c_void_p(stream) if stream else None))
         return res
 
     # -- a batch's pair matches linked into feature tracks --

@@ -2183,45 +2183,53 @@ int brisk_hip_select_pair_matches_device(brisk_hip_ctx* ctx, const brisk_hip_dma
 static_assert(sizeof(brisk_hip_pair_verify) == 20 && sizeof(BriskPairVerify) == 20 && sizeof(brisk_hip_pair_model) == 96 &&
               sizeof(BriskPairModel) == 96 && BRISK_PAIR_NO_MODEL == BRISK_HIP_PAIR_NO_MODEL, "pair verify / model layout");
 
-int brisk_hip_verify_pair_matches_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
-                                         const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
-                                         const brisk_hip_pair_spec* pairs, int rows_cap, const long long* d_offsets,
-                                         const brisk_hip_dmatch* d_matches, long long in_cap, const brisk_hip_pair_verify* verify,
-                                         long long out_cap, brisk_hip_pair_model* d_models, int* d_out_counts, int* d_out_flags,
-                                         long long* d_out_offsets, brisk_hip_dmatch* d_out_matches, void* stream) {
-  if (!ctx) return BRISK_HIP_ERR_ARG;
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  if (!pairs || !verify) return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: null pairs or verify");
-  const int np = pairs->npairs;
+// what the verifier and the refit check alike, before anything is launched, in two steps (the calls' own structure lies between
+// them); name: the head of the messages
+static int pair_lists_check_sizes(brisk_hip_ctx* ctx, const std::string& name, int np, int rows_cap, long long in_cap, long long out_cap) {
   if (np < 0 || rows_cap < 1 || in_cap < 0 || out_cap < 0)
-    return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: npairs / in_cap / out_cap negative, or rows_cap below 1");
-  if (verify->hypotheses < 1 || verify->hypotheses > BRISK_VERIFY_MAX_HYPOTHESES || verify->min_inliers < BRISK_VERIFY_MIN_SAMPLE)
-    return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: hypotheses outside 1 ... 4096, or min_inliers below 4");
+    return fail(ctx, BRISK_HIP_ERR_ARG, (name + ": npairs / in_cap / out_cap negative, or rows_cap below 1").c_str());
+  return BRISK_HIP_OK;
+}
+static int pair_lists_check_arrays(brisk_hip_ctx* ctx, const std::string& name, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                   const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps, const brisk_hip_pair_spec* pairs,
+                                   const long long* d_offsets, const brisk_hip_dmatch* d_matches, long long in_cap, long long out_cap,
+                                   const brisk_hip_pair_model* d_models, const int* d_out_counts, const int* d_out_flags,
+                                   const long long* d_out_offsets, const brisk_hip_dmatch* d_out_matches) {
+  auto err = [&](const char* what) { return fail(ctx, BRISK_HIP_ERR_ARG, (name + ": " + what).c_str()); };
+  const int np = pairs->npairs;
   if (((((uintptr_t)d_matches | (uintptr_t)d_out_matches) & 15)) || (((uintptr_t)d_offsets | (uintptr_t)d_out_offsets | (uintptr_t)d_models) & 7) ||
       (((uintptr_t)d_out_counts | (uintptr_t)d_out_flags | (uintptr_t)pairs->d_pairs) & 3))
-    return fail(ctx, BRISK_HIP_ERR_ARG,
-                "verify_pair_matches: the match arrays must be 16-byte aligned, offsets and models 8-byte, counts, flags and d_pairs 4-byte");
+    return err("the match arrays must be 16-byte aligned, offsets and models 8-byte, counts, flags and d_pairs 4-byte");
   if (np > 0) {
-    if (!query || !train) return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: null descriptor set");
+    if (!query || !train) return err("null descriptor set");
     for (const brisk_hip_desc_set* s : {query, train})
       if (!s->d_counts || ((uintptr_t)s->d_counts & 3) || s->frames <= 0 || s->count_stride <= 0)
-        return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: a descriptor set without counts, or with frames / count_stride below 1");
-    if (!query_kps || !train_kps) return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: null keypoint set");
+        return err("a descriptor set without counts, or with frames / count_stride below 1");
+    if (!query_kps || !train_kps) return err("null keypoint set");
     for (const brisk_hip_kp_set* s : {query_kps, train_kps}) {
-      if (!s->d_kps) return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: a keypoint set without records");
-      if (s->frame_pitch < 0 || (((uintptr_t)s->d_kps | (unsigned long)s->frame_pitch) & 3))
-        return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: bad keypoint set geometry");
+      if (!s->d_kps) return err("a keypoint set without records");
+      if (s->frame_pitch < 0 || (((uintptr_t)s->d_kps | (unsigned long)s->frame_pitch) & 3)) return err("bad keypoint set geometry");
     }
-    if (!d_offsets || (in_cap > 0 && !d_matches)) return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: null match lists");
-    if (!d_models || !d_out_counts || !d_out_flags || !d_out_offsets || (out_cap > 0 && !d_out_matches))
-      return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: null output array");
+    if (!d_offsets || (in_cap > 0 && !d_matches)) return err("null match lists");
+    if (!d_models || !d_out_counts || !d_out_flags || !d_out_offsets || (out_cap > 0 && !d_out_matches)) return err("null output array");
     if (!pairs->d_pairs) {  // (a list on the device is checked there: the pair is flagged bad)
       const long q0 = pairs->query_first, q1 = q0 + (long)(np - 1) * pairs->query_step;
       const long t0 = pairs->train_first, t1 = t0 + (long)(np - 1) * pairs->train_step;
       if (q0 < 0 || q0 >= query->frames || q1 < 0 || q1 >= query->frames || t0 < 0 || t0 >= train->frames || t1 < 0 || t1 >= train->frames)
-        return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: a pair names a frame outside its set");
+        return err("a pair names a frame outside its set");
     }
   }
+  return BRISK_HIP_OK;
+}
+
+// the arguments are checked: the scratch (a keep byte per input record, the pairs' kept counts) grows to the call's size, then
+// launch(Q, T, QK, TK, P, keep, kept, st) queues the kernels
+extern "C++" {  // (a template)
+template <class Launch>
+static int pair_lists_run(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train, const brisk_hip_kp_set* query_kps,
+                          const brisk_hip_kp_set* train_kps, const brisk_hip_pair_spec* pairs, long long in_cap, long long* d_out_offsets,
+                          void* stream, Launch launch) {
+  const int np = pairs->npairs;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
   if (np == 0) {
@@ -2242,13 +2250,69 @@ int brisk_hip_verify_pair_matches_device(brisk_hip_ctx* ctx, const brisk_hip_des
   const BriskPairSpec P{np, pairs->query_first, pairs->query_step, pairs->train_first, pairs->train_step, pairs->d_pairs};
   const BriskKpSet QK{reinterpret_cast<const char*>(query_kps->d_kps), query_kps->frame_pitch};
   const BriskKpSet TK{reinterpret_cast<const char*>(train_kps->d_kps), train_kps->frame_pitch};
-  const BriskPairVerify V{verify->max_error, verify->hypotheses, verify->min_inliers, verify->keep_unverified, verify->seed};
-  brisk_launch_pair_verify(Q, T, QK, TK, P, rows_cap, d_offsets, reinterpret_cast<const BriskDMatch*>(d_matches), in_cap, V, base,
-                           reinterpret_cast<long long*>(base + at_kept), out_cap, reinterpret_cast<BriskPairModel*>(d_models), d_out_counts,
-                           d_out_flags, d_out_offsets, reinterpret_cast<BriskDMatch*>(d_out_matches), st);
+  launch(Q, T, QK, TK, P, base, reinterpret_cast<long long*>(base + at_kept), st);
   HIPCHK(ctx, hipGetLastError());
   if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
   return BRISK_HIP_OK;
+}
+}
+
+int brisk_hip_verify_pair_matches_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                         const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                         const brisk_hip_pair_spec* pairs, int rows_cap, const long long* d_offsets,
+                                         const brisk_hip_dmatch* d_matches, long long in_cap, const brisk_hip_pair_verify* verify,
+                                         long long out_cap, brisk_hip_pair_model* d_models, int* d_out_counts, int* d_out_flags,
+                                         long long* d_out_offsets, brisk_hip_dmatch* d_out_matches, void* stream) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (!pairs || !verify) return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: null pairs or verify");
+  if (int rc = pair_lists_check_sizes(ctx, "verify_pair_matches", pairs->npairs, rows_cap, in_cap, out_cap)) return rc;
+  if (verify->hypotheses < 1 || verify->hypotheses > BRISK_VERIFY_MAX_HYPOTHESES || verify->min_inliers < BRISK_VERIFY_MIN_SAMPLE)
+    return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: hypotheses outside 1 ... 4096, or min_inliers below 4");
+  if (int rc = pair_lists_check_arrays(ctx, "verify_pair_matches", query, train, query_kps, train_kps, pairs, d_offsets, d_matches, in_cap, out_cap,
+                                       d_models, d_out_counts, d_out_flags, d_out_offsets, d_out_matches))
+    return rc;
+  const BriskPairVerify V{verify->max_error, verify->hypotheses, verify->min_inliers, verify->keep_unverified, verify->seed};
+  return pair_lists_run(ctx, query, train, query_kps, train_kps, pairs, in_cap, d_out_offsets, stream,
+                        [&](const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK, const BriskPairSpec& P,
+                            unsigned char* keep, long long* kept, hipStream_t st) {
+                          brisk_launch_pair_verify(Q, T, QK, TK, P, rows_cap, d_offsets, reinterpret_cast<const BriskDMatch*>(d_matches), in_cap, V,
+                                                   keep, kept, out_cap, reinterpret_cast<BriskPairModel*>(d_models), d_out_counts, d_out_flags,
+                                                   d_out_offsets, reinterpret_cast<BriskDMatch*>(d_out_matches), st);
+                        });
+}
+
+// ---- the pairs' models fitted again to all their inliers (kernel: k_refit_models, brisk_pair_verify.hip; the rule: brisk_pair_refit.h) ----
+static_assert(sizeof(brisk_hip_pair_refit) == 16 && sizeof(BriskPairRefit) == 16 && BRISK_PAIR_REFIT == BRISK_HIP_PAIR_REFIT &&
+              BRISK_REFIT_PAIR_REFIT == BRISK_HIP_PAIR_REFIT, "pair refit layout / flag");
+
+int brisk_hip_refit_pair_models_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                       const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                       const brisk_hip_pair_spec* pairs, int rows_cap, const long long* d_offsets,
+                                       const brisk_hip_dmatch* d_matches, long long in_cap, const brisk_hip_pair_model* d_models,
+                                       const brisk_hip_pair_refit* refit, long long out_cap, brisk_hip_pair_model* d_out_models,
+                                       int* d_out_counts, int* d_out_flags, long long* d_out_offsets, brisk_hip_dmatch* d_out_matches,
+                                       void* stream) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (!pairs || !refit) return fail(ctx, BRISK_HIP_ERR_ARG, "refit_pair_models: null pairs or refit");
+  if (int rc = pair_lists_check_sizes(ctx, "refit_pair_models", pairs->npairs, rows_cap, in_cap, out_cap)) return rc;
+  if (refit->rounds < 1 || refit->rounds > BRISK_REFIT_MAX_ROUNDS || refit->min_inliers < BRISK_VERIFY_MIN_SAMPLE)
+    return fail(ctx, BRISK_HIP_ERR_ARG, "refit_pair_models: rounds outside 1 ... 8, or min_inliers below 4");
+  if (((uintptr_t)d_models & 7) || (pairs->npairs > 0 && !d_models))
+    return fail(ctx, BRISK_HIP_ERR_ARG, "refit_pair_models: d_models null or not 8-byte aligned");
+  if (int rc = pair_lists_check_arrays(ctx, "refit_pair_models", query, train, query_kps, train_kps, pairs, d_offsets, d_matches, in_cap, out_cap,
+                                       d_out_models, d_out_counts, d_out_flags, d_out_offsets, d_out_matches))
+    return rc;
+  const BriskPairRefit R{refit->max_error, refit->rounds, refit->min_inliers, refit->keep_unverified};
+  return pair_lists_run(ctx, query, train, query_kps, train_kps, pairs, in_cap, d_out_offsets, stream,
+                        [&](const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK, const BriskPairSpec& P,
+                            unsigned char* keep, long long* kept, hipStream_t st) {
+                          brisk_launch_pair_refit(Q, T, QK, TK, P, rows_cap, d_offsets, reinterpret_cast<const BriskDMatch*>(d_matches), in_cap,
+                                                  reinterpret_cast<const BriskPairModel*>(d_models), R, keep, kept, out_cap,
+                                                  reinterpret_cast<BriskPairModel*>(d_out_models), d_out_counts, d_out_flags, d_out_offsets,
+                                                  reinterpret_cast<BriskDMatch*>(d_out_matches), st);
+                        });
 }
 
 // ---- a batch's pair matches linked into feature tracks (kernels: brisk_track.hip) --------------------------------------------

@@ -7,6 +7,7 @@
 #include "brisk_match_guide.h"
 #include "brisk_match_select.h"
 #include "brisk_pair_verify.h"
+#include "brisk_pair_refit.h"
 #include "brisk_track_link.h"
 #include "brisk_track_points.h"
 
@@ -203,7 +204,7 @@ bool brisk_launch_match_radius_pairs_guided(const BriskDescSet& Q, const BriskDe
 
 // ---- the pair matchers' exit: selected matches, packed (brisk_match_export.hip; the rule: brisk_match_select.h) ----
 // flags of a pair (mirror BRISK_HIP_PAIR_* / BRISK_HIP_ROWS_CUT of brisk_hip.h)
-enum { BRISK_PAIR_ROWS_CUT = 1, BRISK_PAIR_BAD = 2, BRISK_PAIR_ENTRIES_CUT = 4, BRISK_PAIR_NO_MODEL = 8, BRISK_PAIR_MATCHES_CUT = 0x100 };
+enum { BRISK_PAIR_ROWS_CUT = 1, BRISK_PAIR_BAD = 2, BRISK_PAIR_ENTRIES_CUT = 4, BRISK_PAIR_NO_MODEL = 8, BRISK_PAIR_REFIT = 0x10, BRISK_PAIR_MATCHES_CUT = 0x100 };
 int brisk_match_export_blocks_per_pair(int rows_cap);
 // out / out_count / pair_rows: what a pair matcher wrote.  blk [npairs * blocks_per_pair] long long and blk_over (ints, as many):
 // scratch.  counts / flags [npairs], offsets [npairs + 1], matches [matches_cap] (16-byte aligned, like out); rows_copy: NULL or
@@ -224,6 +225,12 @@ void brisk_launch_pair_verify(const BriskDescSet& Q, const BriskDescSet& T, cons
                               int rows_cap, const long long* offsets, const BriskDMatch* matches, long long in_cap, const BriskPairVerify& V,
                               unsigned char* keep, long long* kept, long long out_cap, BriskPairModel* models, int* counts, int* flags,
                               long long* out_offsets, BriskDMatch* out, hipStream_t s);
+// the pairs' models fitted again to all their inliers (the rule: brisk_pair_refit.h): the verifier's arguments, with the models it
+// wrote (in_models [npairs]; models may be the same array) in the place of its sampler.  BRISK_PAIR_REFIT: a round replaced the model
+void brisk_launch_pair_refit(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK, const BriskPairSpec& P,
+                             int rows_cap, const long long* offsets, const BriskDMatch* matches, long long in_cap,
+                             const BriskPairModel* in_models, const BriskPairRefit& R, unsigned char* keep, long long* kept, long long out_cap,
+                             BriskPairModel* models, int* counts, int* flags, long long* out_offsets, BriskDMatch* out, hipStream_t s);
 
 // ---- a batch's pair matches linked into feature tracks (brisk_track.hip; the rule: brisk_track_link.h) ----
 enum { BRISK_TRACK_C_LINKS = 0, BRISK_TRACK_C_LOST = 1, BRISK_TRACK_C_IGNORED = 2, BRISK_TRACK_COUNTERS = 4 };  // the link call's counters

@@ -175,11 +175,16 @@ BRISK_VERIFY_HD bool brisk_verify_threshold_on(float max_error) { return max_err
 BRISK_VERIFY_HD double brisk_verify_thr2(float max_error) { return (double)max_error * (double)max_error; }
 
 // (d) for a USABLE record, with the threshold on.  (A NaN x - how the kernels mark an unusable record in LDS - gives a NaN z and false.)
-BRISK_VERIFY_HD bool brisk_verify_inlier(const BriskHomography& H, double z_ref, double thr2, double x, double y, double xt, double yt) {
-  const double z = brisk_verify_z(H, x, y);
+// the error test alone, z = brisk_verify_z(H, x, y) (brisk_pair_refit.h scores with it too)
+BRISK_VERIFY_HD bool brisk_verify_within(const BriskHomography& H, double z, double thr2, double x, double y, double xt, double yt) {
   const double ex = ((H.h0 * x + H.h1 * y) + H.h2) - z * xt;
   const double ey = ((H.h3 * x + H.h4 * y) + H.h5) - z * yt;
-  return z * z_ref > 0.0 && (ex * ex + ey * ey) <= thr2 * (z * z);
+  return (ex * ex + ey * ey) <= thr2 * (z * z);
+}
+BRISK_VERIFY_HD bool brisk_verify_inlier(const BriskHomography& H, double z_ref, double thr2, double x, double y, double xt, double yt) {
+  const double z = brisk_verify_z(H, x, y);
+  const bool within = brisk_verify_within(H, z, thr2, x, y, xt, yt);
+  return z * z_ref > 0.0 && within;
 }
 
 // (e) 0 = an invalid hypothesis (a valid one has ~h != 0: h < 2^32 - 1)

@@ -14,6 +14,10 @@
 //                     chunk - the models of all its up to 16 passes).  A pair of one chunk (m <= VF_CHUNK, the usual case: the
 //                     lists hold a few dozen records a pair) is staged ONCE and stays in LDS for every pass and for the last
 //                     sweep; only a longer pair restages its chunks per pass: 1 024 record resolutions against 256 x 1 024 scores.
+//   k_refit_models    brisk_hip_refit_pair_models_device (the rule: brisk_pair_refit.h) in k_verify_ransac's place: one workgroup
+//                     per pair, the same staging; lane = record scores the pair's model and adds the partials of the least-squares
+//                     sums, wave shuffles plus one LDS step combine them in the rule's order, one lane solves the 8 x 8 system in
+//                     LDS; then the keep bytes, the kept count and the model record.  The two kernels below pack its result too
 //   k_verify_offsets  one workgroup: exclusive prefix sums of the kept counts, counts / flags / offsets, the cut at out_cap (the
 //                     chunked scan and the cut of k_pair_select_offsets, brisk_match_export.hip)
 //   k_verify_scatter  one workgroup per pair: stable compaction of the kept records in chunks of 256 - a ballot per wave, the wave
@@ -248,6 +252,213 @@ __global__ void __launch_bounds__(VF_THREADS) k_verify_ransac(BriskDescSet Q, Br
   }
 }
 
+// ---- the refit (brisk_pair_refit.h) ----
+// N sums of the workgroup in the rule's order: the lanes' partials through the xor butterfly of their wave, the four waves' totals
+// through LDS, ((W0 + W1) + W2) + W3; every lane gets every sum.  red is free again behind the call
+template <int N, class V>
+__device__ __forceinline__ void vf_block_sums(V (&v)[N], V (*red)[BRISK_REFIT_SUMS], int lane, int wave) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = v[i] + __shfl_xor(v[i], off, 64);
+  if (lane == 0)
+#pragma unroll
+    for (int i = 0; i < N; ++i) red[wave][i] = v[i];
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = ((red[0][i] + red[1][i]) + red[2][i]) + red[3][i];
+  __syncthreads();
+}
+
+// f(record as staged, its list index) for the pair's records, lane = record: lane l sees the indices j = l (mod 256), ascending.  A
+// pair of one chunk is resident in LDS; a longer one restages chunk after chunk
+template <class F>
+__device__ __forceinline__ void vf_each(float4* __restrict__ pts, const BriskDMatch* __restrict__ matches, long long begin, int m, int nchunks,
+                                        const char* qk, const char* tk, int lim_a, int lim_b, F f) {
+  for (int c = 0; c < nchunks; ++c) {
+    if (nchunks > 1) {
+      __syncthreads();  // (the chunk before is read)
+      vf_stage(pts, matches, begin, m, c, qk, tk, lim_a, lim_b);
+      __syncthreads();
+    }
+    const int n = min(VF_CHUNK, m - c * VF_CHUNK);
+    for (int i = threadIdx.x; i < n; i += VF_THREADS) f(pts[i], c * VF_CHUNK + i);
+  }
+}
+
+// One workgroup per pair, lane = record for the score and for the sums' partials; every lane carries the same model, inlier sign
+// and count (what the reductions and the LDS broadcast of the fitted model give every lane alike), so the round loop is uniform.
+// No inlier set is stored: a pass evaluates a record's membership again from the model (some twenty flops).  Lane 0 solves the 8 x 8
+// system in LDS.  in_models may be models: every lane has read its pair's record before the first barrier, lane 0 writes behind the last
+__global__ void __launch_bounds__(VF_THREADS) k_refit_models(BriskDescSet Q, BriskDescSet T, BriskKpSet QK, BriskKpSet TK, BriskPairSpec P,
+                                                             int rows_cap, const long long* __restrict__ offsets,
+                                                             const BriskDMatch* __restrict__ matches, long long in_cap,
+                                                             const BriskPairModel* in_models, BriskPairRefit R, unsigned char* __restrict__ keep,
+                                                             long long* __restrict__ kept, BriskPairModel* models) {
+  __shared__ float4 pts[VF_CHUNK];
+  __shared__ double red[VF_WAVES][BRISK_REFIT_SUMS];
+  __shared__ int ired[VF_WAVES][BRISK_REFIT_SUMS];
+  __shared__ double sys[72];  // the augmented system
+  __shared__ double fit[10];  // the fitted model; [9] != 0: the fit failed
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+  int fa, fb;
+  if (P.pairs) {
+    fa = P.pairs[2 * (long)p];
+    fb = P.pairs[2 * (long)p + 1];
+  } else {
+    fa = P.query_first + p * P.query_step;
+    fb = P.train_first + p * P.train_step;
+  }
+  long long begin;
+  int m;
+  const bool range_ok = vf_range(offsets, p, in_cap, begin, m);
+  const bool frames_ok = fa >= 0 && fa < Q.frames && fb >= 0 && fb < T.frames;
+  if (!range_ok || !frames_ok) {  // nothing is kept, nothing of the pair is read
+    if (tid == 0) {
+      kept[p] = 0;
+      BriskPairModel M;
+      for (int i = 0; i < 9; ++i) M.h[i] = 0.0;
+      M.records = m;
+      M.usable = 0;
+      M.inliers = 0;
+      M.hypothesis = -1;
+      M.valid = 0;
+      M.flags = BRISK_PAIR_BAD | BRISK_PAIR_NO_MODEL;
+      models[p] = M;
+    }
+    return;
+  }
+  const int lim_a = brisk_track_lim(Q.counts[(long)fa * Q.count_stride], rows_cap);
+  const int lim_b = brisk_track_lim(T.counts[(long)fb * T.count_stride], rows_cap);
+  const char* qk = QK.kps + (long)fa * QK.frame_pitch;
+  const char* tk = TK.kps + (long)fb * TK.frame_pitch;
+  const int nchunks = (m + VF_CHUNK - 1) / VF_CHUNK;
+  const double thr2 = brisk_verify_thr2(R.max_error);
+
+  // the input record: one address for the whole workgroup
+  double hin[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) hin[i] = in_models[p].h[i];
+  const int in_hypothesis = in_models[p].hypothesis;
+  const bool has_model = brisk_refit_has_model(hin, in_hypothesis, in_models[p].flags, R.max_error);
+
+  if (nchunks == 1) vf_stage(pts, matches, begin, m, 0, qk, tk, lim_a, lim_b);  // stays for every pass
+  __syncthreads();
+
+  BriskHomography H{hin[0], hin[1], hin[2], hin[3], hin[4], hin[5], hin[6], hin[7], hin[8]};
+  int sign = 0, n = 0, replaced = 0;  // sign 0: nothing is an inlier
+  if (has_model) {
+    int c[2] = {0, 0};
+    vf_each(pts, matches, begin, m, nchunks, qk, tk, lim_a, lim_b, [&](const float4& r, int) {
+      const int s = brisk_refit_pass(H, thr2, (double)r.x, (double)r.y, (double)r.z, (double)r.w);
+      c[0] += s > 0 ? 1 : 0;
+      c[1] += s < 0 ? 1 : 0;
+    });
+    vf_block_sums(c, ired, lane, wave);
+    sign = brisk_refit_sign(c[0], c[1]);
+    n = brisk_refit_count(c[0], c[1]);
+    for (int round = 1; round <= R.rounds && n >= BRISK_VERIFY_MIN_SAMPLE; ++round) {
+      BriskRefitNorm N;
+      double s4[4] = {0.0, 0.0, 0.0, 0.0};
+      vf_each(pts, matches, begin, m, nchunks, qk, tk, lim_a, lim_b, [&](const float4& r, int) {
+        const double x = (double)r.x, y = (double)r.y, xt = (double)r.z, yt = (double)r.w;
+        const bool in = brisk_refit_pass(H, thr2, x, y, xt, yt) == sign;
+        s4[0] = s4[0] + (in ? x : 0.0);
+        s4[1] = s4[1] + (in ? y : 0.0);
+        s4[2] = s4[2] + (in ? xt : 0.0);
+        s4[3] = s4[3] + (in ? yt : 0.0);
+      });
+      vf_block_sums(s4, red, lane, wave);
+      brisk_refit_centroids(s4, n, N);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) s4[i] = 0.0;
+      vf_each(pts, matches, begin, m, nchunks, qk, tk, lim_a, lim_b, [&](const float4& r, int) {
+        const double x = (double)r.x, y = (double)r.y, xt = (double)r.z, yt = (double)r.w;
+        const bool in = brisk_refit_pass(H, thr2, x, y, xt, yt) == sign;
+        double t[4];
+        brisk_refit_spread_terms(N, x, y, xt, yt, t);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s4[i] = s4[i] + (in ? t[i] : 0.0);
+      });
+      vf_block_sums(s4, red, lane, wave);
+      if (!brisk_refit_scales(s4, n, N)) break;
+      double s22[BRISK_REFIT_SUMS];
+#pragma unroll
+      for (int i = 0; i < BRISK_REFIT_SUMS; ++i) s22[i] = 0.0;
+      vf_each(pts, matches, begin, m, nchunks, qk, tk, lim_a, lim_b, [&](const float4& r, int) {
+        const double x = (double)r.x, y = (double)r.y, xt = (double)r.z, yt = (double)r.w;
+        const bool in = brisk_refit_pass(H, thr2, x, y, xt, yt) == sign;
+        double t[BRISK_REFIT_SUMS];
+        brisk_refit_terms(N, x, y, xt, yt, t);
+#pragma unroll
+        for (int i = 0; i < BRISK_REFIT_SUMS; ++i) s22[i] = s22[i] + (in ? t[i] : 0.0);
+      });
+      vf_block_sums(s22, red, lane, wave);
+      if (tid == 0) {  // the solve: one lane, in LDS
+        BriskHomography F;
+        const bool ok = brisk_refit_fit(s22, n, N, sys, F);
+        fit[0] = F.h0; fit[1] = F.h1; fit[2] = F.h2; fit[3] = F.h3; fit[4] = F.h4; fit[5] = F.h5; fit[6] = F.h6; fit[7] = F.h7; fit[8] = F.h8;
+        fit[9] = ok ? 0.0 : 1.0;
+      }
+      __syncthreads();
+      const BriskHomography F{fit[0], fit[1], fit[2], fit[3], fit[4], fit[5], fit[6], fit[7], fit[8]};
+      const bool failed = fit[9] != 0.0;
+      __syncthreads();  // (fit is written again in the next round)
+      if (failed) break;
+      // the fitted model's score; d: the records whose membership differs from the present set's, per candidate sign
+      int d[4] = {0, 0, 0, 0};
+      vf_each(pts, matches, begin, m, nchunks, qk, tk, lim_a, lim_b, [&](const float4& r, int) {
+        const double x = (double)r.x, y = (double)r.y, xt = (double)r.z, yt = (double)r.w;
+        const bool in = brisk_refit_pass(H, thr2, x, y, xt, yt) == sign;
+        const int s = brisk_refit_pass(F, thr2, x, y, xt, yt);
+        d[0] += s > 0 ? 1 : 0;
+        d[1] += s < 0 ? 1 : 0;
+        d[2] += (s > 0) != in ? 1 : 0;
+        d[3] += (s < 0) != in ? 1 : 0;
+      });
+      vf_block_sums(d, ired, lane, wave);
+      const int n1 = brisk_refit_count(d[0], d[1]), sign1 = brisk_refit_sign(d[0], d[1]);
+      if (!brisk_refit_replaces(n1, n)) break;
+      H = F;
+      sign = sign1;
+      n = n1;
+      ++replaced;
+      if ((sign1 > 0 ? d[2] : d[3]) == 0) {  // a fixed point: every round left fits the same set again
+        replaced = R.rounds;
+        break;
+      }
+    }
+  }
+  const bool accepted = brisk_refit_accepted(has_model, n, R.min_inliers);
+
+  // ---- the last sweep ----
+  int e[2] = {0, 0};  // kept, usable
+  vf_each(pts, matches, begin, m, nchunks, qk, tk, lim_a, lim_b, [&](const float4& r, int j) {
+    const bool usable = r.x == r.x;
+    const bool inl = accepted && brisk_refit_pass(H, thr2, (double)r.x, (double)r.y, (double)r.z, (double)r.w) == sign;
+    const bool k = brisk_verify_keeps(accepted, usable, inl, R.keep_unverified);
+    keep[begin + j] = k ? 1 : 0;
+    e[0] += k ? 1 : 0;
+    e[1] += usable ? 1 : 0;
+  });
+  vf_block_sums(e, ired, lane, wave);
+  if (tid == 0) {
+    kept[p] = e[0];
+    BriskPairModel M;
+    const double hout[9] = {H.h0, H.h1, H.h2, H.h3, H.h4, H.h5, H.h6, H.h7, H.h8};
+#pragma unroll
+    for (int i = 0; i < 9; ++i) M.h[i] = has_model ? (replaced > 0 ? hout[i] : hin[i]) : 0.0;
+    M.records = m;
+    M.usable = e[1];
+    M.inliers = n;
+    M.hypothesis = has_model ? in_hypothesis : -1;
+    M.valid = replaced;
+    M.flags = (replaced > 0 ? BRISK_PAIR_REFIT : 0) | (accepted ? 0 : BRISK_PAIR_NO_MODEL);
+    models[p] = M;
+  }
+}
+
 // kept[p] (the pairs' kept counts) -> exclusive prefix sums in place; per pair: count, flags (the model record's too), offset.  The
 // first pair with records that does not fit out_cap and every pair behind it are cut: their counts are reported, their offsets
 // stay at the total stored.
@@ -343,6 +554,18 @@ void brisk_launch_pair_verify(const BriskDescSet& Q, const BriskDescSet& T, cons
   const int np = P.npairs;
   hipLaunchKernelGGL(k_verify_ransac, dim3(np), dim3(VF_THREADS), 0, s, Q, T, QK, TK, P, rows_cap, offsets, matches, in_cap, V, keep, kept,
                      models);
+  hipLaunchKernelGGL(k_verify_offsets, dim3(1), dim3(VF_OFF_THREADS), 0, s, kept, np, out_cap, models, counts, flags, out_offsets);
+  hipLaunchKernelGGL(k_verify_scatter, dim3(np), dim3(VF_THREADS), 0, s, offsets, matches, in_cap, keep, counts, flags, out_offsets, out_cap,
+                     out);
+}
+
+void brisk_launch_pair_refit(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK, const BriskPairSpec& P,
+                             int rows_cap, const long long* offsets, const BriskDMatch* matches, long long in_cap,
+                             const BriskPairModel* in_models, const BriskPairRefit& R, unsigned char* keep, long long* kept, long long out_cap,
+                             BriskPairModel* models, int* counts, int* flags, long long* out_offsets, BriskDMatch* out, hipStream_t s) {
+  const int np = P.npairs;
+  hipLaunchKernelGGL(k_refit_models, dim3(np), dim3(VF_THREADS), 0, s, Q, T, QK, TK, P, rows_cap, offsets, matches, in_cap, in_models, R, keep,
+                     kept, models);
   hipLaunchKernelGGL(k_verify_offsets, dim3(1), dim3(VF_OFF_THREADS), 0, s, kept, np, out_cap, models, counts, flags, out_offsets);
   hipLaunchKernelGGL(k_verify_scatter, dim3(np), dim3(VF_THREADS), 0, s, offsets, matches, in_cap, keep, counts, flags, out_offsets, out_cap,
                      out);

@@ -597,7 +597,8 @@ int brisk_hip_pair_matches_wait(brisk_hip_ctx* ctx, unsigned ticket, int* pairs_
  * KEPT, in the order of the input: the winner's inliers of an accepted pair; of any other pair the usable records if
  * keep_unverified != 0, else nothing.  A pair whose d_pairs entry lies outside its sets, or whose offsets are no range inside
  * [0, in_cap] (or span 2^31 records or more), is BAD: nothing of it is read or kept.
- * Not done here: a refit of the model to all inliers, fundamental or essential matrices, adaptive stopping. */
+ * Not done here: fundamental or essential matrices, adaptive stopping.  The refit of the model to all its inliers is a call of its
+ * own, brisk_hip_refit_pair_models_device below. */
 typedef struct brisk_hip_pair_verify {
   float max_error;     /* pixels, in the train frame */
   int hypotheses;      /* 1 ... 4096 */
@@ -638,6 +639,63 @@ int brisk_hip_verify_pair_matches_device(brisk_hip_ctx* ctx, const brisk_hip_des
                                          const brisk_hip_dmatch* d_matches, long long in_cap, const brisk_hip_pair_verify* verify,
                                          long long out_cap, brisk_hip_pair_model* d_models, int* d_out_counts, int* d_out_flags,
                                          long long* d_out_offsets, brisk_hip_dmatch* d_out_matches, void* stream);
+
+/* ---- each pair's homography fitted again to all its inliers, on the device -------------------------------------------------------
+ * The verifier reports the winner of its four-record hypotheses: a model that is exact for four noisy keypoints and nothing more.
+ * Its kept list and the guided matchers' window centres H_p(Q) inherit that noise.  This call, between the verifier and the guided
+ * matchers or the linker, fits every pair's model again to ALL its inliers by least squares and counts the inliers again, for
+ * `rounds` rounds.  It reads the lists the VERIFIER read (the selection's output), not the verifier's kept lists: a least-squares
+ * model recovers true matches the four-point winner scored just outside max_error, so a kept list can grow.  Its outputs have
+ * exactly the verifier's formats, so the linker, the guided matchers and both exits take them unchanged.  csrc/brisk_pair_refit.h is
+ * the one definition of the rule; all of its arithmetic is IEEE fp64 + - x / in a fixed order (the division is correctly rounded on
+ * host and device, as the guided matchers rely on), so models and kept lists are reproducible bit for bit.
+ * Pairs, records, USABLE records and BAD pairs are the verifier's.
+ * THE INPUT MODEL.  Pair p has one iff it is not BAD, d_models[p].hypothesis >= 0, (d_models[p].flags & (BRISK_HIP_PAIR_BAD |
+ * BRISK_HIP_PAIR_NO_MODEL)) == 0 (the guided matchers' test), the nine elements of h are finite and max_error > 0.  Only h,
+ * hypothesis and flags of an input record are read.  A pair without an input model is treated as the verifier treats a pair without
+ * an accepted model: it keeps its usable records if keep_unverified != 0, else nothing; flags BRISK_HIP_PAIR_NO_MODEL (and
+ * BRISK_HIP_PAIR_BAD); the output model is nine zeros, hypothesis -1, inliers 0, valid 0.
+ * THE SCORE of a model H is sign-free (the reported model lost its sign): a usable record PASSES iff |H (x, y, 1) - z (x', y', 1)|^2
+ * <= max_error^2 z^2 with z = (H6 x + H7 y) + H8, the verifier's expressions; the INLIERS are the passers with z > 0 if those are
+ * at least as many as the passers with z < 0, else the passers with z < 0.  H and -H score alike.
+ * THE FIT to an inlier set of n >= 4 records: both sides are normalised (centroid to the origin, mean absolute coordinate to 1),
+ * the 8 x 8 normal equations of the inhomogeneous system (h8 = 1 in normalised coordinates) are summed in one fixed order (256
+ * partials by list index modulo 256, an xor butterfly inside blocks of 64, then the four blocks) and solved by elimination without
+ * pivoting; the solution is denormalised and divided by its element of largest magnitude, as the verifier reports a model.  The fit
+ * FAILS if a side has no extent, a pivot is not > 0 (inliers on one line, at one point) or an element of the result is not finite.
+ * THE ROUNDS.  H_0 = the input model, n_0 the number of its inliers.  For r = 1 ... rounds: stop if n_(r-1) < 4 or the fit to the
+ * inliers of H_(r-1) fails; if the fitted model H' has n' >= n_(r-1) inliers it REPLACES the model, else stop and keep H_(r-1).  The
+ * number of inliers therefore never falls.  (Once a round returns its own inlier set, every later round fits the same set and
+ * replaces the model by itself.)
+ * ACCEPTED iff the pair has an input model and the final count >= min_inliers.  KEPT, in the order of the input: the final model's
+ * inliers of an accepted pair; of any other pair the usable records if keep_unverified != 0, else nothing.
+ * THE OUTPUT RECORD: h = the final model - the input record's nine doubles, byte for byte, when no round replaced it -, records and
+ * usable as the verifier writes them, inliers = the final count, hypothesis = the input's, valid = the number of rounds that
+ * replaced the model, flags = BRISK_HIP_PAIR_REFIT iff that number is > 0, plus BRISK_HIP_PAIR_NO_MODEL if not accepted (and
+ * BRISK_HIP_ROWS_CUT as below).  The guided matchers read h, hypothesis and flags only: they take these records in place. */
+typedef struct brisk_hip_pair_refit {
+  float max_error;     /* pixels, in the train frame: the verifier's inlier threshold */
+  int rounds;          /* 1 ... 8 */
+  int min_inliers;     /* >= 4 */
+  int keep_unverified; /* pairs without an accepted model: as brisk_hip_pair_verify */
+} brisk_hip_pair_refit;
+#define BRISK_HIP_PAIR_REFIT 0x10 /* at least one round replaced the input model */
+/* d_offsets / d_matches / in_cap: what the VERIFIER was given for these pairs; d_models [npairs]: the models it wrote (or any
+ * brisk_hip_pair_model records), DEVICE memory, 8-byte aligned.  d_out_models, d_out_counts, d_out_flags, d_out_offsets,
+ * d_out_matches and out_cap: exactly the verifier's d_models ... d_out_matches - the same cut at out_cap, and nothing behind the
+ * stored counts is written.  d_out_models may be the same array as d_models (a pair's record is read before it is written); no
+ * other overlap is allowed.
+ * Asynchronous on `stream`, no host synchronisation, no allocation once the context's scratch has the verifier's size for this in_cap
+ * and npairs (it is the same scratch).  Ordered behind the context's previous call and in front of its next, like every call.
+ * BRISK_HIP_ERR_ARG, before anything is launched: the verifier's errors (refit in the place of verify, min_inliers < 4 included),
+ * rounds outside 1 ... 8, a misaligned d_models, a NULL d_models with npairs > 0.  npairs == 0: BRISK_HIP_OK, d_out_offsets[0] = 0. */
+int brisk_hip_refit_pair_models_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                       const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                       const brisk_hip_pair_spec* pairs, int rows_cap, const long long* d_offsets,
+                                       const brisk_hip_dmatch* d_matches, long long in_cap, const brisk_hip_pair_model* d_models,
+                                       const brisk_hip_pair_refit* refit, long long out_cap, brisk_hip_pair_model* d_out_models,
+                                       int* d_out_counts, int* d_out_flags, long long* d_out_offsets, brisk_hip_dmatch* d_out_matches,
+                                       void* stream);
 
 /* ---- a batch's pairs matched again inside a window around each pair's model ----------------------------------------------------
  * What reaches the linker after the verification is the part of the first pass that survived the descriptor test (Lowe's ratio

@@ -56,6 +56,14 @@ With --verify (k-NN only, profiles/verify_pairs.json) what checking the matches 
 plus V / T beside the spread of both windows, the HIP-event time of the verify call (three launches; a `rocprofv3 --kernel-trace
 --stats` pass around --verify --stats-pass gives the single kernels), the records per pair that go in and come out, the pairs with
 an accepted model, and whether the device's arrays equal the NumPy restatement of the rule on one batch's downloaded lists.
+With --refit (k-NN only, profiles/refit_pairs.json) what fitting the pairs' models again to all their inliers adds, two windows:
+  V  --verify's window V: detect + describe + match + select + verify + link + list
+  R  V with brisk_hip_refit_pair_models_device (--rounds 2, the verifier's threshold, the models in place) between verify and link
+plus R / V beside the spread of both windows and the HIP-event time of the refit call (three launches).  The stream's consecutive
+frames are unrelated, so no pair there has a model (as with --guided): the call's time is also taken on a RELATED batch made here
+(as many pairs, 1 024 points a frame seen through mild homographies with 0.5 px noise, --related-records 200 records a pair, three
+quarters of them true), whose result is compared with the restated rule.  --refit --stats-pass runs the related batch only, so
+that a `rocprofv3 --kernel-trace --stats` pass around it gives k_refit_models on pairs that have models.
 With --guided (k-NN only, profiles/guided_pairs.json) what matching again under the pairs' models adds, two windows:
   V  --verify's window V: detect + describe + match + select + verify + link + list
   G  V followed by brisk_hip_match_knn_pairs_guided_device (k = 1, window +-6 px, octave difference 1, fallback 0) reading the verifier's
@@ -477,6 +485,203 @@ def verify_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
     ctx.close()
 
 
+def related_batch(dev, npairs, rows, per_pair, noise, seed=2024):
+    """a batch whose consecutive frames ARE related: `rows` points seen by npairs + 1 frames, each through a mild homography of its own
+    with Gaussian noise of `noise` px; pair p = (frame p + 1, frame p) has per_pair records, three quarters of them true.  Returns
+    (DescSet - the counts only -, KpSet, offsets, matches, the tensors that must stay alive)."""
+    rng = np.random.default_rng(seed)
+    nf = npairs + 1
+    base = np.stack([rng.uniform(20, 1900, rows), rng.uniform(20, 1060, rows)], axis=1)
+    kps = np.zeros((nf, rows), B.KEYPOINT)
+    for f in range(nf):
+        a_ = float(rng.uniform(-0.05, 0.05))
+        Hm = np.array([[np.cos(a_), -np.sin(a_), rng.uniform(-20, 20)], [np.sin(a_), np.cos(a_), rng.uniform(-20, 20)],
+                       [rng.uniform(-2e-5, 2e-5), rng.uniform(-2e-5, 2e-5), 1.0]])
+        w = Hm[2, 0] * base[:, 0] + Hm[2, 1] * base[:, 1] + Hm[2, 2]
+        kps["x"][f] = ((Hm[0, 0] * base[:, 0] + Hm[0, 1] * base[:, 1] + Hm[0, 2]) / w + rng.normal(0, noise, rows)).astype(np.float32)
+        kps["y"][f] = ((Hm[1, 0] * base[:, 0] + Hm[1, 1] * base[:, 1] + Hm[1, 2]) / w + rng.normal(0, noise, rows)).astype(np.float32)
+    rec = np.zeros((npairs, per_pair), B.DMATCH)
+    q = np.sort(rng.integers(0, rows, (npairs, per_pair)), axis=1)
+    rec["queryIdx"] = q
+    rec["trainIdx"] = np.where(rng.random((npairs, per_pair)) < 0.75, q, rng.integers(0, rows, (npairs, per_pair)))
+    rec["distance"] = rng.integers(0, 90, (npairs, per_pair))
+    d_counts = torch.full((nf,), rows, dtype=torch.int32, device=dev)
+    d_kps = torch.from_numpy(kps.view(np.int32).reshape(nf, rows, 7).copy()).to(dev)
+    d_off = torch.arange(npairs + 1, dtype=torch.int64, device=dev) * per_pair
+    d_rec = torch.from_numpy(rec.view(np.int32).reshape(-1, 4).copy()).to(dev)
+    return (B.DescSet(None, d_counts.data_ptr(), 1, 0, 0, nf), B.KpSet(d_kps.data_ptr(), rows * 28), d_off, d_rec, (d_counts, d_kps),
+            [np.stack([kps["x"][f], kps["y"][f]], axis=1) for f in range(nf)], rec.reshape(-1))
+
+
+def refit_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
+    """--refit: windows V and R (see the module's text); writes a.out"""
+    from test_abi_refit import restated_refit
+    st = work.cuda_stream
+    select = B.MatchSelect(float("inf"), 0.8, 1)
+    verify = B.PairVerify(a.max_error, a.hypotheses, a.min_inliers, 1, 2024)
+    refit = B.PairRefit(a.max_error, a.rounds, a.min_inliers, 1)
+    spec = B.PairSpec(n - 1, 1, 1, 0, 1, None)
+    L, h = ctx._L, ctx._h
+    mcap = (n - 1) * cap                                            # (one match per row at the most)
+
+    def lists_of():
+        return (torch.zeros((mcap, 4), dtype=torch.int32, device=dev), torch.zeros(n - 1, dtype=torch.int32, device=dev),
+                torch.zeros(n - 1, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int64, device=dev))
+
+    sel, ver, ref = lists_of(), lists_of(), lists_of()
+    models = torch.zeros((n - 1, 12), dtype=torch.int64, device=dev)
+    prev, age = (torch.zeros((n, cap), dtype=torch.int32, device=dev) for _ in range(2))
+    track = torch.zeros((n, cap), dtype=torch.int64, device=dev)
+    summary = torch.zeros(8, dtype=torch.int64, device=dev)
+    tcap, ocap = n * cap // 4, n * cap
+    lists = (torch.zeros(tcap, dtype=torch.int64, device=dev), torch.zeros(tcap, dtype=torch.int32, device=dev),
+             torch.zeros(tcap + 1, dtype=torch.int64, device=dev), torch.zeros((ocap, 2), dtype=torch.int32, device=dev),
+             torch.zeros(4, dtype=torch.int64, device=dev))
+    seed = B.TrackSeed(None, None, 0, summary.data_ptr())
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    m, cnt, rows = outs["B"]
+
+    def run(refitted, timed=False):
+        run_b0()
+        ctx.check(L.brisk_hip_select_pair_matches_device(h, m.data_ptr(), cnt.data_ptr(), rows.data_ptr(), n - 1, cap, k, C.byref(select), mcap,
+                                                         sel[1].data_ptr(), sel[2].data_ptr(), sel[3].data_ptr(), sel[0].data_ptr(), st))
+        dset, _ = ctx.batch_desc_set()
+        kps = ctx.batch_kp_set()
+        ctx.check(L.brisk_hip_verify_pair_matches_device(h, C.byref(dset), C.byref(dset), C.byref(kps), C.byref(kps), C.byref(spec), cap,
+                                                         sel[3].data_ptr(), sel[0].data_ptr(), mcap, C.byref(verify), mcap, models.data_ptr(),
+                                                         ver[1].data_ptr(), ver[2].data_ptr(), ver[3].data_ptr(), ver[0].data_ptr(), st))
+        src = ver
+        if refitted:                                                # the models in place
+            if timed:
+                ev[0].record(work)
+            ctx.check(L.brisk_hip_refit_pair_models_device(h, C.byref(dset), C.byref(dset), C.byref(kps), C.byref(kps), C.byref(spec), cap,
+                                                           sel[3].data_ptr(), sel[0].data_ptr(), mcap, models.data_ptr(), C.byref(refit), mcap,
+                                                           models.data_ptr(), ref[1].data_ptr(), ref[2].data_ptr(), ref[3].data_ptr(),
+                                                           ref[0].data_ptr(), st))
+            if timed:
+                ev[1].record(work)
+            src = ref
+        ptr, stride = ctx._node_rows((dset, 0, 1))
+        ctx.check(L.brisk_hip_link_tracks_device(h, ptr, stride, n, cap, src[3].data_ptr(), src[0].data_ptr(), C.byref(seed), prev.data_ptr(),
+                                                 track.data_ptr(), age.data_ptr(), summary.data_ptr(), st))
+        ctx.check(L.brisk_hip_list_tracks_device(h, ptr, stride, n, cap, prev.data_ptr(), track.data_ptr(), age.data_ptr(), 3, tcap, ocap,
+                                                 lists[0].data_ptr(), lists[1].data_ptr(), lists[2].data_ptr(), lists[3].data_ptr(),
+                                                 lists[4].data_ptr(), st))
+
+    # the related batch: the stream's consecutive frames are unrelated (no pair has a model there, as with --guided), so the kernel's
+    # own time is taken on pairs that have one
+    rp, rrows, rper = n - 1, 1024, a.related_records
+    rset, rkps, roff, rrec, keep_alive, rxy, rhost = related_batch(dev, rp, rrows, rper, 0.5)
+    rspec = B.PairSpec(rp, 1, 1, 0, 1, None)
+    rcap = rp * rper
+    rmodels = torch.zeros((rp, 12), dtype=torch.int64, device=dev)
+    rver, rref = [(torch.zeros((rcap, 4), dtype=torch.int32, device=dev), torch.zeros(rp, dtype=torch.int32, device=dev),
+                   torch.zeros(rp, dtype=torch.int32, device=dev), torch.zeros(rp + 1, dtype=torch.int64, device=dev)) for _ in range(2)]
+    rout = torch.zeros((rp, 12), dtype=torch.int64, device=dev)
+
+    def run_related(timed=False):
+        ctx.check(L.brisk_hip_verify_pair_matches_device(h, C.byref(rset), C.byref(rset), C.byref(rkps), C.byref(rkps), C.byref(rspec), rrows,
+                                                         roff.data_ptr(), rrec.data_ptr(), rcap, C.byref(verify), rcap, rmodels.data_ptr(),
+                                                         rver[1].data_ptr(), rver[2].data_ptr(), rver[3].data_ptr(), rver[0].data_ptr(), st))
+        if timed:
+            ev[0].record(work)
+        ctx.check(L.brisk_hip_refit_pair_models_device(h, C.byref(rset), C.byref(rset), C.byref(rkps), C.byref(rkps), C.byref(rspec), rrows,
+                                                       roff.data_ptr(), rrec.data_ptr(), rcap, rmodels.data_ptr(), C.byref(refit), rcap,
+                                                       rout.data_ptr(), rref[1].data_ptr(), rref[2].data_ptr(), rref[3].data_ptr(),
+                                                       rref[0].data_ptr(), st))
+        if timed:
+            ev[1].record(work)
+
+    if a.stats_pass:                                                # (the related batch only: every launch of k_refit_models in the trace has models to fit)
+        for _ in range(10):
+            run_related()
+        torch.cuda.synchronize()
+        return
+    runs = {"V": lambda: run(False), "R": lambda: run(True)}
+    order = "VR"
+    for v in order + "VR":                                          # warm-up: buffers sized, scratch grown
+        runs[v]()
+        torch.cuda.synchronize()
+    run_related()
+    torch.cuda.synchronize()
+
+    # the related batch against the restatement of the rule
+    vm = rmodels.cpu().numpy().reshape(-1).view(B.PAIR_MODEL).copy()
+    counts_r = [rrows] * (rp + 1)
+    want = restated_refit([(p + 1, p) for p in range(rp)], counts_r, counts_r, rrows, rxy, rxy, roff.cpu().numpy(), rhost, vm,
+                          (a.max_error, a.rounds, a.min_inliers, 1), rcap, rcap)
+    stored = int(want[3][-1])
+    identical = bool(rout.cpu().numpy().reshape(-1).view(B.PAIR_MODEL).tobytes() == want[0].tobytes() and
+                     rref[1].cpu().numpy().tobytes() == want[1].tobytes() and rref[2].cpu().numpy().tobytes() == want[2].tobytes() and
+                     rref[3].cpu().numpy().tobytes() == want[3].tobytes() and rref[0].cpu().numpy()[:stored].tobytes() == want[4].tobytes())
+    related_ms, call_ms = [], []
+    for _ in range(max(a.repeats, 5)):
+        run_related(timed=True)
+        torch.cuda.synchronize()
+        related_ms.append(ev[0].elapsed_time(ev[1]))
+    for _ in range(max(a.repeats, 5)):
+        run(True, timed=True)
+        torch.cuda.synchronize()
+        call_ms.append(ev[0].elapsed_time(ev[1]))
+    stream_models = models.cpu().numpy().reshape(-1).view(B.PAIR_MODEL)
+
+    fps = {v: [] for v in order}
+    for _ in range(a.repeats):
+        for v in order:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            calls = 0
+            while True:
+                runs[v]()
+                calls += 1
+                if time.perf_counter() - t0 >= a.window:
+                    break
+            torch.cuda.synchronize()
+            fps[v].append(calls * n / (time.perf_counter() - t0))
+    med = {v: float(np.median(fps[v])) for v in order}
+    ms = {v: 1e3 * n / med[v] for v in order}
+    spread = {v: (max(fps[v]) - min(fps[v])) / med[v] for v in order}
+    rm = want[0]
+    has = (rm["flags"] & B.PAIR_NO_MODEL) == 0
+    res = {
+        "workload": "bench.py's stream: %dx%d, threshold %d, %d octaves, %d frames per batch (%d distinct) in HBM; frame-to-previous-frame, "
+                    "k = %d, rows_cap %d, ratio 0.8, one match per row; verify: %d hypotheses, max_error %g, min_inliers %d, "
+                    "keep_unverified 1; refit: %d rounds, the models in place; tracks of min_len 3" %
+                    (W, H, THRESHOLD, OCTAVES, n, nd, k, cap, a.hypotheses, a.max_error, a.min_inliers, a.rounds),
+        "kernel_revision": ctx.kernel_revision(),
+        "device": torch.cuda.get_device_name(0),
+        "windows": {"repeats": a.repeats, "seconds_each": a.window, "order": ", ".join(order) + " alternating; every window ends in a synchronise"},
+        "frames_per_s": {v: round(med[v], 1) for v in order},
+        "frames_per_s_all": {v: [round(x, 1) for x in fps[v]] for v in order},
+        "spread_rel": {v: round(spread[v], 4) for v in order},
+        "ms_per_batch": {v: round(ms[v], 4) for v in order},
+        "refit_ms_per_batch": {"R_minus_V": round(ms["R"] - ms["V"], 4)},
+        "R_over_V_frames_per_s": round(med["R"] / med["V"], 4),
+        "hip_event_ms": {"refit_call_3_launches_stream": {"median": round(float(np.median(call_ms)), 4), "all": [round(x, 4) for x in call_ms]},
+                         "refit_call_3_launches_related_batch": {"median": round(float(np.median(related_ms)), 4),
+                                                                 "all": [round(x, 4) for x in related_ms]}},
+        "stream_per_batch": {"pairs": n - 1, "pairs_with_an_input_model": int(((stream_models["hypothesis"] >= 0) &
+                                                                               ((stream_models["flags"] & B.PAIR_NO_MODEL) == 0)).sum()),
+                             "note": "the stream's consecutive frames are unrelated: no pair has a model, as with --guided; the call then "
+                                     "costs its launches and one sweep over the records"},
+        "related_batch": {"pairs": rp, "rows_per_frame": rrows, "records_per_pair": rper, "true_share": 0.75, "noise_px": 0.5,
+                          "pairs_with_a_model": int(has.sum()), "pairs_refitted": int(((rm["flags"] & B.PAIR_REFIT) != 0).sum()),
+                          "inliers_per_model_mean_verifier": round(float(vm["inliers"][has].mean()), 2) if has.any() else 0.0,
+                          "inliers_per_model_mean_refit": round(float(rm["inliers"][has].mean()), 2) if has.any() else 0.0,
+                          "rounds_that_replaced_mean": round(float(rm["valid"][has].mean()), 2) if has.any() else 0.0,
+                          "equals_the_restated_rule": identical},
+        "legend": {"V": "detect_describe_batch + match_knn_pairs + select + brisk_hip_verify_pair_matches_device + link + list on one stream",
+                   "R": "V with brisk_hip_refit_pair_models_device between verify and link (the linker reads the refit's lists)"},
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+    ext.close()
+    ctx.close()
+
+
 def guided_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
     """--guided: windows V and G (see the module's text); writes a.out"""
     from test_abi_match_guided import restated_centres
@@ -816,6 +1021,10 @@ def main():
     ap.add_argument("--verify", action="store_true", help="windows T (--tracks' T) and V (T with verify_pair_matches between select and link)")
     ap.add_argument("--guided", action="store_true",
                     help="windows V (--verify's V) and G (V + match_knn_pairs_guided on the verifier's models + select + link)")
+    ap.add_argument("--refit", action="store_true",
+                    help="windows V (--verify's V) and R (V with refit_pair_models between verify and link), and the call on a related batch")
+    ap.add_argument("--rounds", type=int, default=2, help="--refit: rounds of fit and recount")
+    ap.add_argument("--related-records", type=int, default=200, help="--refit: records per pair of the related batch")
     ap.add_argument("--hypotheses", type=int, default=256, help="--verify: hypotheses per pair")
     ap.add_argument("--max-error", type=float, default=3.0, help="--verify: the inlier threshold in pixels")
     ap.add_argument("--min-inliers", type=int, default=8, help="--verify: inliers an accepted model needs")
@@ -851,6 +1060,11 @@ def main():
             ap.error("--guided measures the k-NN pair call: without --radius / --gate / --export / --tracks / --tracks-download / --verify")
         if a.out is None:
             a.out = os.path.join(ROOT, "profiles", "guided_pairs.json")
+    if a.refit:
+        if radius is not None or gate or a.export or a.tracks or a.tracks_download or a.verify or a.guided:
+            ap.error("--refit measures the k-NN pair call: without --radius / --gate / --export / --tracks / --tracks-download / --verify / --guided")
+        if a.out is None:
+            a.out = os.path.join(ROOT, "profiles", "refit_pairs.json")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", ("match_radius_pairs" if radius is not None else "match_pairs") +
                              ("_gated" if gate else "") + ".json")
@@ -910,6 +1124,9 @@ def main():
         return
     if a.guided:
         guided_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b)
+        return
+    if a.refit:
+        refit_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b)
         return
 
     vp = C.c_void_p
