@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "brisk_hip_batch_kp_set", "brisk_hip_match_knn_pairs_gated_device", "brisk_hip_match_radius_pairs_gated_device",
     "brisk_hip_select_pair_matches_device", "brisk_hip_pair_matches_download", "brisk_hip_pair_matches_wait",
     "brisk_hip_verify_pair_matches_device", "brisk_hip_refit_pair_models_device",
+    "brisk_hip_verify_pair_matches_epipolar_device",
     "brisk_hip_match_knn_pairs_guided_device", "brisk_hip_match_radius_pairs_guided_device",
     "brisk_hip_link_tracks_device", "brisk_hip_list_tracks_device",
     "brisk_hip_track_points_device", "brisk_hip_tracks_download", "brisk_hip_tracks_wait",
@@ -145,6 +146,11 @@ class PairRefit(C.Structure):
 # brisk_hip_pair_model: the winner's normalised H and the pair's counts
 PAIR_MODEL = np.dtype([("h", "<f8", (9,)), ("records", "<i4"), ("usable", "<i4"), ("inliers", "<i4"), ("hypothesis", "<i4"),
                        ("valid", "<i4"), ("flags", "<i4")])
+
+# brisk_hip_pair_epipolar_model: the winner's normalised F (row-major, x'^T F x = 0) and the pair's counts.  PAIR_MODEL's layout under
+# another name on purpose: refit_pair_models and the guided matchers read a PAIR_MODEL as a homography
+PAIR_EPIPOLAR_MODEL = np.dtype([("f", "<f8", (9,)), ("records", "<i4"), ("usable", "<i4"), ("inliers", "<i4"), ("hypothesis", "<i4"),
+                                ("valid", "<i4"), ("flags", "<i4")])
 
 
 class TrackSeed(C.Structure):
@@ -356,6 +362,7 @@ def load_library():
     L.brisk_hip_verify_pair_matches_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
                                                        C.POINTER(PairSpec), C.c_int, vp, vp, C.c_longlong, C.POINTER(PairVerify),
                                                        C.c_longlong, vp, vp, vp, vp, vp, vp]
+    L.brisk_hip_verify_pair_matches_epipolar_device.argtypes = L.brisk_hip_verify_pair_matches_device.argtypes
     L.brisk_hip_refit_pair_models_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
                                                      C.POINTER(PairSpec), C.c_int, vp, vp, C.c_longlong, vp, C.POINTER(PairRefit),
                                                      C.c_longlong, vp, vp, vp, vp, vp, vp]
@@ -851,6 +858,34 @@ class Context:
                                                                 C.byref(verify), int(out_cap), res[4].data_ptr(), res[1].data_ptr(),
                                                                 res[2].data_ptr(), res[3].data_ptr(), res[0].data_ptr(),
                                                                 C.c_void_p(stream) if stream else None))
+        return res
+
+    # -- a batch's pair matches checked against an epipolar geometry --
+    def verify_pair_matches_epipolar(self, query, train, pairs, rows_cap, offsets, matches, verify, out_cap=None, query_kps=None,
+                                     train_kps=None, stream=None):
+        """brisk_hip_verify_pair_matches_epipolar_device: verify_pair_matches with an eight-point fundamental matrix in the
+        homography's place, for scenes with depth (left against right, a moving camera).  The arguments are verify_pair_matches';
+        verify: a PairVerify whose max_error is the Sampson distance in pixels and whose min_inliers is >= 8.  Returns the same
+        five device tensors; models [npairs, 12] int64 holds PAIR_EPIPOLAR_MODEL records - not homographies: they are not for
+        refit_pair_models or the guided matchers.  Asynchronous on `stream`."""
+        import torch
+        n, in_cap = int(pairs.npairs), int(matches.shape[0])
+        if out_cap is None:
+            out_cap = in_cap
+        if query_kps is None or train_kps is None:
+            own = self.batch_kp_set()
+            query_kps = own if query_kps is None else query_kps
+            train_kps = own if train_kps is None else train_kps
+        dev = matches.device
+        res = (torch.empty((max(int(out_cap), 0), 4), dtype=torch.int32, device=dev), torch.empty(max(n, 0), dtype=torch.int32, device=dev),
+               torch.empty(max(n, 0), dtype=torch.int32, device=dev), torch.empty(max(n, 0) + 1, dtype=torch.int64, device=dev),
+               torch.empty((max(n, 0), 12), dtype=torch.int64, device=dev))
+        self.check(self._L.brisk_hip_verify_pair_matches_epipolar_device(self._h, C.byref(query), C.byref(train), C.byref(query_kps),
+                                                                         C.byref(train_kps), C.byref(pairs), int(rows_cap), offsets.data_ptr(),
+                                                                         matches.data_ptr(), in_cap, C.byref(verify), int(out_cap),
+                                                                         res[4].data_ptr(), res[1].data_ptr(), res[2].data_ptr(),
+                                                                         res[3].data_ptr(), res[0].data_ptr(),
+                                                                         C.c_void_p(stream) if stream else None))
         return res
 
     # -- each pair's homography fitted again to all its inliers --

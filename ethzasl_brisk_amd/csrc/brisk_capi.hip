@@ -2282,6 +2282,37 @@ int brisk_hip_verify_pair_matches_device(brisk_hip_ctx* ctx, const brisk_hip_des
                         });
 }
 
+// ---- a batch's pair matches checked against an epipolar geometry (kernel: k_epipolar_ransac, brisk_pair_verify.hip; the rule:
+// brisk_pair_epipolar.h).  The verifier's checks, scratch and packing; the model record is a type of its own with the same layout
+static_assert(sizeof(brisk_hip_pair_epipolar_model) == 96 && sizeof(BriskPairEpipolarModel) == 96 && alignof(brisk_hip_pair_epipolar_model) == 8,
+              "pair epipolar model layout");
+
+int brisk_hip_verify_pair_matches_epipolar_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                                  const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                                  const brisk_hip_pair_spec* pairs, int rows_cap, const long long* d_offsets,
+                                                  const brisk_hip_dmatch* d_matches, long long in_cap, const brisk_hip_pair_verify* verify,
+                                                  long long out_cap, brisk_hip_pair_epipolar_model* d_models, int* d_out_counts,
+                                                  int* d_out_flags, long long* d_out_offsets, brisk_hip_dmatch* d_out_matches, void* stream) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (!pairs || !verify) return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches_epipolar: null pairs or verify");
+  if (int rc = pair_lists_check_sizes(ctx, "verify_pair_matches_epipolar", pairs->npairs, rows_cap, in_cap, out_cap)) return rc;
+  if (verify->hypotheses < 1 || verify->hypotheses > BRISK_VERIFY_MAX_HYPOTHESES || verify->min_inliers < BRISK_EPIPOLAR_MIN_SAMPLE)
+    return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches_epipolar: hypotheses outside 1 ... 4096, or min_inliers below 8");
+  if (int rc = pair_lists_check_arrays(ctx, "verify_pair_matches_epipolar", query, train, query_kps, train_kps, pairs, d_offsets, d_matches, in_cap,
+                                       out_cap, reinterpret_cast<const brisk_hip_pair_model*>(d_models), d_out_counts, d_out_flags, d_out_offsets,
+                                       d_out_matches))
+    return rc;
+  const BriskPairVerify V{verify->max_error, verify->hypotheses, verify->min_inliers, verify->keep_unverified, verify->seed};
+  return pair_lists_run(ctx, query, train, query_kps, train_kps, pairs, in_cap, d_out_offsets, stream,
+                        [&](const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK, const BriskPairSpec& P,
+                            unsigned char* keep, long long* kept, hipStream_t st) {
+                          brisk_launch_pair_epipolar(Q, T, QK, TK, P, rows_cap, d_offsets, reinterpret_cast<const BriskDMatch*>(d_matches), in_cap,
+                                                     V, keep, kept, out_cap, reinterpret_cast<BriskPairEpipolarModel*>(d_models), d_out_counts,
+                                                     d_out_flags, d_out_offsets, reinterpret_cast<BriskDMatch*>(d_out_matches), st);
+                        });
+}
+
 // ---- the pairs' models fitted again to all their inliers (kernel: k_refit_models, brisk_pair_verify.hip; the rule: brisk_pair_refit.h) ----
 static_assert(sizeof(brisk_hip_pair_refit) == 16 && sizeof(BriskPairRefit) == 16 && BRISK_PAIR_REFIT == BRISK_HIP_PAIR_REFIT &&
               BRISK_REFIT_PAIR_REFIT == BRISK_HIP_PAIR_REFIT, "pair refit layout / flag");

@@ -8,6 +8,7 @@
 #include "brisk_match_select.h"
 #include "brisk_pair_verify.h"
 #include "brisk_pair_refit.h"
+#include "brisk_pair_epipolar.h"
 #include "brisk_track_link.h"
 #include "brisk_track_points.h"
 
@@ -225,6 +226,12 @@ void brisk_launch_pair_verify(const BriskDescSet& Q, const BriskDescSet& T, cons
                               int rows_cap, const long long* offsets, const BriskDMatch* matches, long long in_cap, const BriskPairVerify& V,
                               unsigned char* keep, long long* kept, long long out_cap, BriskPairModel* models, int* counts, int* flags,
                               long long* out_offsets, BriskDMatch* out, hipStream_t s);
+// the verifier with the eight-point epipolar model in the homography's place (the rule: brisk_pair_epipolar.h): its arguments, its
+// scratch and its two packing kernels; models [npairs] are BriskPairEpipolarModel records
+void brisk_launch_pair_epipolar(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK, const BriskPairSpec& P,
+                                int rows_cap, const long long* offsets, const BriskDMatch* matches, long long in_cap, const BriskPairVerify& V,
+                                unsigned char* keep, long long* kept, long long out_cap, BriskPairEpipolarModel* models, int* counts, int* flags,
+                                long long* out_offsets, BriskDMatch* out, hipStream_t s);
 // the pairs' models fitted again to all their inliers (the rule: brisk_pair_refit.h): the verifier's arguments, with the models it
 // wrote (in_models [npairs]; models may be the same array) in the place of its sampler.  BRISK_PAIR_REFIT: a round replaced the model
 void brisk_launch_pair_refit(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK, const BriskPairSpec& P,

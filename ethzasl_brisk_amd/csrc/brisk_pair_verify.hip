@@ -547,6 +547,190 @@ __global__ void __launch_bounds__(VF_THREADS) k_verify_scatter(const long long* 
   }
 }
 
+// ---- the epipolar verifier (brisk_pair_epipolar.h) ----
+// the model of hypothesis h of a pair with m >= 8 records; false = invalid
+__device__ __forceinline__ bool vf_epipolar_hypothesis(const BriskDMatch* __restrict__ matches, long long begin, int m, uint32_t pair_seed, int h,
+                                                       const char* qk, const char* tk, int lim_a, int lim_b, BriskFundamental& F) {
+  int idx[8];
+  brisk_epipolar_sample(pair_seed, h, m, idx);
+  BriskVerifyPoints pt[8];
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+    // (every index is below m by construction; a draw that is not - it cannot happen - would make the hypothesis invalid, not a read)
+    ok = ok && (unsigned)idx[k] < (unsigned)m && vf_resolve(matches, begin + idx[k], qk, tk, lim_a, lim_b, r);
+    pt[k] = vf_points(r);
+  }
+  if (!ok) return false;
+  int free_col;
+  return brisk_epipolar_model(pt, F, free_col);
+}
+
+// k_verify_ransac with the eight-point model in the homography's place: one workgroup per pair, a lane = a hypothesis, the pass
+// over 256 hypotheses outside, the chunk inside, the same staging, key reduction and keep sweep; k_verify_offsets and
+// k_verify_scatter pack the result (BriskPairEpipolarModel has BriskPairModel's layout).  What is new is the solve: the lane keeps
+// its 8 x 9 system in registers - brisk_epipolar_step indexes it with constants only, the row and column swaps of the complete
+// pivoting are compare-selects - so nothing goes to scratch.  The registers of one wave per SIMD are there for it: a workgroup is
+// four waves, one per SIMD, and the 16 KB chunk leaves room for nine more workgroups on the CU that the registers do not.
+__global__ void __launch_bounds__(VF_THREADS) k_epipolar_ransac(BriskDescSet Q, BriskDescSet T, BriskKpSet QK, BriskKpSet TK, BriskPairSpec P,
+                                                                int rows_cap, const long long* __restrict__ offsets,
+                                                                const BriskDMatch* __restrict__ matches, long long in_cap, BriskPairVerify V,
+                                                                unsigned char* __restrict__ keep, long long* __restrict__ kept,
+                                                                BriskPairEpipolarModel* __restrict__ models) {
+  __shared__ float4 pts[VF_CHUNK];
+  __shared__ unsigned long long wkey[VF_WAVES];
+  __shared__ double win[9];  // the winner's F
+  __shared__ int wsum[2][VF_WAVES];
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+  // the pair, as the pair matchers resolve it
+  int fa, fb;
+  if (P.pairs) {
+    fa = P.pairs[2 * (long)p];
+    fb = P.pairs[2 * (long)p + 1];
+  } else {
+    fa = P.query_first + p * P.query_step;
+    fb = P.train_first + p * P.train_step;
+  }
+  long long begin;
+  int m;
+  const bool range_ok = vf_range(offsets, p, in_cap, begin, m);
+  const bool frames_ok = fa >= 0 && fa < Q.frames && fb >= 0 && fb < T.frames;
+  if (!range_ok || !frames_ok) {  // nothing is kept, nothing of the pair is read
+    if (tid == 0) {
+      kept[p] = 0;
+      BriskPairEpipolarModel M;
+      for (int i = 0; i < 9; ++i) M.f[i] = 0.0;
+      M.records = m;
+      M.usable = 0;
+      M.inliers = 0;
+      M.hypothesis = -1;
+      M.valid = 0;
+      M.flags = BRISK_PAIR_BAD | BRISK_PAIR_NO_MODEL;
+      models[p] = M;
+    }
+    return;
+  }
+  const int lim_a = brisk_track_lim(Q.counts[(long)fa * Q.count_stride], rows_cap);
+  const int lim_b = brisk_track_lim(T.counts[(long)fb * T.count_stride], rows_cap);
+  const char* qk = QK.kps + (long)fa * QK.frame_pitch;
+  const char* tk = TK.kps + (long)fb * TK.frame_pitch;
+  const int nchunks = (m + VF_CHUNK - 1) / VF_CHUNK;
+  const uint32_t pair_seed = brisk_verify_pair_seed(V.seed, p);
+  const bool thr_on = brisk_verify_threshold_on(V.max_error);
+  const double thr2 = brisk_verify_thr2(V.max_error);
+
+  if (nchunks == 1) vf_stage(pts, matches, begin, m, 0, qk, tk, lim_a, lim_b);  // stays for every pass and the last sweep
+  __syncthreads();
+
+  // ---- the hypotheses: passes of 256 outside, chunks inside; the pass behind the last one is the winner's, on every lane ----
+  unsigned long long best = 0ull;
+  int nvalid = 0, hwin = -1;
+  bool accepted = false;
+  BriskFundamental W{0., 0., 0., 0., 0., 0., 0., 0., 0.};
+  const int npass = m >= BRISK_EPIPOLAR_MIN_SAMPLE ? (V.hypotheses + VF_THREADS - 1) / VF_THREADS : 0;
+  for (int pass = 0; pass <= npass; ++pass) {
+    const bool last = pass == npass;
+    if (last) {
+      // the winner: wave shuffles, one LDS step; the number of valid hypotheses rides along
+      for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(best, off, 64);
+        best = o > best ? o : best;
+        nvalid += __shfl_xor(nvalid, off, 64);
+      }
+      if (lane == 0) { wkey[wave] = best; wsum[0][wave] = nvalid; }
+      __syncthreads();
+      best = 0ull;
+      nvalid = 0;
+#pragma unroll
+      for (int w = 0; w < VF_WAVES; ++w) {
+        const unsigned long long o = wkey[w];
+        best = o > best ? o : best;
+        nvalid += wsum[0][w];
+      }
+      accepted = brisk_verify_accepted(best, V.min_inliers);
+      hwin = brisk_verify_key_hypothesis(best);
+      if (hwin < 0) break;
+    }
+    // (the winner's model is the same arithmetic again, by lane 0 alone: one instance of the solve in the kernel's code)
+    const int h = last ? hwin : pass * VF_THREADS + tid;
+    BriskFundamental F{0., 0., 0., 0., 0., 0., 0., 0., 0.};
+    bool valid = false;
+    if (last ? tid == 0 : h < V.hypotheses) valid = vf_epipolar_hypothesis(matches, begin, m, pair_seed, h, qk, tk, lim_a, lim_b, F);
+    if (!valid) F = BriskFundamental{0., 0., 0., 0., 0., 0., 0., 0., 0.};
+    if (last) {
+      if (tid == 0) {
+        win[0] = F.f0; win[1] = F.f1; win[2] = F.f2; win[3] = F.f3; win[4] = F.f4; win[5] = F.f5; win[6] = F.f6; win[7] = F.f7; win[8] = F.f8;
+      }
+      break;
+    }
+    const bool score = valid && thr_on;
+    int count = 0;
+    for (int c = 0; c < nchunks; ++c) {
+      if (nchunks > 1) {
+        __syncthreads();  // (the chunk before is read)
+        vf_stage(pts, matches, begin, m, c, qk, tk, lim_a, lim_b);
+        __syncthreads();
+      }
+      const int n = min(VF_CHUNK, m - c * VF_CHUNK);
+      if (score)
+        for (int i = 0; i < n; ++i) {
+          const float4 r = pts[i];  // one address for the whole wave: a broadcast
+          count += brisk_epipolar_inlier(F, thr2, (double)r.x, (double)r.y, (double)r.z, (double)r.w) ? 1 : 0;
+        }
+    }
+    const unsigned long long key = brisk_verify_key(valid, count, h);
+    best = key > best ? key : best;
+    nvalid += valid ? 1 : 0;
+  }
+  __syncthreads();  // (win is written; wsum is written again below)
+  if (hwin >= 0) W = BriskFundamental{win[0], win[1], win[2], win[3], win[4], win[5], win[6], win[7], win[8]};
+
+  // ---- the last sweep: lane = record ----
+  int nkept = 0, nusable = 0;
+  for (int c = 0; c < nchunks; ++c) {
+    if (nchunks > 1) {
+      __syncthreads();
+      vf_stage(pts, matches, begin, m, c, qk, tk, lim_a, lim_b);
+      __syncthreads();
+    }
+    const int n = min(VF_CHUNK, m - c * VF_CHUNK);
+    for (int i = tid; i < n; i += VF_THREADS) {
+      const float4 r = pts[i];
+      const bool usable = r.x == r.x;
+      const bool inl = accepted && usable && brisk_epipolar_inlier(W, thr2, (double)r.x, (double)r.y, (double)r.z, (double)r.w);
+      const bool k = brisk_verify_keeps(accepted, usable, inl, V.keep_unverified);
+      keep[begin + (long long)c * VF_CHUNK + i] = k ? 1 : 0;
+      nkept += k ? 1 : 0;
+      nusable += usable ? 1 : 0;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    nkept += __shfl_xor(nkept, off, 64);
+    nusable += __shfl_xor(nusable, off, 64);
+  }
+  if (lane == 0) { wsum[0][wave] = nkept; wsum[1][wave] = nusable; }
+  __syncthreads();
+  if (tid == 0) {
+    nkept = nusable = 0;
+#pragma unroll
+    for (int w = 0; w < VF_WAVES; ++w) { nkept += wsum[0][w]; nusable += wsum[1][w]; }
+    kept[p] = nkept;
+    BriskPairEpipolarModel M;
+    const double f[9] = {W.f0, W.f1, W.f2, W.f3, W.f4, W.f5, W.f6, W.f7, W.f8};  // (zeros without a valid hypothesis)
+#pragma unroll
+    for (int i = 0; i < 9; ++i) M.f[i] = f[i];
+    M.records = m;
+    M.usable = nusable;
+    M.inliers = brisk_verify_key_count(best);
+    M.hypothesis = hwin;
+    M.valid = nvalid;
+    M.flags = accepted ? 0 : BRISK_PAIR_NO_MODEL;
+    models[p] = M;
+  }
+}
+
 void brisk_launch_pair_verify(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK, const BriskPairSpec& P,
                               int rows_cap, const long long* offsets, const BriskDMatch* matches, long long in_cap, const BriskPairVerify& V,
                               unsigned char* keep, long long* kept, long long out_cap, BriskPairModel* models, int* counts, int* flags,
@@ -567,6 +751,21 @@ void brisk_launch_pair_refit(const BriskDescSet& Q, const BriskDescSet& T, const
   hipLaunchKernelGGL(k_refit_models, dim3(np), dim3(VF_THREADS), 0, s, Q, T, QK, TK, P, rows_cap, offsets, matches, in_cap, in_models, R, keep,
                      kept, models);
   hipLaunchKernelGGL(k_verify_offsets, dim3(1), dim3(VF_OFF_THREADS), 0, s, kept, np, out_cap, models, counts, flags, out_offsets);
+  hipLaunchKernelGGL(k_verify_scatter, dim3(np), dim3(VF_THREADS), 0, s, offsets, matches, in_cap, keep, counts, flags, out_offsets, out_cap,
+                     out);
+}
+
+void brisk_launch_pair_epipolar(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK, const BriskPairSpec& P,
+                                int rows_cap, const long long* offsets, const BriskDMatch* matches, long long in_cap, const BriskPairVerify& V,
+                                unsigned char* keep, long long* kept, long long out_cap, BriskPairEpipolarModel* models, int* counts, int* flags,
+                                long long* out_offsets, BriskDMatch* out, hipStream_t s) {
+  static_assert(sizeof(BriskPairEpipolarModel) == sizeof(BriskPairModel) && offsetof(BriskPairEpipolarModel, flags) == offsetof(BriskPairModel, flags),
+                "k_verify_offsets reads and writes the flags of either record");
+  const int np = P.npairs;
+  hipLaunchKernelGGL(k_epipolar_ransac, dim3(np), dim3(VF_THREADS), 0, s, Q, T, QK, TK, P, rows_cap, offsets, matches, in_cap, V, keep, kept,
+                     models);
+  hipLaunchKernelGGL(k_verify_offsets, dim3(1), dim3(VF_OFF_THREADS), 0, s, kept, np, out_cap, reinterpret_cast<BriskPairModel*>(models), counts,
+                     flags, out_offsets);
   hipLaunchKernelGGL(k_verify_scatter, dim3(np), dim3(VF_THREADS), 0, s, offsets, matches, in_cap, keep, counts, flags, out_offsets, out_cap,
                      out);
 }

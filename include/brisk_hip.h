@@ -597,8 +597,8 @@ int brisk_hip_pair_matches_wait(brisk_hip_ctx* ctx, unsigned ticket, int* pairs_
  * KEPT, in the order of the input: the winner's inliers of an accepted pair; of any other pair the usable records if
  * keep_unverified != 0, else nothing.  A pair whose d_pairs entry lies outside its sets, or whose offsets are no range inside
  * [0, in_cap] (or span 2^31 records or more), is BAD: nothing of it is read or kept.
- * Not done here: fundamental or essential matrices, adaptive stopping.  The refit of the model to all its inliers is a call of its
- * own, brisk_hip_refit_pair_models_device below. */
+ * Not done here: essential matrices, adaptive stopping.  The refit of the model to all its inliers is a call of its own,
+ * brisk_hip_refit_pair_models_device below; scenes that are no plane have brisk_hip_verify_pair_matches_epipolar_device further below. */
 typedef struct brisk_hip_pair_verify {
   float max_error;     /* pixels, in the train frame */
   int hypotheses;      /* 1 ... 4096 */
@@ -696,6 +696,69 @@ int brisk_hip_refit_pair_models_device(brisk_hip_ctx* ctx, const brisk_hip_desc_
                                        const brisk_hip_pair_refit* refit, long long out_cap, brisk_hip_pair_model* d_out_models,
                                        int* d_out_counts, int* d_out_flags, long long* d_out_offsets, brisk_hip_dmatch* d_out_matches,
                                        void* stream);
+
+/* ---- a batch's pair matches checked against an epipolar geometry, on the device ---------------------------------------------------
+ * A homography is the right model for a plane or a pure rotation.  Left against right, and frame against previous frame of a moving
+ * camera, see a scene with depth: no homography holds there, and the verifier above keeps the dominant plane and drops true matches
+ * everywhere else.  What holds is the epipolar constraint x'^T F x = 0.  This call is the verifier with that model in the
+ * homography's place - the same place in the chain (select -> verify -> link), the same inputs, packed lists of the same format out.
+ * csrc/brisk_pair_epipolar.h is the one definition of the rule; all of its arithmetic is IEEE fp64 + - x / in a fixed order (the
+ * division is correctly rounded on host and device), so models and kept lists are reproducible bit for bit.
+ * Pairs, records, USABLE records and BAD pairs are the verifier's.
+ * THE RULE.  Hypothesis h (0 <= h < hypotheses) samples EIGHT distinct records from a hash of (seed, p, h).  Both sides of the
+ * sample are normalised (centroid to the origin, mean absolute coordinate to 1), and F, query -> train, row-major, is the null vector
+ * of the linear 8 x 9 system of the eight records, found by elimination with complete pivoting: no element is fixed to 1 beforehand,
+ * so rectified stereo, where the last element of F is 0, is no special case.  F is denormalised and divided by its element of largest
+ * magnitude; that F is what is scored and what is reported.  The hypothesis is INVALID if m < 8, if a sampled record is unusable, if
+ * a side of the sample has no extent, if a pivot is not > 0 and finite (the eight points of a side on one axis-parallel line) or an
+ * element of F is not finite.  A usable record (x, y) -> (x', y') is an INLIER iff its Sampson distance is at most max_error pixels,
+ * tested without a division: with l = F (x, y, 1), l' = F^T (x', y', 1), r = (x', y', 1) . l and g = l0^2 + l1^2 + l'0^2 + l'1^2:
+ * g > 0 and r^2 <= max_error^2 g.  There is no sign test.  max_error <= 0 or NaN: nothing is an inlier.  WINNER, ACCEPTED (with
+ * min_inliers >= 8) and KEPT are the verifier's.
+ * WHAT THE MODEL IS.  A filter: it decides which records agree with ONE epipolar geometry.  RANK 2 IS NOT ENFORCED, so the reported
+ * F is the linear eight-point solution and in general has no epipoles; it is not meant for rectification or for recovering a pose.
+ * Eight coplanar points (and a scene that is a plane) give a degenerate system; its null vector still vanishes on the plane's
+ * records, so the plane is kept - with more random records beside it than a proper F lets through.
+ * Not done here: essential matrices (no intrinsics enter), the refit of F to all its inliers, guided matching along epipolar lines,
+ * seven- or five-point samples, adaptive stopping. */
+typedef struct brisk_hip_pair_epipolar_model { /* 96 bytes, 8-byte aligned.  A type of its own ON PURPOSE: brisk_hip_refit_pair_models_device
+                                                  and the guided matchers read a brisk_hip_pair_model as a homography and must not be
+                                                  handed an F */
+  double f[9];                                 /* the winner's F, row-major, x'^T F x = 0, every element divided by the one of largest
+                                                  magnitude (the first on a tie); nine zeros without a valid hypothesis */
+  int records, usable, inliers;                /* m, the usable ones, the winner's inliers */
+  int hypothesis;                              /* the winner, -1: none valid */
+  int valid;                                   /* valid hypotheses */
+  int flags;                                   /* as d_out_flags[p] */
+} brisk_hip_pair_epipolar_model;
+/* The arguments are brisk_hip_verify_pair_matches_device's, one for one, except that d_models holds brisk_hip_pair_epipolar_model
+ * records.  `verify` is the verifier's structure, unchanged: max_error is the Sampson distance in pixels, hypotheses 1 ... 4096
+ * eight-record samples, min_inliers >= 8.
+ * d_offsets [npairs + 1] / d_matches: the lists a selection with matches_cap = in_cap wrote for these npairs = pairs->npairs pairs
+ * and this rows_cap; in_cap bounds the INPUT (d_matches holds in_cap records, no offset lies beyond it), out_cap the output.
+ * Outputs, all in caller-provided DEVICE memory:
+ *   d_models      [npairs]      the pairs' models
+ *   d_out_counts  [npairs]      records kept for pair p
+ *   d_out_flags   [npairs]      BRISK_HIP_PAIR_BAD, BRISK_HIP_PAIR_NO_MODEL; BRISK_HIP_ROWS_CUT = this pair and every pair behind it
+ *                               did not fit out_cap: their counts are still reported, nothing of them is stored, their offsets stay
+ *                               at the total (the cut of brisk_hip_select_pair_matches_device)
+ *   d_out_offsets [npairs + 1]  exclusive prefix sums of the stored counts; d_out_offsets[npairs] = records stored
+ *   d_out_matches [out_cap]     the kept records, byte-identical to the source records; nothing behind d_out_offsets[npairs] is
+ *                               written.  It must not overlap d_matches.
+ * Asynchronous on `stream` (hipStream_t, NULL = the context's stream), no host synchronisation, no allocation per call once the
+ * context's scratch has grown to the call's size (in_cap bytes - one per input record - and npairs sums; it is the verifier's
+ * scratch).  Ordered behind the context's previous call and in front of its next, like every call.
+ * BRISK_HIP_ERR_ARG, before anything is launched: NULL pairs or verify, npairs < 0, rows_cap < 1, in_cap < 0, out_cap < 0, hypotheses
+ * outside 1 ... 4096, min_inliers < 8, and - with npairs > 0 - a NULL set, a descriptor set without counts or with frames /
+ * count_stride < 1, an arithmetic-form frame outside its set, the keypoint-set errors of the gated matchers, a NULL or misaligned
+ * array (d_matches / d_out_matches 16-byte and NULL allowed when their capacity is 0, d_offsets / d_out_offsets / d_models 8-byte, the
+ * int arrays 4-byte).  npairs == 0: BRISK_HIP_OK, d_out_offsets[0] = 0 (d_out_offsets NULL is then allowed too). */
+int brisk_hip_verify_pair_matches_epipolar_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                                  const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                                  const brisk_hip_pair_spec* pairs, int rows_cap, const long long* d_offsets,
+                                                  const brisk_hip_dmatch* d_matches, long long in_cap, const brisk_hip_pair_verify* verify,
+                                                  long long out_cap, brisk_hip_pair_epipolar_model* d_models, int* d_out_counts,
+                                                  int* d_out_flags, long long* d_out_offsets, brisk_hip_dmatch* d_out_matches, void* stream);
 
 /* ---- a batch's pairs matched again inside a window around each pair's model ----------------------------------------------------
  * What reaches the linker after the verification is the part of the first pass that survived the descriptor test (Lowe's ratio

@@ -56,6 +56,10 @@ With --verify (k-NN only, profiles/verify_pairs.json) what checking the matches 
 plus V / T beside the spread of both windows, the HIP-event time of the verify call (three launches; a `rocprofv3 --kernel-trace
 --stats` pass around --verify --stats-pass gives the single kernels), the records per pair that go in and come out, the pairs with
 an accepted model, and whether the device's arrays equal the NumPy restatement of the rule on one batch's downloaded lists.
+With --epipolar (k-NN only, profiles/epipolar_pairs.json) the same two windows with brisk_hip_verify_pair_matches_epipolar_device in
+the verifier's place, E instead of V: E / T, the HIP-event time of the call, the records in and out, and whether the device's arrays
+equal the restatement of the epipolar rule (tests/test_abi_epipolar.py).  --epipolar --stats-pass runs E and, on the same lists, the
+homography verifier, so that a `rocprofv3 --kernel-trace --stats` pass around it gives k_epipolar_ransac beside k_verify_ransac.
 With --refit (k-NN only, profiles/refit_pairs.json) what fitting the pairs' models again to all their inliers adds, two windows:
   V  --verify's window V: detect + describe + match + select + verify + link + list
   R  V with brisk_hip_refit_pair_models_device (--rounds 2, the verifier's threshold, the models in place) between verify and link
@@ -349,9 +353,13 @@ def tracks_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
     ctx.close()
 
 
-def verify_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
-    """--verify: windows T and V (see the module's text); writes a.out"""
+def verify_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0, epipolar=False):
+    """--verify: windows T and V; --epipolar: windows T and E, the same with the epipolar call (see the module's text); writes a.out"""
+    from test_abi_epipolar import restated_epipolar
     from test_abi_verify import restated_verify
+    win = "E" if epipolar else "V"
+    entry = "brisk_hip_verify_pair_matches_epipolar_device" if epipolar else "brisk_hip_verify_pair_matches_device"
+    restated, model_dtype = (restated_epipolar, B.PAIR_EPIPOLAR_MODEL) if epipolar else (restated_verify, B.PAIR_MODEL)
     st = work.cuda_stream
     select = B.MatchSelect(float("inf"), 0.8, 1)
     verify = B.PairVerify(a.max_error, a.hypotheses, a.min_inliers, 1, 2024)
@@ -376,7 +384,7 @@ def verify_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
     m, cnt, rows = outs["B"]
 
-    def run(verified, timed=False):
+    def run(verified, timed=False, call=None):
         run_b0()
         ctx.check(L.brisk_hip_select_pair_matches_device(h, m.data_ptr(), cnt.data_ptr(), rows.data_ptr(), n - 1, cap, k, C.byref(select), mcap,
                                                          sel[1].data_ptr(), sel[2].data_ptr(), sel[3].data_ptr(), sel[0].data_ptr(), st))
@@ -386,10 +394,9 @@ def verify_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
             kps = ctx.batch_kp_set()
             if timed:
                 ev[0].record(work)
-            ctx.check(L.brisk_hip_verify_pair_matches_device(h, C.byref(dset), C.byref(dset), C.byref(kps), C.byref(kps), C.byref(spec), cap,
-                                                             sel[3].data_ptr(), sel[0].data_ptr(), mcap, C.byref(verify), mcap,
-                                                             models.data_ptr(), ver[1].data_ptr(), ver[2].data_ptr(), ver[3].data_ptr(),
-                                                             ver[0].data_ptr(), st))
+            ctx.check(getattr(L, call or entry)(h, C.byref(dset), C.byref(dset), C.byref(kps), C.byref(kps), C.byref(spec), cap,
+                                                sel[3].data_ptr(), sel[0].data_ptr(), mcap, C.byref(verify), mcap, models.data_ptr(),
+                                                ver[1].data_ptr(), ver[2].data_ptr(), ver[3].data_ptr(), ver[0].data_ptr(), st))
             if timed:
                 ev[1].record(work)
             src = ver
@@ -400,19 +407,21 @@ def verify_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
                                                  lists[0].data_ptr(), lists[1].data_ptr(), lists[2].data_ptr(), lists[3].data_ptr(),
                                                  lists[4].data_ptr(), st))
 
-    runs = {"T": lambda: run(False), "V": lambda: run(True)}
-    order = "TV"
-    for v in order + "TV":                                          # warm-up: buffers sized, scratch grown
+    runs = {"T": lambda: run(False), win: lambda: run(True)}
+    order = "T" + win
+    for v in order + order:                                         # warm-up: buffers sized, scratch grown
         runs[v]()
         torch.cuda.synchronize()
     if a.stats_pass:
         for _ in range(8):
-            runs["V"]()
+            runs[win]()
+            if epipolar:                                            # k_verify_ransac beside k_epipolar_ransac, on the same lists
+                run(True, call="brisk_hip_verify_pair_matches_device")
         torch.cuda.synchronize()
         return
 
     # one batch against the restatement of the rule on its downloaded lists and keypoints
-    runs["V"]()
+    runs[win]()
     torch.cuda.synchronize()
     dset, dim = ctx.batch_desc_set()
     ints = dset.count_stride
@@ -422,9 +431,9 @@ def verify_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
         kp = ctx.batch_download(f, True, strings=dim)[0]
         xy.append(np.stack([kp["x"], kp["y"]], axis=1).astype(np.float32).reshape(-1, 2))
     so, sm = sel[3].cpu().numpy(), sel[0].cpu().numpy().view(B.DMATCH).reshape(-1)
-    want = restated_verify([(p + 1, p) for p in range(n - 1)], node_rows, node_rows, cap, xy, xy, so, sm[:int(so[-1])],
-                           (a.max_error, a.hypotheses, a.min_inliers, 1, 2024), mcap, mcap)
-    got_models = models.cpu().numpy().reshape(-1).view(B.PAIR_MODEL)
+    want = restated([(p + 1, p) for p in range(n - 1)], node_rows, node_rows, cap, xy, xy, so, sm[:int(so[-1])],
+                    (a.max_error, a.hypotheses, a.min_inliers, 1, 2024), mcap, mcap)
+    got_models = models.cpu().numpy().reshape(-1).view(model_dtype)
     stored = int(want[3][-1])
     identical = bool(got_models.tobytes() == want[0].tobytes() and ver[1].cpu().numpy().tobytes() == want[1].tobytes() and
                      ver[2].cpu().numpy().tobytes() == want[2].tobytes() and ver[3].cpu().numpy().tobytes() == want[3].tobytes() and
@@ -455,8 +464,9 @@ def verify_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
     mod = want[0]
     res = {
         "workload": "bench.py's stream: %dx%d, threshold %d, %d octaves, %d frames per batch (%d distinct) in HBM; frame-to-previous-frame, "
-                    "k = %d, rows_cap %d, ratio 0.8, one match per row; verify: %d hypotheses, max_error %g, min_inliers %d, "
-                    "keep_unverified 1; tracks of min_len 3" % (W, H, THRESHOLD, OCTAVES, n, nd, k, cap, a.hypotheses, a.max_error, a.min_inliers),
+                    "k = %d, rows_cap %d, ratio 0.8, one match per row; %s: %d hypotheses, max_error %g, min_inliers %d, "
+                    "keep_unverified 1; tracks of min_len 3" % (W, H, THRESHOLD, OCTAVES, n, nd, k, cap, "epipolar verify" if epipolar else "verify",
+                                                                a.hypotheses, a.max_error, a.min_inliers),
         "kernel_revision": ctx.kernel_revision(),
         "device": torch.cuda.get_device_name(0),
         "windows": {"repeats": a.repeats, "seconds_each": a.window, "order": ", ".join(order) + " alternating; every window ends in a synchronise"},
@@ -464,17 +474,17 @@ def verify_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
         "frames_per_s_all": {v: [round(x, 1) for x in fps[v]] for v in order},
         "spread_rel": {v: round(spread[v], 4) for v in order},
         "ms_per_batch": {v: round(ms[v], 4) for v in order},
-        "verify_ms_per_batch": {"V_minus_T": round(ms["V"] - ms["T"], 4)},
-        "V_over_T_frames_per_s": round(med["V"] / med["T"], 4),
+        "verify_ms_per_batch": {win + "_minus_T": round(ms[win] - ms["T"], 4)},
+        win + "_over_T_frames_per_s": round(med[win] / med["T"], 4),
         "hip_event_ms": {"verify_call_3_launches": {"median": round(float(np.median(call_ms)), 4), "all": [round(x, 4) for x in call_ms]}},
         "per_batch": {"pairs": n - 1, "hypotheses": a.hypotheses, "records_per_pair_mean": round(float(mod["records"].mean()), 2),
                       "records_per_pair_max": int(mod["records"].max()), "usable_per_pair_mean": round(float(mod["usable"].mean()), 2),
                       "kept_per_pair_mean": round(float(want[1].mean()), 2), "pairs_with_a_model": int((mod["flags"] & B.PAIR_NO_MODEL == 0).sum()),
                       "inliers_per_model_mean": round(float(mod["inliers"][mod["flags"] & B.PAIR_NO_MODEL == 0].mean()), 2)
                       if (mod["flags"] & B.PAIR_NO_MODEL == 0).any() else 0.0},
-        "V_equals_the_restated_rule": identical,
+        win + "_equals_the_restated_rule": identical,
         "legend": {"T": "detect_describe_batch + match_knn_pairs + select + brisk_hip_link_tracks_device + brisk_hip_list_tracks_device on one stream",
-                   "V": "T with brisk_hip_verify_pair_matches_device between select and link"},
+                   win: "T with %s between select and link" % entry},
     }
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
@@ -1019,6 +1029,8 @@ def main():
     ap.add_argument("--tracks-download", action="store_true",
                     help="windows T (--tracks' T), D (tracks_download in place of the list call) and P (list, synchronise, copies, batch_download_all)")
     ap.add_argument("--verify", action="store_true", help="windows T (--tracks' T) and V (T with verify_pair_matches between select and link)")
+    ap.add_argument("--epipolar", action="store_true",
+                    help="windows T (--tracks' T) and E (T with verify_pair_matches_epipolar between select and link)")
     ap.add_argument("--guided", action="store_true",
                     help="windows V (--verify's V) and G (V + match_knn_pairs_guided on the verifier's models + select + link)")
     ap.add_argument("--refit", action="store_true",
@@ -1055,6 +1067,12 @@ def main():
             ap.error("--verify measures the k-NN pair call: without --radius / --gate / --export / --tracks / --tracks-download")
         if a.out is None:
             a.out = os.path.join(ROOT, "profiles", "verify_pairs.json")
+    if a.epipolar:
+        if radius is not None or gate or a.export or a.tracks or a.tracks_download or a.verify or a.guided or a.refit:
+            ap.error("--epipolar measures the k-NN pair call: without --radius / --gate / --export / --tracks / --tracks-download / --verify / "
+                     "--guided / --refit")
+        if a.out is None:
+            a.out = os.path.join(ROOT, "profiles", "epipolar_pairs.json")
     if a.guided:
         if radius is not None or gate or a.export or a.tracks or a.tracks_download or a.verify:
             ap.error("--guided measures the k-NN pair call: without --radius / --gate / --export / --tracks / --tracks-download / --verify")
@@ -1121,6 +1139,9 @@ def main():
         return
     if a.verify:
         verify_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b)
+        return
+    if a.epipolar:
+        verify_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b, epipolar=True)
         return
     if a.guided:
         guided_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b)
