@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "brisk_hip_verify_pair_matches_device", "brisk_hip_refit_pair_models_device",
     "brisk_hip_verify_pair_matches_epipolar_device",
     "brisk_hip_match_knn_pairs_guided_device", "brisk_hip_match_radius_pairs_guided_device",
+    "brisk_hip_match_knn_pairs_epipolar_guided_device", "brisk_hip_match_radius_pairs_epipolar_guided_device",
     "brisk_hip_link_tracks_device", "brisk_hip_list_tracks_device",
     "brisk_hip_track_points_device", "brisk_hip_tracks_download", "brisk_hip_tracks_wait",
 ]
@@ -113,6 +114,20 @@ class MatchGuide(C.Structure):
         return cls(MatchGate(-r, r, -r, r, int(max_octave_diff)), int(fallback))
 
 
+class MatchEpipolarGuide(C.Structure):
+    """brisk_hip_match_epipolar_guide: a train keypoint T may match query keypoint Q iff it lies within `band` pixels of Q's epipolar
+    line under the pair's model F and passes the gate `window` around Q itself (bounds on T - Q, max_octave_diff between Q and T);
+    fallback: a pair without a usable model - 0 = its rows match nothing, else the plain gate of `window`"""
+    _fields_ = [("window", MatchGate), ("band", C.c_float), ("fallback", C.c_int)]
+
+    @classmethod
+    def around(cls, band, window=None, max_octave_diff=-1, fallback=0):
+        """+-band pixels around the line; window: a MatchGate or its (dx_min, dx_max, dy_min, dy_max) - None = all-pass -, whose
+        octave rule is max_octave_diff"""
+        w = MatchGate.all_pass() if window is None else window if isinstance(window, MatchGate) else MatchGate(*[float(v) for v in window][:4])
+        return cls(MatchGate(w.dx_min, w.dx_max, w.dy_min, w.dy_max, int(max_octave_diff)), float(band), int(fallback))
+
+
 class MatchSelect(C.Structure):
     """brisk_hip_match_select: an entry is kept iff distance < max_distance (and it is no top-up entry); ratio > 0: Lowe's ratio
     test, the row gives at most its best entry; otherwise the leading keep_per_row entries that pass"""
@@ -148,7 +163,8 @@ PAIR_MODEL = np.dtype([("h", "<f8", (9,)), ("records", "<i4"), ("usable", "<i4")
                        ("valid", "<i4"), ("flags", "<i4")])
 
 # brisk_hip_pair_epipolar_model: the winner's normalised F (row-major, x'^T F x = 0) and the pair's counts.  PAIR_MODEL's layout under
-# another name on purpose: refit_pair_models and the guided matchers read a PAIR_MODEL as a homography
+# another name on purpose: refit_pair_models and the guided matchers read a PAIR_MODEL as a homography; the epipolar-guided matchers
+# read these
 PAIR_EPIPOLAR_MODEL = np.dtype([("f", "<f8", (9,)), ("records", "<i4"), ("usable", "<i4"), ("inliers", "<i4"), ("hypothesis", "<i4"),
                                 ("valid", "<i4"), ("flags", "<i4")])
 
@@ -369,6 +385,12 @@ def load_library():
     L.brisk_hip_match_knn_pairs_guided_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
                                                           C.POINTER(PairSpec), vp, C.POINTER(MatchGuide), C.c_int, C.c_int, C.c_int,
                                                           vp, vp, vp, vp]
+    L.brisk_hip_match_knn_pairs_epipolar_guided_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
+                                                                   C.POINTER(PairSpec), vp, C.POINTER(MatchEpipolarGuide), C.c_int, C.c_int, C.c_int,
+                                                                   vp, vp, vp, vp]
+    L.brisk_hip_match_radius_pairs_epipolar_guided_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
+                                                                      C.POINTER(PairSpec), vp, C.POINTER(MatchEpipolarGuide), C.c_int, C.c_float,
+                                                                      C.c_int, C.c_int, vp, vp, vp, vp]
     L.brisk_hip_match_radius_pairs_guided_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
                                                              C.POINTER(PairSpec), vp, C.POINTER(MatchGuide), C.c_int, C.c_float, C.c_int,
                                                              C.c_int, vp, vp, vp, vp]
@@ -791,6 +813,36 @@ class Context:
         self.check(self._L.brisk_hip_match_radius_pairs_guided_device(self._h, C.byref(query), C.byref(train), qk, tk, C.byref(pairs), mp, gp,
                                                                       int(dim_bytes), float(max_distance), cpq, int(rows_cap), m.data_ptr(),
                                                                       cnt.data_ptr(), rows.data_ptr(), C.c_void_p(stream) if stream else None))
+        return self._radius_rows(out, n, rows_cap, cpq) if download else out
+
+    # -- the pairs matched again inside a band around each epipolar line --
+    def match_knn_pairs_epipolar_guided(self, query, train, pairs, k, models, guide, rows_cap=None, query_kps=None, train_kps=None, stream=None,
+                                        dim_bytes=None, out=None, download=False):
+        """brisk_hip_match_knn_pairs_epipolar_guided_device: match_knn_pairs behind `guide` (a MatchEpipolarGuide) - the band around each
+        query keypoint's epipolar line under pair p's model models[p], inside the guide's window around the keypoint.  models: the
+        tensor verify_pair_matches_epipolar returns ([npairs, 12] int64, PAIR_EPIPOLAR_MODEL records), or any device pointer to npairs
+        records.  No cross check.  Everything else, and what is returned, as match_knn_pairs with a gate."""
+        n = pairs.npairs
+        dim_bytes, rows_cap, out = self._pairs_prologue(pairs, dim_bytes, rows_cap, k, out)
+        m, cnt, rows = out
+        qk, tk, mp, gp = self._guide_args(models, guide, query_kps, train_kps)
+        self.check(self._L.brisk_hip_match_knn_pairs_epipolar_guided_device(self._h, C.byref(query), C.byref(train), qk, tk, C.byref(pairs), mp, gp,
+                                                                            int(dim_bytes), int(k), int(rows_cap), m.data_ptr(), cnt.data_ptr(),
+                                                                            rows.data_ptr(), C.c_void_p(stream) if stream else None))
+        return self._knn_rows(out, n, rows_cap, k) if download else out
+
+    def match_radius_pairs_epipolar_guided(self, query, train, pairs, max_distance, cap_per_query, models, guide, rows_cap=None, query_kps=None,
+                                           train_kps=None, stream=None, dim_bytes=None, out=None, download=False):
+        """brisk_hip_match_radius_pairs_epipolar_guided_device: match_radius_pairs behind the epipolar guide; the conventions of
+        match_knn_pairs_epipolar_guided, and what is returned as match_radius_pairs."""
+        n, cpq = pairs.npairs, int(cap_per_query)
+        dim_bytes, rows_cap, out = self._pairs_prologue(pairs, dim_bytes, rows_cap, cpq, out)
+        m, cnt, rows = out
+        qk, tk, mp, gp = self._guide_args(models, guide, query_kps, train_kps)
+        self.check(self._L.brisk_hip_match_radius_pairs_epipolar_guided_device(self._h, C.byref(query), C.byref(train), qk, tk, C.byref(pairs), mp, gp,
+                                                                               int(dim_bytes), float(max_distance), cpq, int(rows_cap),
+                                                                               m.data_ptr(), cnt.data_ptr(), rows.data_ptr(),
+                                                                               C.c_void_p(stream) if stream else None))
         return self._radius_rows(out, n, rows_cap, cpq) if download else out
 
     # -- the pair matchers' exit: selected matches, packed --

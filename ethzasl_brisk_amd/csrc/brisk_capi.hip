@@ -1944,10 +1944,12 @@ static const char* match_gated_check(const brisk_hip_kp_set* qk, const brisk_hip
   return nullptr;
 }
 
-// What the six pair matchers (k-NN and radius, each plain, gated and guided) share.  An entry point runs its own checks and the shared
+// What the eight pair matchers (k-NN and radius, each plain, gated, guided and epipolar-guided) share.  An entry point runs its own checks and the shared
 // ones in ITS order - the k-NN forms look at the sets before npairs == 0 returns OK, the radius forms behind it - and ends in run().
 // name: "match_pairs" or "match_radius_pairs", the head of the messages; the keypoint sets and the gate: the gated forms only.
 // guided (with gated): the window is the guide's, centred by the device records `models` (one per PAIR); `gate` is not used.
+// The epipolar-guided forms are guided forms whose guide is `line` (`guide` is not used) and whose records are
+// brisk_hip_pair_epipolar_model.
 extern "C++" {  // (a member template)
 struct PairCall {
   brisk_hip_ctx* ctx;
@@ -1959,8 +1961,11 @@ struct PairCall {
   const brisk_hip_kp_set *query_kps, *train_kps;
   const brisk_hip_match_gate* gate;
   bool guided;
-  const brisk_hip_pair_model* models;
+  const void* models;
   const brisk_hip_match_guide* guide;
+  const brisk_hip_match_epipolar_guide* line;
+
+  const brisk_hip_match_gate* window() const { return !guided ? gate : line ? &line->window : &guide->window; }
 
   int err(int code, const char* what) const { return fail(ctx, code, (std::string(name) + ": " + what).c_str()); }
   // other: where the ungated forms send the caller for other sizes
@@ -1977,9 +1982,9 @@ struct PairCall {
   // launch(Q, T, P, QK, TK, G, out, stream) on the caller's stream or the context's
   template <class Launch>
   int run(int rows_cap, brisk_hip_dmatch* d_out, int* d_out_count, int* d_pair_rows, void* stream, Launch launch) const {
-    if (guided && (!guide || !models || ((uintptr_t)models & 7))) return err(BRISK_HIP_ERR_ARG, "null guide, or null or misaligned d_models");
+    if (guided && ((!guide && !line) || !models || ((uintptr_t)models & 7))) return err(BRISK_HIP_ERR_ARG, "null guide, or null or misaligned d_models");
     if (gated)
-      if (const char* msg = match_gated_check(query_kps, train_kps, guided ? &guide->window : gate)) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
+      if (const char* msg = match_gated_check(query_kps, train_kps, window())) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
     if (rows_cap < 1 || !d_out || !d_out_count || !d_pair_rows) return err(BRISK_HIP_ERR_ARG, "bad output argument");
     const int np = pairs->npairs;
     if (!pairs->d_pairs) {  // (a list on the device is checked there: d_pair_rows = -1)
@@ -2002,7 +2007,7 @@ struct PairCall {
     if (gated) {
       QK = BriskKpSet{reinterpret_cast<const char*>(query_kps->d_kps), query_kps->frame_pitch};
       TK = BriskKpSet{reinterpret_cast<const char*>(train_kps->d_kps), train_kps->frame_pitch};
-      const brisk_hip_match_gate* g = guided ? &guide->window : gate;
+      const brisk_hip_match_gate* g = window();
       G = BriskMatchGate{g->dx_min, g->dx_max, g->dy_min, g->dy_max, g->max_octave_diff};
     }
     if (!launch(Q, T, P, QK, TK, G, reinterpret_cast<BriskDMatch*>(d_out), st)) return err(BRISK_HIP_ERR_UNSUPPORTED, "descriptor size not covered");
@@ -2026,6 +2031,10 @@ static int match_knn_pairs_call(const PairCall& C, int k, int cross_check, int r
                [&](const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, const BriskKpSet& QK, const BriskKpSet& TK,
                    const BriskMatchGate& G, BriskDMatch* out, hipStream_t st) {
                  const bool cross = cross_check != 0;
+                 if (C.line)
+                   return brisk_launch_match_knn_pairs_epiline(Q, T, QK, TK, reinterpret_cast<const BriskPairEpipolarModel*>(C.models),
+                                                               BriskMatchEpiGuide{G, C.line->band, C.line->fallback}, P, C.dim_bytes / 4, k, rows_cap,
+                                                               out, d_out_count, d_pair_rows, st);
                  if (C.guided)
                    return brisk_launch_match_knn_pairs_guided(Q, T, QK, TK, reinterpret_cast<const BriskPairModel*>(C.models),
                                                               BriskMatchGuide{G, C.guide->fallback}, P, C.dim_bytes / 4, k, rows_cap, out, d_out_count,
@@ -2046,6 +2055,10 @@ static int match_radius_pairs_call(const PairCall& C, float max_distance, int ca
   return C.run(rows_cap, d_out, d_out_count, d_pair_rows, stream,
                [&](const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, const BriskKpSet& QK, const BriskKpSet& TK,
                    const BriskMatchGate& G, BriskDMatch* out, hipStream_t st) {
+                 if (C.line)
+                   return brisk_launch_match_radius_pairs_epiline(Q, T, QK, TK, reinterpret_cast<const BriskPairEpipolarModel*>(C.models),
+                                                                  BriskMatchEpiGuide{G, C.line->band, C.line->fallback}, P, C.dim_bytes / 4, max_distance,
+                                                                  cap_per_query, rows_cap, out, d_out_count, d_pair_rows, st);
                  if (C.guided)
                    return brisk_launch_match_radius_pairs_guided(Q, T, QK, TK, reinterpret_cast<const BriskPairModel*>(C.models),
                                                                  BriskMatchGuide{G, C.guide->fallback}, P, C.dim_bytes / 4, max_distance, cap_per_query,
@@ -2114,6 +2127,31 @@ int brisk_hip_match_radius_pairs_guided_device(brisk_hip_ctx* ctx, const brisk_h
   if (!ctx) return BRISK_HIP_ERR_ARG;
   std::lock_guard<std::mutex> lock(ctx->mu);
   return match_radius_pairs_call({ctx, "match_radius_pairs", query, train, pairs, dim_bytes, true, query_kps, train_kps, nullptr, true, d_models, guide},
+                                 max_distance, cap_per_query, rows_cap, d_out, d_out_count, d_pair_rows, stream);
+}
+// the epipolar-guided forms (brisk_match_epiline.h): the gated calls behind the band around each query keypoint's epipolar line under
+// the pair's model; no cross check.  The model argument's type keeps a homography record out
+static_assert(sizeof(brisk_hip_match_epipolar_guide) == 28 && sizeof(BriskMatchEpiGuide) == 28, "epipolar match guide layout");
+int brisk_hip_match_knn_pairs_epipolar_guided_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                                     const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                                     const brisk_hip_pair_spec* pairs, const brisk_hip_pair_epipolar_model* d_models,
+                                                     const brisk_hip_match_epipolar_guide* guide, int dim_bytes, int k, int rows_cap,
+                                                     brisk_hip_dmatch* d_out, int* d_out_count, int* d_pair_rows, void* stream) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  return match_knn_pairs_call({ctx, "match_pairs", query, train, pairs, dim_bytes, true, query_kps, train_kps, nullptr, true, d_models, nullptr, guide}, k,
+                              0, rows_cap, d_out, d_out_count, d_pair_rows, stream);
+}
+int brisk_hip_match_radius_pairs_epipolar_guided_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                                        const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                                        const brisk_hip_pair_spec* pairs, const brisk_hip_pair_epipolar_model* d_models,
+                                                        const brisk_hip_match_epipolar_guide* guide, int dim_bytes, float max_distance,
+                                                        int cap_per_query, int rows_cap, brisk_hip_dmatch* d_out, int* d_out_count,
+                                                        int* d_pair_rows, void* stream) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  return match_radius_pairs_call({ctx, "match_radius_pairs", query, train, pairs, dim_bytes, true, query_kps, train_kps, nullptr, true, d_models, nullptr,
+                                  guide},
                                  max_distance, cap_per_query, rows_cap, d_out, d_out_count, d_pair_rows, stream);
 }
 

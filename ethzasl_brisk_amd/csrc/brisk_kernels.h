@@ -4,6 +4,7 @@
 
 #include "brisk_common.h"
 #include "brisk_match_gate.h"
+#include "brisk_match_epiline.h"
 #include "brisk_match_guide.h"
 #include "brisk_match_select.h"
 #include "brisk_pair_verify.h"
@@ -202,6 +203,16 @@ bool brisk_launch_match_radius_pairs_guided(const BriskDescSet& Q, const BriskDe
                                             const BriskPairModel* models, const BriskMatchGuide& guide, const BriskPairSpec& P, int words32,
                                             float max_distance, int cap, int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows,
                                             hipStream_t s);
+
+// the gated matchers behind the band around the query keypoint's epipolar line under pair p's model models[p]
+// (brisk_match_epiline.h): k-NN without the cross check, and radius.  models: device, [npairs], indexed by PAIR
+bool brisk_launch_match_knn_pairs_epiline(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
+                                          const BriskPairEpipolarModel* models, const BriskMatchEpiGuide& guide, const BriskPairSpec& P,
+                                          int words32, int k, int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s);
+bool brisk_launch_match_radius_pairs_epiline(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
+                                             const BriskPairEpipolarModel* models, const BriskMatchEpiGuide& guide, const BriskPairSpec& P,
+                                             int words32, float max_distance, int cap, int rows_cap, BriskDMatch* out, int* out_count,
+                                             int* pair_rows, hipStream_t s);
 
 // ---- the pair matchers' exit: selected matches, packed (brisk_match_export.hip; the rule: brisk_match_select.h) ----
 // flags of a pair (mirror BRISK_HIP_PAIR_* / BRISK_HIP_ROWS_CUT of brisk_hip.h)

@@ -25,6 +25,10 @@
 //   k_guided_knn_pairs          the gated k-NN kernel (no cross check) with the window centred where the pair's model puts the
 //                               lane's query keypoint (brisk_match_guide.h): a per-lane fp64 prologue in front of the same scan
 //   k_guided_radius_pairs       the gated radius kernel, guided the same way
+//   k_epiline_knn_pairs, k_epiline_radius_pairs
+//                               the gated kernels (no cross check) behind the band around the lane's epipolar line under the
+//                               pair's model (brisk_match_epiline.h): the line is made per lane in front of the same scan, the
+//                               band is three fp64 multiplies per passing row beside the gate's compares
 //   k_match_radius_pairs[_gated], k_match_radius_pairs_one
 //                               radius matching in the same shape (mrp_body): hits collected in a short LDS list per
 //                               query and ranked; a query with more hits than the list holds is redone by one wave
@@ -403,6 +407,21 @@ __device__ __forceinline__ bool mpu_lane(const BriskPairModel* __restrict__ M, b
   const BriskMatchGuide U{window, fallback};
   return brisk_guide_lane(U, guided, H, kp->x, kp->y, kp->octave, L);
 }
+// The kinds of guide of mp_body / mrp_body, and the model record each reads
+#define MP_GUIDE_NONE 0
+#define MP_GUIDE_CENTRE 1  // brisk_match_guide.h: the window centred at H(kp)
+#define MP_GUIDE_LINE 2    // brisk_match_epiline.h: the window at kp itself, and the band around F kp
+template <int GUIDE>
+using MpModelOf = std::conditional_t<GUIDE == MP_GUIDE_LINE, BriskPairEpipolarModel, BriskPairModel>;
+// The epipolar guide: the lane of query keypoint kp in a pair whose model record is *M - the gate's own lane and the line F kp with
+// the band's bound w.  M is wave-uniform as in mpu_lane; what stays live across the scan is the lane and four doubles.
+// false: the row matches nothing.
+__device__ __forceinline__ bool mpe_lane(const BriskPairEpipolarModel* __restrict__ M, bool guided, const BriskMatchGate& window, float band,
+                                         int fallback, const BriskKeyPoint* kp, BriskEpiLane& L) {
+  const BriskFundamental F{M->f[0], M->f[1], M->f[2], M->f[3], M->f[4], M->f[5], M->f[6], M->f[7], M->f[8]};
+  const BriskMatchEpiGuide U{window, band, fallback};
+  return brisk_epiguide_lane(U, guided, F, kp->x, kp->y, kp->octave, L);
+}
 
 // The gated scans.  The keypoint of the wave-uniform row comes through the same scalar loads as the row itself, MPG_CHUNK records
 // ahead of the rows they belong to (one wait for the chunk, not one per row); the predicate is a handful of VALU compares whose
@@ -413,26 +432,32 @@ __device__ __forceinline__ bool mpu_lane(const BriskPairModel* __restrict__ M, b
 // its rows instead of one load and wait in front of each.  (No scheduling barrier between the loads and the compares: with one
 // the compiler no longer takes the loop's loads - the descriptor rows included - for scalar loads.)
 // SWAP (the cross check): the roles swap - the lane holds the train side's keypoint, the row passing by is a query row.
+// LINE (the epipolar guide, never with SWAP): the row must also lie in the band around the lane's line *E when `band` (wave-uniform:
+// the pair is guided) is set.
 #define MPG_CHUNK 4
-template <bool SWAP>
+template <bool SWAP, bool LINE = false>
 __device__ __forceinline__ void mpg_allowed(const BriskMatchGate& g, const BriskGateLane& L, bool on, const char* kps, int tc, int t1,
-                                            bool (&ok)[MPG_CHUNK], unsigned long long (&live)[MPG_CHUNK]) {
+                                            bool (&ok)[MPG_CHUNK], unsigned long long (&live)[MPG_CHUNK], const BriskEpiLine* E = nullptr,
+                                            bool band = false) {
 #pragma unroll
   for (int i = 0; i < MPG_CHUNK; ++i) {
     const BriskKeyPoint* kp = mp_kp(kps, min(tc + i, t1 - 1));
-    const bool pass = SWAP ? brisk_gate_train_lane(g, L, kp->x, kp->y, kp->octave) : brisk_gate_query_lane(g, L, kp->x, kp->y, kp->octave);
+    const bool pass = LINE   ? brisk_epiguide_query_lane(g, band, L, *E, kp->x, kp->y, kp->octave)
+                      : SWAP ? brisk_gate_train_lane(g, L, kp->x, kp->y, kp->octave)
+                             : brisk_gate_query_lane(g, L, kp->x, kp->y, kp->octave);
     ok[i] = on && tc + i < t1 && pass;
     live[i] = __ballot(ok[i]);
   }
 }
 // mp_scan behind the gate: the two smallest keys among the allowed rows
-template <int W32, bool ALIGNED, bool SWAP>
+template <int W32, bool ALIGNED, bool SWAP, bool LINE = false>
 __device__ __forceinline__ void mpg_scan(const unsigned (&qv)[W32], const uint8_t* rows, int pitch, int t0, int t1, const BriskMatchGate& g,
-                                         const BriskGateLane& L, bool on, const char* kps, unsigned& b1, unsigned& b2) {
+                                         const BriskGateLane& L, bool on, const char* kps, unsigned& b1, unsigned& b2,
+                                         const BriskEpiLine* E = nullptr, bool band = false) {
   for (int tc = t0; tc < t1; tc += MPG_CHUNK) {
     bool ok[MPG_CHUNK];
     unsigned long long live[MPG_CHUNK];
-    mpg_allowed<SWAP>(g, L, on, kps, tc, t1, ok, live);
+    mpg_allowed<SWAP, LINE>(g, L, on, kps, tc, t1, ok, live, E, band);
 #pragma unroll
     for (int i = 0; i < MPG_CHUNK; ++i) {
       if (live[i] == 0) continue;  // wave-uniform
@@ -444,17 +469,19 @@ __device__ __forceinline__ void mpg_scan(const unsigned (&qv)[W32], const uint8_
 }
 
 // this wave's slice of the n rows of one frame against the lane's descriptor: the two smallest keys.  GATE: `self` is the lane's
-// own keypoint, kps the records of the rows passing by; `guided` (the guided kernels): the lane as mpu_lane made it, instead of self's
-template <int W32, bool GATE, bool SWAP>
+// own keypoint, kps the records of the rows passing by; `guided` (the guided kernels): the lane as mpu_lane made it, instead of self's;
+// LINE: `guided` and *E are what mpe_lane made, `band` as in mpg_allowed
+template <int W32, bool GATE, bool SWAP, bool LINE = false>
 __device__ __forceinline__ void mp_scan_slice(const unsigned (&v)[W32], const uint8_t* rows, int pitch, bool aligned, int n, int wave,
                                               const BriskMatchGate& g, const BriskKeyPoint* self, bool on, const char* kps, unsigned& b1,
-                                              unsigned& b2, const BriskGateLane* guided = nullptr) {
+                                              unsigned& b2, const BriskGateLane* guided = nullptr, const BriskEpiLine* E = nullptr,
+                                              bool band = false) {
   const int per = (n + MP_WAVES - 1) / MP_WAVES;
   const int t0 = __builtin_amdgcn_readfirstlane(wave * per), t1 = min(n, t0 + per);
   if (GATE) {
     const BriskGateLane L = guided ? *guided : brisk_gate_lane(g, self->x, self->y, self->octave);
-    if (aligned) mpg_scan<W32, true, SWAP>(v, rows, pitch, t0, t1, g, L, on, kps, b1, b2);
-    else mpg_scan<W32, false, SWAP>(v, rows, pitch, t0, t1, g, L, on, kps, b1, b2);
+    if (aligned) mpg_scan<W32, true, SWAP, LINE>(v, rows, pitch, t0, t1, g, L, on, kps, b1, b2, E, band);
+    else mpg_scan<W32, false, SWAP, LINE>(v, rows, pitch, t0, t1, g, L, on, kps, b1, b2, E, band);
   } else {
     if (aligned) mp_scan<W32, true>(v, rows, pitch, t0, t1, b1, b2);  // (batch results: 4-byte aligned rows at pitch 64)
     else mp_scan<W32, false>(v, rows, pitch, t0, t1, b1, b2);         // (a caller's set whose base, frame pitch or row pitch is not)
@@ -469,12 +496,13 @@ __device__ __forceinline__ void mp_scan_slice(const unsigned (&v)[W32], const ui
 // GATE: a lane the gate forbids keeps MF_NO_KEY, so a row holds min(k, allowed rows) REAL matches and is never topped up; in the
 // cross check a lane without a forward match takes no part.
 // GUIDE (with GATE, without CROSS): `gate` is the guide's window, centred by models[p] (mpu_lane); a lane whose row has no centre
-// takes no part, and a pair without a usable model and without the fallback has empty rows.
-template <int W32, bool CROSS, bool GATE, bool GUIDE = false>
+// takes no part, and a pair without a usable model and without the fallback has empty rows.  GUIDE == MP_GUIDE_LINE: the window stays
+// at the lane's own keypoint, and the lane carries its epipolar line under models[p] and `band` (mpe_lane).
+template <int W32, bool CROSS, bool GATE, int GUIDE = MP_GUIDE_NONE>
 __device__ __forceinline__ void mp_body(const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, int pair0, int k, int rows_cap,
                                         BriskDMatch* __restrict__ out, int* __restrict__ out_count, int* __restrict__ pair_rows,
                                         const BriskKpSet& QK, const BriskKpSet& TK, const BriskMatchGate& gate,
-                                        const BriskPairModel* __restrict__ models = nullptr, int fallback = 0) {
+                                        const MpModelOf<GUIDE>* __restrict__ models = nullptr, int fallback = 0, float band = 0.f) {
   __shared__ unsigned part[MP_WAVES][2][64];
   __shared__ unsigned fwd[64];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -497,7 +525,12 @@ __device__ __forceinline__ void mp_body(const BriskDescSet& Q, const BriskDescSe
   {
     unsigned qv[W32];
     mp_load_row<W32>(qrows + (long)min(q, R.rows - 1) * Q.row_pitch, R.q_aligned, qv);
-    if (GUIDE) {
+    if constexpr (GUIDE == MP_GUIDE_LINE) {
+      BriskEpiLane L;
+      const bool has = mpe_lane(models + p, guided, gate, band, fallback, mp_kp(qk, min(q, R.rows - 1)), L);
+      mp_scan_slice<W32, GATE, false, true>(qv, trows, T.row_pitch, R.t_aligned, R.n_b, wave, gate, nullptr, q < R.rows && has, tk, b1, b2, &L.gate,
+                                            &L.line, guided);
+    } else if constexpr (GUIDE == MP_GUIDE_CENTRE) {
       BriskGateLane L;
       const bool has = mpu_lane(models + p, guided, gate, fallback, mp_kp(qk, min(q, R.rows - 1)), L);
       mp_scan_slice<W32, GATE, false>(qv, trows, T.row_pitch, R.t_aligned, R.n_b, wave, gate, nullptr, q < R.rows && has, tk, b1, b2, &L);
@@ -574,7 +607,16 @@ __global__ void __launch_bounds__(MP_WAVES * 64) k_guided_knn_pairs(const BriskD
                                                                      const BriskMatchGuide guide, const BriskPairSpec P, int pair0, int k,
                                                                      int rows_cap, BriskDMatch* __restrict__ out, int* __restrict__ out_count,
                                                                      int* __restrict__ pair_rows) {
-  mp_body<W32, false, true, true>(Q, T, P, pair0, k, rows_cap, out, out_count, pair_rows, QK, TK, guide.window, models, guide.fallback);
+  mp_body<W32, false, true, MP_GUIDE_CENTRE>(Q, T, P, pair0, k, rows_cap, out, out_count, pair_rows, QK, TK, guide.window, models, guide.fallback);
+}
+template <int W32>
+__global__ void __launch_bounds__(MP_WAVES * 64) k_epiline_knn_pairs(const BriskDescSet Q, const BriskDescSet T, const BriskKpSet QK,
+                                                                      const BriskKpSet TK, const BriskPairEpipolarModel* __restrict__ models,
+                                                                      const BriskMatchEpiGuide guide, const BriskPairSpec P, int pair0, int k,
+                                                                      int rows_cap, BriskDMatch* __restrict__ out, int* __restrict__ out_count,
+                                                                      int* __restrict__ pair_rows) {
+  mp_body<W32, false, true, MP_GUIDE_LINE>(Q, T, P, pair0, k, rows_cap, out, out_count, pair_rows, QK, TK, guide.window, models, guide.fallback,
+                                           guide.band);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -609,14 +651,14 @@ __device__ __forceinline__ void mrp_scan(const unsigned (&qv)[W32], const uint8_
   }
 }
 // mrp_scan behind the gate (mpg_scan's loop)
-template <int W32, bool ALIGNED>
+template <int W32, bool ALIGNED, bool LINE = false>
 __device__ __forceinline__ void mrpg_scan(const unsigned (&qv)[W32], const uint8_t* rows, int pitch, int t0, int t1, unsigned thr,
                                           const BriskMatchGate& g, const BriskGateLane& L, bool on, const char* kps, int* cnt,
-                                          unsigned (*list)[64], int lane) {
+                                          unsigned (*list)[64], int lane, const BriskEpiLine* E = nullptr, bool band = false) {
   for (int tc = t0; tc < t1; tc += MPG_CHUNK) {
     bool ok[MPG_CHUNK];
     unsigned long long live[MPG_CHUNK];
-    mpg_allowed<false>(g, L, on, kps, tc, t1, ok, live);
+    mpg_allowed<false, LINE>(g, L, on, kps, tc, t1, ok, live, E, band);
 #pragma unroll
     for (int i = 0; i < MPG_CHUNK; ++i) {
       if (live[i] == 0) continue;  // wave-uniform
@@ -626,26 +668,30 @@ __device__ __forceinline__ void mrpg_scan(const unsigned (&qv)[W32], const uint8
     }
   }
 }
-// the dense path's distance of train row t (one per lane) to the wave's query; GATE: a row the gate forbids is no hit (thr)
-template <int W32, bool ALIGNED, bool GATE>
+// the dense path's distance of train row t (one per lane) to the wave's query; GATE: a row the gate forbids is no hit (thr);
+// LINE: nor is a row outside the band around the query's line *E (wave-uniform) when `band` is set
+template <int W32, bool ALIGNED, bool GATE, bool LINE = false>
 __device__ __forceinline__ unsigned mrp_dense_dist(const unsigned (&uq)[W32], const uint8_t* trows, int t_pitch, int t, unsigned thr,
-                                                   const MpGate& G, const BriskGateLane& QL) {
-  if (GATE) {
+                                                   const MpGate& G, const BriskGateLane& QL, const BriskEpiLine* E = nullptr, bool band = false) {
+  if (LINE) {
+    const BriskKeyPoint* kp = mp_kp(G.tk, t);
+    if (!brisk_epiguide_query_lane(G.g, band, QL, *E, kp->x, kp->y, kp->octave)) return thr;
+  } else if (GATE) {
     const BriskKeyPoint* kp = mp_kp(G.tk, t);
     if (!brisk_gate_query_lane(G.g, QL, kp->x, kp->y, kp->octave)) return thr;
   }
   return m_dist<W32, ALIGNED>(uq, trows + (long)t * t_pitch);
 }
 // one wave, one query with more than MRP_LIST hits.  bins: thr + 1 ints of this wave's own
-template <int W32, bool ALIGNED, bool GATE>
+template <int W32, bool ALIGNED, bool GATE, bool LINE = false>
 __device__ __forceinline__ void mrp_dense(int* bins, const unsigned (&uq)[W32], const uint8_t* trows, int t_pitch, int n_b, unsigned thr,
                                           int cap, int lane, int q, int img, BriskDMatch* __restrict__ orow, const MpGate& G,
-                                          const BriskGateLane& QL) {
+                                          const BriskGateLane& QL, const BriskEpiLine* E = nullptr, bool band = false) {
   for (int b = lane; b <= (int)thr; b += 64) bins[b] = 0;
   __builtin_amdgcn_s_waitcnt(0);
   __builtin_amdgcn_wave_barrier();
   for (int t = lane; t < n_b; t += 64) {
-    const unsigned d = mrp_dense_dist<W32, ALIGNED, GATE>(uq, trows, t_pitch, t, thr, G, QL);
+    const unsigned d = mrp_dense_dist<W32, ALIGNED, GATE, LINE>(uq, trows, t_pitch, t, thr, G, QL, E, band);
     if (d < thr) atomicAdd(&bins[d], 1);
   }
   __builtin_amdgcn_s_waitcnt(0);
@@ -678,7 +724,7 @@ __device__ __forceinline__ void mrp_dense(int* bins, const unsigned (&uq)[W32], 
   for (int t0 = 0; t0 < n_b; t0 += 64) {
     const int t = t0 + lane;
     unsigned d = thr;
-    if (t < n_b) d = mrp_dense_dist<W32, ALIGNED, GATE>(uq, trows, t_pitch, t, thr, G, QL);
+    if (t < n_b) d = mrp_dense_dist<W32, ALIGNED, GATE, LINE>(uq, trows, t_pitch, t, thr, G, QL, E, band);
     const bool hit = d < thr && bins[d] < cap;
     unsigned long long todo = __ballot(hit);
     while (todo) {
@@ -704,12 +750,14 @@ __device__ __forceinline__ void mrp_dense(int* bins, const unsigned (&uq)[W32], 
 }
 
 // the workgroup's 64 query rows [blockIdx.x * 64, ...) of `rows` against the n_b train rows; out / out_count: row 0 of this query set
-// GUIDE (with GATE): G.g is the guide's window, centred by the pair's model record *model (mpu_lane)
-template <int W32, bool GATE = false, bool GUIDE = false>
+// GUIDE (with GATE): G.g is the guide's window, centred by the pair's model record *model (mpu_lane); MP_GUIDE_LINE: the window stays at
+// the query keypoint and the rows pass the band around its line under *model (mpe_lane)
+template <int W32, bool GATE = false, int GUIDE = MP_GUIDE_NONE>
 __device__ __forceinline__ void mrp_body(const uint8_t* qrows, int q_pitch, bool q_aligned, int rows, const uint8_t* trows, int t_pitch,
                                          bool t_aligned, int n_b, float max_distance, int cap, int img, BriskDMatch* __restrict__ out,
                                          int* __restrict__ out_count, const MpGate& G = MpGate(),
-                                         const BriskPairModel* __restrict__ model = nullptr, bool guided = false, int fallback = 0) {
+                                         const MpModelOf<GUIDE>* __restrict__ model = nullptr, bool guided = false, int fallback = 0,
+                                         float band = 0.f) {
   __shared__ int cnt[64];
   __shared__ unsigned list[MRP_LIST][64];
   __shared__ int bins[MP_WAVES][MRP_BINS + 3];
@@ -732,12 +780,19 @@ __device__ __forceinline__ void mrp_body(const uint8_t* qrows, int q_pitch, bool
     const int t0 = wave * per, t1 = min(n_b, t0 + per);
     if (GATE) {
       const BriskKeyPoint* kp = mp_kp(G.qk, min(q, rows - 1));
-      BriskGateLane L;
       bool on = q < rows;
-      if (GUIDE) on = mpu_lane(model, guided, G.g, fallback, kp, L) && on;
-      else L = brisk_gate_lane(G.g, kp->x, kp->y, kp->octave);
-      if (t_aligned) mrpg_scan<W32, true>(qv, trows, t_pitch, t0, t1, thr, G.g, L, on, G.tk, cnt, list, lane);
-      else mrpg_scan<W32, false>(qv, trows, t_pitch, t0, t1, thr, G.g, L, on, G.tk, cnt, list, lane);
+      if constexpr (GUIDE == MP_GUIDE_LINE) {
+        BriskEpiLane L;
+        on = mpe_lane(model, guided, G.g, band, fallback, kp, L) && on;
+        if (t_aligned) mrpg_scan<W32, true, true>(qv, trows, t_pitch, t0, t1, thr, G.g, L.gate, on, G.tk, cnt, list, lane, &L.line, guided);
+        else mrpg_scan<W32, false, true>(qv, trows, t_pitch, t0, t1, thr, G.g, L.gate, on, G.tk, cnt, list, lane, &L.line, guided);
+      } else {
+        BriskGateLane L;
+        if (GUIDE) on = mpu_lane(model, guided, G.g, fallback, kp, L) && on;
+        else L = brisk_gate_lane(G.g, kp->x, kp->y, kp->octave);
+        if (t_aligned) mrpg_scan<W32, true>(qv, trows, t_pitch, t0, t1, thr, G.g, L, on, G.tk, cnt, list, lane);
+        else mrpg_scan<W32, false>(qv, trows, t_pitch, t0, t1, thr, G.g, L, on, G.tk, cnt, list, lane);
+      }
     } else {
       if (t_aligned) mrp_scan<W32, true>(qv, trows, t_pitch, t0, t1, thr_lane, cnt, list, lane);
       else mrp_scan<W32, false>(qv, trows, t_pitch, t0, t1, thr_lane, cnt, list, lane);
@@ -771,17 +826,26 @@ __device__ __forceinline__ void mrp_body(const uint8_t* qrows, int q_pitch, bool
     if (cnt[ql] <= MRP_LIST) continue;
     unsigned uq[W32];
     mp_load_row<W32>(qrows + (long)qq * q_pitch, q_aligned, uq);
-    BriskGateLane QL = {};
-    if (GATE) {
-      const BriskKeyPoint* kp = mp_kp(G.qk, qq);  // (wave-uniform)
-      if (GUIDE) {  // (the model is read again: a rare path, and nothing of it stays live across the scan)
-        if (!mpu_lane(model, guided, G.g, fallback, kp, QL)) continue;  // (cannot be: a row without a centre has no hits)
-      } else {
-        QL = brisk_gate_lane(G.g, kp->x, kp->y, kp->octave);
+    if constexpr (GUIDE == MP_GUIDE_LINE) {  // (the model is read again, as below; the query's line is wave-uniform)
+      BriskEpiLane QE;
+      if (!mpe_lane(model, guided, G.g, band, fallback, mp_kp(G.qk, qq), QE)) continue;  // (cannot be: a row without a line has no hits)
+      if (t_aligned)
+        mrp_dense<W32, true, GATE, true>(bins[wave], uq, trows, t_pitch, n_b, thr, cap, lane, qq, img, out + (long)qq * cap, G, QE.gate, &QE.line, guided);
+      else
+        mrp_dense<W32, false, GATE, true>(bins[wave], uq, trows, t_pitch, n_b, thr, cap, lane, qq, img, out + (long)qq * cap, G, QE.gate, &QE.line, guided);
+    } else {
+      BriskGateLane QL = {};
+      if (GATE) {
+        const BriskKeyPoint* kp = mp_kp(G.qk, qq);  // (wave-uniform)
+        if (GUIDE) {  // (the model is read again: a rare path, and nothing of it stays live across the scan)
+          if (!mpu_lane(model, guided, G.g, fallback, kp, QL)) continue;  // (cannot be: a row without a centre has no hits)
+        } else {
+          QL = brisk_gate_lane(G.g, kp->x, kp->y, kp->octave);
+        }
       }
+      if (t_aligned) mrp_dense<W32, true, GATE>(bins[wave], uq, trows, t_pitch, n_b, thr, cap, lane, qq, img, out + (long)qq * cap, G, QL);
+      else mrp_dense<W32, false, GATE>(bins[wave], uq, trows, t_pitch, n_b, thr, cap, lane, qq, img, out + (long)qq * cap, G, QL);
     }
-    if (t_aligned) mrp_dense<W32, true, GATE>(bins[wave], uq, trows, t_pitch, n_b, thr, cap, lane, qq, img, out + (long)qq * cap, G, QL);
-    else mrp_dense<W32, false, GATE>(bins[wave], uq, trows, t_pitch, n_b, thr, cap, lane, qq, img, out + (long)qq * cap, G, QL);
   }
 }
 
@@ -822,8 +886,25 @@ __global__ void __launch_bounds__(MP_WAVES * 64) k_guided_radius_pairs(const Bri
   const bool guided = brisk_guide_guided(models[p].hypothesis, models[p].flags);  // (wave-uniform)
   const int n_b = guided || guide.fallback != 0 ? R.n_b : 0;  // a pair without a usable model and without the fallback: empty rows
   const MpGate G{guide.window, QK.kps + (long)R.a * QK.frame_pitch, TK.kps + (long)R.b * TK.frame_pitch};
-  mrp_body<W32, true, true>(mp_frame(Q, R.a), Q.row_pitch, R.q_aligned, R.rows, mp_frame(T, R.b), T.row_pitch, R.t_aligned, n_b, max_distance, cap,
-                            R.b, out + (long)p * rows_cap * cap, out_count + (long)p * rows_cap, G, models + p, guided, guide.fallback);
+  mrp_body<W32, true, MP_GUIDE_CENTRE>(mp_frame(Q, R.a), Q.row_pitch, R.q_aligned, R.rows, mp_frame(T, R.b), T.row_pitch, R.t_aligned, n_b, max_distance,
+                                       cap, R.b, out + (long)p * rows_cap * cap, out_count + (long)p * rows_cap, G, models + p, guided, guide.fallback);
+}
+template <int W32>
+__global__ void __launch_bounds__(MP_WAVES * 64) k_epiline_radius_pairs(const BriskDescSet Q, const BriskDescSet T, const BriskKpSet QK,
+                                                                         const BriskKpSet TK, const BriskPairEpipolarModel* __restrict__ models,
+                                                                         const BriskMatchEpiGuide guide, const BriskPairSpec P, int pair0,
+                                                                         float max_distance, int cap, int rows_cap,
+                                                                         BriskDMatch* __restrict__ out, int* __restrict__ out_count,
+                                                                         int* __restrict__ pair_rows) {
+  const int p = pair0 + blockIdx.y;
+  MpPair R;
+  if (!mp_resolve(Q, T, P, p, false, rows_cap, pair_rows, R)) return;
+  const bool guided = brisk_guide_guided(models[p].hypothesis, models[p].flags);  // (wave-uniform)
+  const int n_b = guided || guide.fallback != 0 ? R.n_b : 0;  // a pair without a usable model and without the fallback: empty rows
+  const MpGate G{guide.window, QK.kps + (long)R.a * QK.frame_pitch, TK.kps + (long)R.b * TK.frame_pitch};
+  mrp_body<W32, true, MP_GUIDE_LINE>(mp_frame(Q, R.a), Q.row_pitch, R.q_aligned, R.rows, mp_frame(T, R.b), T.row_pitch, R.t_aligned, n_b, max_distance,
+                                     cap, R.b, out + (long)p * rows_cap * cap, out_count + (long)p * rows_cap, G, models + p, guided, guide.fallback,
+                                     guide.band);
 }
 // one query set against one train set, counts from the host (brisk_hip_match_radius_device); grid ceil(nq / 64)
 template <int W32>
@@ -924,6 +1005,27 @@ bool brisk_launch_match_radius_pairs_guided(const BriskDescSet& Q, const BriskDe
   return m_dispatch_words(words32, [&](auto W) {
     mp_launch_pairs(P.npairs, rows_cap, [&](dim3 grid, int p0) {
       hipLaunchKernelGGL(k_guided_radius_pairs<decltype(W)::value>, grid, dim3(MP_WAVES * 64), 0, s, Q, T, QK, TK, models, guide, P, p0, max_distance,
+                         cap, rows_cap, out, out_count, pair_rows);
+    });
+  });
+}
+bool brisk_launch_match_knn_pairs_epiline(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
+                                          const BriskPairEpipolarModel* models, const BriskMatchEpiGuide& guide, const BriskPairSpec& P,
+                                          int words32, int k, int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s) {
+  return m_dispatch_words(words32, [&](auto W) {
+    mp_launch_pairs(P.npairs, rows_cap, [&](dim3 grid, int p0) {
+      hipLaunchKernelGGL(k_epiline_knn_pairs<decltype(W)::value>, grid, dim3(MP_WAVES * 64), 0, s, Q, T, QK, TK, models, guide, P, p0, k, rows_cap, out,
+                         out_count, pair_rows);
+    });
+  });
+}
+bool brisk_launch_match_radius_pairs_epiline(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
+                                             const BriskPairEpipolarModel* models, const BriskMatchEpiGuide& guide, const BriskPairSpec& P,
+                                             int words32, float max_distance, int cap, int rows_cap, BriskDMatch* out, int* out_count,
+                                             int* pair_rows, hipStream_t s) {
+  return m_dispatch_words(words32, [&](auto W) {
+    mp_launch_pairs(P.npairs, rows_cap, [&](dim3 grid, int p0) {
+      hipLaunchKernelGGL(k_epiline_radius_pairs<decltype(W)::value>, grid, dim3(MP_WAVES * 64), 0, s, Q, T, QK, TK, models, guide, P, p0, max_distance,
                          cap, rows_cap, out, out_count, pair_rows);
     });
   });

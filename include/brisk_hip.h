@@ -719,8 +719,9 @@ int brisk_hip_refit_pair_models_device(brisk_hip_ctx* ctx, const brisk_hip_desc_
  * F is the linear eight-point solution and in general has no epipoles; it is not meant for rectification or for recovering a pose.
  * Eight coplanar points (and a scene that is a plane) give a degenerate system; its null vector still vanishes on the plane's
  * records, so the plane is kept - with more random records beside it than a proper F lets through.
- * Not done here: essential matrices (no intrinsics enter), the refit of F to all its inliers, guided matching along epipolar lines,
- * seven- or five-point samples, adaptive stopping. */
+ * Not done here: essential matrices (no intrinsics enter), the refit of F to all its inliers, seven- or five-point samples, adaptive
+ * stopping.  The second pass - guided matching along epipolar lines - reads these models in place: "a batch's pairs matched again
+ * inside a band around each epipolar line" below. */
 typedef struct brisk_hip_pair_epipolar_model { /* 96 bytes, 8-byte aligned.  A type of its own ON PURPOSE: brisk_hip_refit_pair_models_device
                                                   and the guided matchers read a brisk_hip_pair_model as a homography and must not be
                                                   handed an F */
@@ -804,6 +805,51 @@ int brisk_hip_match_radius_pairs_guided_device(brisk_hip_ctx* ctx, const brisk_h
                                                const brisk_hip_pair_spec* pairs, const brisk_hip_pair_model* d_models,
                                                const brisk_hip_match_guide* guide, int dim_bytes, float max_distance, int cap_per_query,
                                                int rows_cap, brisk_hip_dmatch* d_out, int* d_out_count, int* d_pair_rows, void* stream);
+
+/* ---- a batch's pairs matched again inside a band around each epipolar line -----------------------------------------------------
+ * The second pass of the epipolar branch (select -> brisk_hip_verify_pair_matches_epipolar_device -> these calls -> select -> link),
+ * for scenes with depth: left against right, or a moving camera.  Every query keypoint is matched again, only against the train
+ * keypoints that lie within `band` pixels of its epipolar line F_p (x, y, 1), inside an optional window around the query keypoint's
+ * own position (the disparity range, or the tracking window along the line), and that satisfy the gate's octave rule.  The calls
+ * read the epipolar verifier's d_models in place, and their output goes through the selection, either verifier, the linker and both
+ * exits like any pair matcher's.  csrc/brisk_match_epiline.h is the one definition of the rule; all of its decision arithmetic is
+ * IEEE fp64 + - x and compares in a fixed order - no division, no square root -, so host and device agree bit for bit.
+ * d_models: a DEVICE array [npairs] of brisk_hip_pair_epipolar_model, 8-byte aligned, indexed by PAIR p.  Only f[0..8], hypothesis
+ * and flags of a record are read; the records may be the epipolar verifier's, an earlier batch's, or the caller's own.  The type is
+ * the epipolar model's on purpose: a homography record does not compile in.
+ * GUIDED: pair p iff d_models[p].hypothesis >= 0 and (flags & (BRISK_HIP_PAIR_BAD | BRISK_HIP_PAIR_NO_MODEL)) == 0.
+ * THE LINE of query row q, keypoint (x, y, octave), in a guided pair: x and y converted to double, then step (d) of the verifier:
+ *   l0 = (f0 x + f1 y) + f2   l1 = (f3 x + f4 y) + f5   l2 = (f6 x + f7 y) + f8   n = l0 l0 + l1 l1   w = (double(band) double(band)) n
+ * The row HAS A LINE iff band > 0 (fp32; a NaN, zero or negative band gives none), n > 0, and n and l2 are finite.  w may be +inf:
+ * a band of +INFINITY switches the band off.  A query at an epipole of a rank-2 F, a NaN or infinite model element, a NaN
+ * coordinate, an overflow of n and the zero model give no line.
+ * THE BAND for a train keypoint (x', y'), converted to double: r = (x' l0 + y' l1) + l2 passes iff r r <= w (closed; a NaN fails).
+ * THE MASK in a guided pair: M[q][t] = has_line(q) and band(q, t) and the gate of `window` between Q and T - centred on the query
+ * keypoint itself, not on a projection.  In an unguided pair with fallback != 0 the band is off and the mask is the plain gate's;
+ * with fallback == 0 no row matches anything.
+ * Rectified stereo, F = s [0 0 0; 0 0 -1; 0 1 0], gives the gated matcher's mask with dy in [-band, band].  With band == the
+ * verifier's max_error every allowed (q, t) of finite coordinates is a Sampson inlier of that F under the verifier's rule (n <= g). */
+typedef struct brisk_hip_match_epipolar_guide {
+  brisk_hip_match_gate window; /* bounds on T - Q; max_octave_diff between Q and T as in the gate.  All-pass: the band alone */
+  float band;                  /* pixels on either side of the epipolar line */
+  int fallback;                /* a pair without a usable model: 0 = its rows match nothing, else the plain gated matcher of `window` */
+} brisk_hip_match_epipolar_guide;
+/* Everything not named here is exactly as in the guided call of the same kind above, with the mask M of this section: both pair
+ * forms, d_pair_rows, rows_cap, memory that is never written, k-NN rows holding min(k, allowed) real entries and never topped up
+ * (k = 1, 2), radius counts = matches found, the four descriptor sizes, no cross check, asynchronous on `stream`, no workspace.
+ * BRISK_HIP_ERR_ARG before anything is launched: the guided calls' list - with npairs > 0 a NULL or misaligned d_models, a NULL
+ * guide, the gated calls' keypoint-set errors.  npairs == 0 is BRISK_HIP_OK. */
+int brisk_hip_match_knn_pairs_epipolar_guided_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                                     const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                                     const brisk_hip_pair_spec* pairs, const brisk_hip_pair_epipolar_model* d_models,
+                                                     const brisk_hip_match_epipolar_guide* guide, int dim_bytes, int k, int rows_cap,
+                                                     brisk_hip_dmatch* d_out, int* d_out_count, int* d_pair_rows, void* stream);
+int brisk_hip_match_radius_pairs_epipolar_guided_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                                        const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                                        const brisk_hip_pair_spec* pairs, const brisk_hip_pair_epipolar_model* d_models,
+                                                        const brisk_hip_match_epipolar_guide* guide, int dim_bytes, float max_distance,
+                                                        int cap_per_query, int rows_cap, brisk_hip_dmatch* d_out, int* d_out_count,
+                                                        int* d_pair_rows, void* stream);
 
 /* ---- a batch's pair matches linked into feature tracks, on the device ----------------------------------------------------------
  * What every consumer of a frame-to-previous-frame matcher does next: "row q of frame i matched row t of frame i - 1" becomes

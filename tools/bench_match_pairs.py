@@ -68,6 +68,18 @@ frames are unrelated, so no pair there has a model (as with --guided): the call'
 (as many pairs, 1 024 points a frame seen through mild homographies with 0.5 px noise, --related-records 200 records a pair, three
 quarters of them true), whose result is compared with the restated rule.  --refit --stats-pass runs the related batch only, so
 that a `rocprofv3 --kernel-trace --stats` pass around it gives k_refit_models on pairs that have models.
+With --epiguided (k-NN only, profiles/epiguided_pairs.json) the second pass of the epipolar branch, two windows:
+  E  --epipolar's E
+  L  E followed by brisk_hip_match_knn_pairs_epipolar_guided_device (k = 1, band = --max-error, window +-64 px, octave difference 1,
+     fallback 0) reading the verifier's models in place, select (keep 1) and link on the new lists
+plus L / E beside the spread of both windows, the HIP-event time of the call, the records per pair that reach the linker and the links
+made in E and in L, and whether every record of L is a Sampson inlier of its pair's model inside the window.  The stream's frames are
+unrelated, yet the epipolar verifier accepts models at --min-inliers 8, so L does scan.  --epiguided --stats-pass [--epi-case window |
+band] is for a `rocprofv3 --kernel-trace --stats` pass of its own per case: k_epiline_knn_pairs<12> with the band off under a +-6 px
+window beside k_match_knn_pairs_gated<12, false> at the same window and shapes (the same rows pass: the difference is the band's
+arithmetic), and with band 3 under an all-pass window beside the ungated k_match_knn_pairs<12, false> (whether skipping rows pays for the
+fp64 test): profiles/epiguided_pairs_kernel_stats.csv.
+
 With --guided (k-NN only, profiles/guided_pairs.json) what matching again under the pairs' models adds, two windows:
   V  --verify's window V: detect + describe + match + select + verify + link + list
   G  V followed by brisk_hip_match_knn_pairs_guided_device (k = 1, window +-6 px, octave difference 1, fallback 0) reading the verifier's
@@ -862,6 +874,192 @@ def guided_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
     ctx.close()
 
 
+def epiguided_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
+    """--epiguided: windows E and L (see the module's text); writes a.out"""
+    from test_abi_epipolar import restated_inliers8
+    st = work.cuda_stream
+    select = B.MatchSelect(float("inf"), 0.8, 1)
+    reselect = B.MatchSelect(float("inf"), 0.0, 1)                  # the second pass' lists: the distance bound only, one entry per row
+    verify = B.PairVerify(a.max_error, a.hypotheses, a.min_inliers, 1, 2024)
+    window_px, octaves = 64.0, 1
+    guide = B.MatchEpipolarGuide.around(a.max_error, window=(-window_px, window_px, -window_px, window_px), max_octave_diff=octaves, fallback=0)
+    spec = B.PairSpec(n - 1, 1, 1, 0, 1, None)
+    L, h = ctx._L, ctx._h
+    mcap = (n - 1) * cap                                            # (one match per row at the most)
+
+    def lists_of():
+        return (torch.zeros((mcap, 4), dtype=torch.int32, device=dev), torch.zeros(n - 1, dtype=torch.int32, device=dev),
+                torch.zeros(n - 1, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int64, device=dev))
+
+    def link_of():
+        return (torch.zeros((n, cap), dtype=torch.int32, device=dev), torch.zeros((n, cap), dtype=torch.int64, device=dev),
+                torch.zeros((n, cap), dtype=torch.int32, device=dev), torch.zeros(8, dtype=torch.int64, device=dev))
+
+    sel, ver, lsel = lists_of(), lists_of(), lists_of()
+    models = torch.zeros((n - 1, 12), dtype=torch.int64, device=dev)
+    link_e, link_l = link_of(), link_of()
+    tcap, ocap = n * cap // 4, n * cap
+    lists = (torch.zeros(tcap, dtype=torch.int64, device=dev), torch.zeros(tcap, dtype=torch.int32, device=dev),
+             torch.zeros(tcap + 1, dtype=torch.int64, device=dev), torch.zeros((ocap, 2), dtype=torch.int32, device=dev),
+             torch.zeros(4, dtype=torch.int64, device=dev))
+    seeds = {id(lk): B.TrackSeed(None, None, 0, lk[3].data_ptr()) for lk in (link_e, link_l)}   # numbered on from the call before
+    again = (torch.zeros((n - 1, cap, 1, 4), dtype=torch.int32, device=dev), torch.zeros((n - 1, cap), dtype=torch.int32, device=dev),
+             torch.zeros(n - 1, dtype=torch.int32, device=dev))
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    m, cnt, rows = outs["B"]
+
+    def link(dset, src, lk):
+        ptr, stride = ctx._node_rows((dset, 0, 1))
+        ctx.check(L.brisk_hip_link_tracks_device(h, ptr, stride, n, cap, src[3].data_ptr(), src[0].data_ptr(), C.byref(seeds[id(lk)]),
+                                                 lk[0].data_ptr(), lk[1].data_ptr(), lk[2].data_ptr(), lk[3].data_ptr(), st))
+        return ptr, stride
+
+    def run_e():
+        run_b0()
+        ctx.check(L.brisk_hip_select_pair_matches_device(h, m.data_ptr(), cnt.data_ptr(), rows.data_ptr(), n - 1, cap, k, C.byref(select), mcap,
+                                                         sel[1].data_ptr(), sel[2].data_ptr(), sel[3].data_ptr(), sel[0].data_ptr(), st))
+        dset, dim = ctx.batch_desc_set()
+        kps = ctx.batch_kp_set()
+        ctx.check(L.brisk_hip_verify_pair_matches_epipolar_device(h, C.byref(dset), C.byref(dset), C.byref(kps), C.byref(kps), C.byref(spec), cap,
+                                                                  sel[3].data_ptr(), sel[0].data_ptr(), mcap, C.byref(verify), mcap,
+                                                                  models.data_ptr(), ver[1].data_ptr(), ver[2].data_ptr(), ver[3].data_ptr(),
+                                                                  ver[0].data_ptr(), st))
+        ptr, stride = link(dset, ver, link_e)
+        ctx.check(L.brisk_hip_list_tracks_device(h, ptr, stride, n, cap, link_e[0].data_ptr(), link_e[1].data_ptr(), link_e[2].data_ptr(), 3,
+                                                 tcap, ocap, lists[0].data_ptr(), lists[1].data_ptr(), lists[2].data_ptr(), lists[3].data_ptr(),
+                                                 lists[4].data_ptr(), st))
+        return dset, dim, kps
+
+    def run_l(timed=False):
+        dset, dim, kps = run_e()
+        if timed:
+            ev[0].record(work)
+        ctx.check(L.brisk_hip_match_knn_pairs_epipolar_guided_device(h, C.byref(dset), C.byref(dset), C.byref(kps), C.byref(kps), C.byref(spec),
+                                                                     models.data_ptr(), C.byref(guide), dim, 1, cap, again[0].data_ptr(),
+                                                                     again[1].data_ptr(), again[2].data_ptr(), st))
+        if timed:
+            ev[1].record(work)
+        ctx.check(L.brisk_hip_select_pair_matches_device(h, again[0].data_ptr(), again[1].data_ptr(), again[2].data_ptr(), n - 1, cap, 1,
+                                                         C.byref(reselect), mcap, lsel[1].data_ptr(), lsel[2].data_ptr(), lsel[3].data_ptr(),
+                                                         lsel[0].data_ptr(), st))
+        link(dset, lsel, link_l)
+
+    rectified = np.zeros(n - 1, B.PAIR_EPIPOLAR_MODEL)
+    rectified["f"] = (0.0, 0.0, 0.0, 0.0, 0.0, -1.0, 0.0, 1.0, 0.0)
+    rectified = torch.from_numpy(rectified.view(np.int64).reshape(n - 1, 12).copy()).to(dev)
+
+    def run_yardstick():
+        """the kernel trace's pairs, EVERY pair guided by the rectified model (every row has a line).  --epi-case window: the band off
+        (+inf) under a +-6 px window, beside the gated k-NN call at the same window, k and shapes - the same rows pass, the difference
+        is the band's arithmetic.  --epi-case band: band 3 under an all-pass window, beside the UNGATED k-NN call - whether skipping
+        rows pays for the fp64 test."""
+        dset, dim = ctx.batch_desc_set()
+        kps = ctx.batch_kp_set()
+        if a.epi_case == "window":
+            g = B.MatchEpipolarGuide.around(float("inf"), window=(-6.0, 6.0, -6.0, 6.0), max_octave_diff=1, fallback=0)
+            ctx.match_knn_pairs_epipolar_guided(dset, dset, spec, 1, rectified, g, rows_cap=cap, query_kps=kps, train_kps=kps, stream=st,
+                                                dim_bytes=dim, out=again)
+            ctx.match_knn_pairs(dset, dset, spec, 1, rows_cap=cap, stream=st, dim_bytes=dim, out=again, gate=g.window, query_kps=kps,
+                                train_kps=kps)
+        else:
+            g = B.MatchEpipolarGuide.around(3.0, fallback=0)
+            ctx.match_knn_pairs_epipolar_guided(dset, dset, spec, 1, rectified, g, rows_cap=cap, query_kps=kps, train_kps=kps, stream=st,
+                                                dim_bytes=dim, out=again)
+            ctx.match_knn_pairs(dset, dset, spec, 1, rows_cap=cap, stream=st, dim_bytes=dim, out=again)
+
+    runs = {"E": run_e, "L": run_l}
+    order = "EL"
+    if a.stats_pass:                                                # (no L: every launch of the new kernel in the trace is the yardstick's)
+        for _ in range(2 + 8):
+            run_e()
+            run_yardstick()
+            torch.cuda.synchronize()
+        return
+    for v in order + "EL":                                          # warm-up: buffers sized, scratch grown
+        runs[v]()
+        torch.cuda.synchronize()
+
+    # one batch: what reaches the linker and what it makes of it, in E and in L; band == max_error: every record of L is a Sampson
+    # inlier of its pair's model by the verifier's restated score
+    run_l()
+    torch.cuda.synchronize()
+    dset, dim = ctx.batch_desc_set()
+    mod = models.cpu().numpy().reshape(-1).view(B.PAIR_EPIPOLAR_MODEL)
+    has_model = (mod["hypothesis"] >= 0) & ((mod["flags"] & (B.PAIR_NO_MODEL | B.PAIR_BAD)) == 0)
+    ecounts, lcounts = ver[1].cpu().numpy(), lsel[1].cpu().numpy()
+    sum_e, sum_l = link_e[3].cpu().numpy(), link_l[3].cpu().numpy()
+    loffs, lrec = lsel[3].cpu().numpy(), lsel[0].cpu().numpy().view(B.DMATCH).reshape(-1)
+    kps = [ctx.batch_download(f, True, strings=dim)[0] for f in range(n)]
+    inliers = True
+    for p in range(n - 1):
+        rec = lrec[int(loffs[p]):int(loffs[p + 1])]
+        if not has_model[p]:
+            inliers = inliers and len(rec) == 0
+            continue
+        kq, kt = kps[p + 1][rec["queryIdx"]], kps[p][rec["trainIdx"]]
+        ok = restated_inliers8(mod["f"][p][None, :], float(np.float32(a.max_error)) ** 2, kq["x"].astype(np.float64), kq["y"].astype(np.float64),
+                               kt["x"].astype(np.float64), kt["y"].astype(np.float64))[0]
+        inliers = bool(inliers and ok.all() and (np.abs(kt["x"] - kq["x"]) <= window_px).all() and (np.abs(kt["y"] - kq["y"]) <= window_px).all()
+                       and (np.abs(kt["octave"] - kq["octave"]) <= octaves).all())
+
+    call_ms = []
+    for _ in range(max(a.repeats, 5)):
+        run_l(timed=True)
+        torch.cuda.synchronize()
+        call_ms.append(ev[0].elapsed_time(ev[1]))
+
+    fps = {v: [] for v in order}
+    for _ in range(a.repeats):
+        for v in order:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            calls = 0
+            while True:
+                runs[v]()
+                calls += 1
+                if time.perf_counter() - t0 >= a.window:
+                    break
+            torch.cuda.synchronize()
+            fps[v].append(calls * n / (time.perf_counter() - t0))
+    med = {v: float(np.median(fps[v])) for v in order}
+    ms = {v: 1e3 * n / med[v] for v in order}
+    spread = {v: (max(fps[v]) - min(fps[v])) / med[v] for v in order}
+    res = {
+        "workload": "bench.py's stream: %dx%d, threshold %d, %d octaves, %d frames per batch (%d distinct) in HBM; frame-to-previous-frame, "
+                    "k = %d, rows_cap %d, ratio 0.8, one match per row; epipolar verify: %d hypotheses, max_error %g, min_inliers %d, "
+                    "keep_unverified 1; second pass: k = 1, band %g px, window +-%g px, octave difference %d, fallback 0, then keep 1 without "
+                    "a ratio; tracks of min_len 3" % (W, H, THRESHOLD, OCTAVES, n, nd, k, cap, a.hypotheses, a.max_error, a.min_inliers,
+                                                      a.max_error, window_px, octaves),
+        "kernel_revision": ctx.kernel_revision(),
+        "device": torch.cuda.get_device_name(0),
+        "windows": {"repeats": a.repeats, "seconds_each": a.window, "order": ", ".join(order) + " alternating; every window ends in a synchronise"},
+        "frames_per_s": {v: round(med[v], 1) for v in order},
+        "frames_per_s_all": {v: [round(x, 1) for x in fps[v]] for v in order},
+        "spread_rel": {v: round(spread[v], 4) for v in order},
+        "ms_per_batch": {v: round(ms[v], 4) for v in order},
+        "second_pass_ms_per_batch": {"L_minus_E": round(ms["L"] - ms["E"], 4)},
+        "L_over_E_frames_per_s": round(med["L"] / med["E"], 4),
+        "hip_event_ms": {"epipolar_guided_call_1_launch": {"median": round(float(np.median(call_ms)), 4), "all": [round(x, 4) for x in call_ms]}},
+        "per_batch": {"pairs": n - 1, "pairs_with_a_model": int(has_model.sum()),
+                      "records_per_pair_to_the_linker": {"E": round(float(ecounts.mean()), 2), "L": round(float(lcounts.mean()), 2)},
+                      "links": {"E": int(sum_e[2]), "L": int(sum_l[2])},
+                      "proposals_lost": {"E": int(sum_e[3]), "L": int(sum_l[3])}},
+        "L_records_are_sampson_inliers_inside_their_windows": inliers,
+        "note": "the stream's consecutive frames are unrelated; the epipolar verifier still accepts models at min_inliers %d, so L does scan" %
+                a.min_inliers,
+        "legend": {"E": "detect_describe_batch + match_knn_pairs + select + brisk_hip_verify_pair_matches_epipolar_device + link + list on one "
+                        "stream",
+                   "L": "E + brisk_hip_match_knn_pairs_epipolar_guided_device on the verifier's models + select (keep 1) + link on the new lists"},
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+    ext.close()
+    ctx.close()
+
+
 def tracks_download_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
     """--tracks-download: windows T, D and P (see the module's text); writes a.out"""
     st = work.cuda_stream
@@ -1033,6 +1231,11 @@ def main():
                     help="windows T (--tracks' T) and E (T with verify_pair_matches_epipolar between select and link)")
     ap.add_argument("--guided", action="store_true",
                     help="windows V (--verify's V) and G (V + match_knn_pairs_guided on the verifier's models + select + link)")
+    ap.add_argument("--epiguided", action="store_true",
+                    help="windows E (--epipolar's E) and L (E + match_knn_pairs_epipolar_guided on the verifier's models + select + link)")
+    ap.add_argument("--epi-case", choices=("window", "band"), default="window",
+                    help="--epiguided --stats-pass: the new kernel with the band off under a +-6 px window beside the gated kernel, or with "
+                         "band 3 under an all-pass window beside the ungated kernel (one rocprofv3 run each: the stats merge a kernel's launches)")
     ap.add_argument("--refit", action="store_true",
                     help="windows V (--verify's V) and R (V with refit_pair_models between verify and link), and the call on a related batch")
     ap.add_argument("--rounds", type=int, default=2, help="--refit: rounds of fit and recount")
@@ -1078,6 +1281,12 @@ def main():
             ap.error("--guided measures the k-NN pair call: without --radius / --gate / --export / --tracks / --tracks-download / --verify")
         if a.out is None:
             a.out = os.path.join(ROOT, "profiles", "guided_pairs.json")
+    if a.epiguided:
+        if radius is not None or gate or a.export or a.tracks or a.tracks_download or a.verify or a.guided or a.refit or a.epipolar:
+            ap.error("--epiguided measures the k-NN pair call: without --radius / --gate / --export / --tracks / --tracks-download / --verify / "
+                     "--guided / --refit / --epipolar")
+        if a.out is None:
+            a.out = os.path.join(ROOT, "profiles", "epiguided_pairs.json")
     if a.refit:
         if radius is not None or gate or a.export or a.tracks or a.tracks_download or a.verify or a.guided:
             ap.error("--refit measures the k-NN pair call: without --radius / --gate / --export / --tracks / --tracks-download / --verify / --guided")
@@ -1148,6 +1357,9 @@ def main():
         return
     if a.refit:
         refit_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b)
+        return
+    if a.epiguided:
+        epiguided_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b)
         return
 
     vp = C.c_void_p
