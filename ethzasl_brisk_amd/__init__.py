@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "brisk_hip_verify_pair_matches_epipolar_device",
     "brisk_hip_match_knn_pairs_guided_device", "brisk_hip_match_radius_pairs_guided_device",
     "brisk_hip_match_knn_pairs_epipolar_guided_device", "brisk_hip_match_radius_pairs_epipolar_guided_device",
+    "brisk_hip_match_mutual_pairs_guided_device", "brisk_hip_match_mutual_pairs_epipolar_guided_device",
     "brisk_hip_link_tracks_device", "brisk_hip_list_tracks_device",
     "brisk_hip_track_points_device", "brisk_hip_tracks_download", "brisk_hip_tracks_wait",
 ]
@@ -394,6 +395,11 @@ def load_library():
     L.brisk_hip_match_radius_pairs_guided_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
                                                              C.POINTER(PairSpec), vp, C.POINTER(MatchGuide), C.c_int, C.c_float, C.c_int,
                                                              C.c_int, vp, vp, vp, vp]
+    L.brisk_hip_match_mutual_pairs_guided_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
+                                                             C.POINTER(PairSpec), vp, C.POINTER(MatchGuide), C.c_int, C.c_int, vp, vp, vp, vp]
+    L.brisk_hip_match_mutual_pairs_epipolar_guided_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
+                                                                      C.POINTER(PairSpec), vp, C.POINTER(MatchEpipolarGuide), C.c_int, C.c_int,
+                                                                      vp, vp, vp, vp]
     L.brisk_hip_link_tracks_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(TrackSeed), vp, vp, vp, vp, vp]
     L.brisk_hip_list_tracks_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_longlong, C.c_longlong,
                                                vp, vp, vp, vp, vp, vp]
@@ -791,7 +797,7 @@ class Context:
                                dim_bytes=None, out=None, download=False):
         """brisk_hip_match_knn_pairs_guided_device: match_knn_pairs behind the window of `guide` (a MatchGuide) centred where pair
         p's model models[p] puts each query keypoint.  models: the tensor verify_pair_matches returns ([npairs, 12] int64, PAIR_MODEL
-        records), or any device pointer to npairs records.  No cross check.  Everything else, and what is returned, as match_knn_pairs
+        records), or any device pointer to npairs records.  No cross_check argument (match_mutual_pairs_guided).  Everything else, and what is returned, as match_knn_pairs
         with a gate."""
         n = pairs.npairs
         dim_bytes, rows_cap, out = self._pairs_prologue(pairs, dim_bytes, rows_cap, k, out)
@@ -821,7 +827,8 @@ class Context:
         """brisk_hip_match_knn_pairs_epipolar_guided_device: match_knn_pairs behind `guide` (a MatchEpipolarGuide) - the band around each
         query keypoint's epipolar line under pair p's model models[p], inside the guide's window around the keypoint.  models: the
         tensor verify_pair_matches_epipolar returns ([npairs, 12] int64, PAIR_EPIPOLAR_MODEL records), or any device pointer to npairs
-        records.  No cross check.  Everything else, and what is returned, as match_knn_pairs with a gate."""
+        records.  No cross_check argument (match_mutual_pairs_epipolar_guided).  Everything else, and what is returned, as match_knn_pairs
+        with a gate."""
         n = pairs.npairs
         dim_bytes, rows_cap, out = self._pairs_prologue(pairs, dim_bytes, rows_cap, k, out)
         m, cnt, rows = out
@@ -844,6 +851,34 @@ class Context:
                                                                                m.data_ptr(), cnt.data_ptr(), rows.data_ptr(),
                                                                                C.c_void_p(stream) if stream else None))
         return self._radius_rows(out, n, rows_cap, cpq) if download else out
+
+    # -- the guided pair matchers' mutual forms: k = 1 with the cross check --
+    def match_mutual_pairs_guided(self, query, train, pairs, models, guide, rows_cap=None, query_kps=None, train_kps=None, stream=None,
+                                  dim_bytes=None, out=None, download=False):
+        """brisk_hip_match_mutual_pairs_guided_device: match_knn_pairs_guided for k = 1 with the cross check - row q keeps its record
+        iff, under the same mask asked from the train side, its train row's best match among ALL rows of the query frame is q.
+        Arguments, and what is returned, as match_knn_pairs_guided with k = 1."""
+        n = pairs.npairs
+        dim_bytes, rows_cap, out = self._pairs_prologue(pairs, dim_bytes, rows_cap, 1, out)
+        m, cnt, rows = out
+        qk, tk, mp, gp = self._guide_args(models, guide, query_kps, train_kps)
+        self.check(self._L.brisk_hip_match_mutual_pairs_guided_device(self._h, C.byref(query), C.byref(train), qk, tk, C.byref(pairs), mp, gp,
+                                                                      int(dim_bytes), int(rows_cap), m.data_ptr(), cnt.data_ptr(),
+                                                                      rows.data_ptr(), C.c_void_p(stream) if stream else None))
+        return self._knn_rows(out, n, rows_cap, 1) if download else out
+
+    def match_mutual_pairs_epipolar_guided(self, query, train, pairs, models, guide, rows_cap=None, query_kps=None, train_kps=None, stream=None,
+                                           dim_bytes=None, out=None, download=False):
+        """brisk_hip_match_mutual_pairs_epipolar_guided_device: match_knn_pairs_epipolar_guided for k = 1 with the cross check; the
+        conventions of match_mutual_pairs_guided."""
+        n = pairs.npairs
+        dim_bytes, rows_cap, out = self._pairs_prologue(pairs, dim_bytes, rows_cap, 1, out)
+        m, cnt, rows = out
+        qk, tk, mp, gp = self._guide_args(models, guide, query_kps, train_kps)
+        self.check(self._L.brisk_hip_match_mutual_pairs_epipolar_guided_device(self._h, C.byref(query), C.byref(train), qk, tk, C.byref(pairs), mp,
+                                                                               gp, int(dim_bytes), int(rows_cap), m.data_ptr(), cnt.data_ptr(),
+                                                                               rows.data_ptr(), C.c_void_p(stream) if stream else None))
+        return self._knn_rows(out, n, rows_cap, 1) if download else out
 
     # -- the pair matchers' exit: selected matches, packed --
     def select_pair_matches(self, out_triple, per_row, select, matches_cap=None, stream=None):

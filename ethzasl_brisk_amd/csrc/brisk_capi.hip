@@ -2031,6 +2031,14 @@ static int match_knn_pairs_call(const PairCall& C, int k, int cross_check, int r
                [&](const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, const BriskKpSet& QK, const BriskKpSet& TK,
                    const BriskMatchGate& G, BriskDMatch* out, hipStream_t st) {
                  const bool cross = cross_check != 0;
+                 if (C.line && cross)
+                   return brisk_launch_match_mutual_pairs_epiline(Q, T, QK, TK, reinterpret_cast<const BriskPairEpipolarModel*>(C.models),
+                                                                  BriskMatchEpiGuide{G, C.line->band, C.line->fallback}, P, C.dim_bytes / 4, rows_cap,
+                                                                  out, d_out_count, d_pair_rows, st);
+                 if (C.guided && cross)
+                   return brisk_launch_match_mutual_pairs_guided(Q, T, QK, TK, reinterpret_cast<const BriskPairModel*>(C.models),
+                                                                 BriskMatchGuide{G, C.guide->fallback}, P, C.dim_bytes / 4, rows_cap, out, d_out_count,
+                                                                 d_pair_rows, st);
                  if (C.line)
                    return brisk_launch_match_knn_pairs_epiline(Q, T, QK, TK, reinterpret_cast<const BriskPairEpipolarModel*>(C.models),
                                                                BriskMatchEpiGuide{G, C.line->band, C.line->fallback}, P, C.dim_bytes / 4, k, rows_cap,
@@ -2153,6 +2161,28 @@ int brisk_hip_match_radius_pairs_epipolar_guided_device(brisk_hip_ctx* ctx, cons
   return match_radius_pairs_call({ctx, "match_radius_pairs", query, train, pairs, dim_bytes, true, query_kps, train_kps, nullptr, true, d_models, nullptr,
                                   guide},
                                  max_distance, cap_per_query, rows_cap, d_out, d_out_count, d_pair_rows, stream);
+}
+// the mutual guided forms: the two guided k-NN calls for k = 1 with the cross check fused - the guide's mask asked from the train side
+// (brisk_guide_train_row / brisk_epiguide_train_row).  The guided calls' checks in the guided calls' order
+int brisk_hip_match_mutual_pairs_guided_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                               const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                               const brisk_hip_pair_spec* pairs, const brisk_hip_pair_model* d_models,
+                                               const brisk_hip_match_guide* guide, int dim_bytes, int rows_cap, brisk_hip_dmatch* d_out,
+                                               int* d_out_count, int* d_pair_rows, void* stream) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  return match_knn_pairs_call({ctx, "match_pairs", query, train, pairs, dim_bytes, true, query_kps, train_kps, nullptr, true, d_models, guide}, 1, 1,
+                              rows_cap, d_out, d_out_count, d_pair_rows, stream);
+}
+int brisk_hip_match_mutual_pairs_epipolar_guided_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                                        const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                                        const brisk_hip_pair_spec* pairs, const brisk_hip_pair_epipolar_model* d_models,
+                                                        const brisk_hip_match_epipolar_guide* guide, int dim_bytes, int rows_cap,
+                                                        brisk_hip_dmatch* d_out, int* d_out_count, int* d_pair_rows, void* stream) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  return match_knn_pairs_call({ctx, "match_pairs", query, train, pairs, dim_bytes, true, query_kps, train_kps, nullptr, true, d_models, nullptr, guide}, 1,
+                              1, rows_cap, d_out, d_out_count, d_pair_rows, stream);
 }
 
 // ---- the pair matchers' exit: selected matches, packed (kernels: brisk_match_export.hip) -----------------------------------------

@@ -214,6 +214,15 @@ bool brisk_launch_match_radius_pairs_epiline(const BriskDescSet& Q, const BriskD
                                              int words32, float max_distance, int cap, int rows_cap, BriskDMatch* out, int* out_count,
                                              int* pair_rows, hipStream_t s);
 
+// the two guided k-NN forms for k = 1 WITH the cross check: a row's match is kept iff the guide's mask, asked from the train side over
+// ALL rows of the query frame, gives the row back (brisk_guide_train_row / brisk_epiguide_train_row).  out: [npairs][rows_cap][1]
+bool brisk_launch_match_mutual_pairs_guided(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
+                                            const BriskPairModel* models, const BriskMatchGuide& guide, const BriskPairSpec& P, int words32,
+                                            int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s);
+bool brisk_launch_match_mutual_pairs_epiline(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
+                                             const BriskPairEpipolarModel* models, const BriskMatchEpiGuide& guide, const BriskPairSpec& P,
+                                             int words32, int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s);
+
 // ---- the pair matchers' exit: selected matches, packed (brisk_match_export.hip; the rule: brisk_match_select.h) ----
 // flags of a pair (mirror BRISK_HIP_PAIR_* / BRISK_HIP_ROWS_CUT of brisk_hip.h)
 enum { BRISK_PAIR_ROWS_CUT = 1, BRISK_PAIR_BAD = 2, BRISK_PAIR_ENTRIES_CUT = 4, BRISK_PAIR_NO_MODEL = 8, BRISK_PAIR_REFIT = 0x10, BRISK_PAIR_MATCHES_CUT = 0x100 };

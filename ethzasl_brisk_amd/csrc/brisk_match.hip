@@ -29,6 +29,10 @@
 //                               the gated kernels (no cross check) behind the band around the lane's epipolar line under the
 //                               pair's model (brisk_match_epiline.h): the line is made per lane in front of the same scan, the
 //                               band is three fp64 multiplies per passing row beside the gate's compares
+//   k_mutual_centre_knn, k_mutual_line_knn
+//                               the two guided k-NN kernels for k = 1 WITH the cross check: the backward scan asks the guide's mask from
+//                               the train side, the centres / lines of the query rows passing by made 64 at a time, one per lane, and
+//                               handed round by v_readlane (mpm_scan)
 //   k_match_radius_pairs[_gated], k_match_radius_pairs_one
 //                               radius matching in the same shape (mrp_body): hits collected in a short LDS list per
 //                               query and ranked; a query with more hits than the list holds is redone by one wave
@@ -488,6 +492,77 @@ __device__ __forceinline__ void mp_scan_slice(const unsigned (&v)[W32], const ui
   }
 }
 
+// The backward scan of the mutual guided forms (k_mutual_centre_knn, k_mutual_line_knn).  The lane holds train row f(q) and its
+// keypoint's lane TL; the rows passing by are QUERY rows, and the guide's mask needs what the model makes of each of them: its centre,
+// or its line.  The wave makes them 64 at a time - lane i stages row base + i with the forward scan's own brisk_guide_centre /
+// brisk_epiguide_lane, one fp64 prologue per 64 scanned rows - and the row loop reads record j out of lane j's registers with
+// v_readlane (j is the loop's scalar counter).  A readlane writes SGPRs: the predicate's compares take the centre as scalar operands,
+// exactly as mpg_scan's take the keypoint its scalar loads brought, and nothing of the staging goes through LDS - an LDS table would
+// return to VGPRs and count on lgkmcnt beside the descriptor rows' scalar loads, whose out-of-order return forces every wait to 0.
+// has-centre / has-line is one ballot per block, kept as a lane mask.  mpg_scan's chunks, ballots before the first branch and the
+// live == 0 skip are kept: a query row that no lane may match costs its readlanes and compares only.
+__device__ __forceinline__ float mpm_readlane(float v, int j) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j)); }
+__device__ __forceinline__ double mpm_readlane(double v, int j) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), j), __builtin_amdgcn_readlane(__double2loint(v), j));
+}
+// rows [t0, t1) of frame a (wave-uniform) against the lane's train row tv: the smallest key (distance, q') among the rows whose mask
+// allows the lane's train keypoint.  kps: frame a's keypoints; M, guided, fallback, band: as the forward scan's mpu_lane / mpe_lane
+template <int W32, bool ALIGNED, int GUIDE>
+__device__ __forceinline__ void mpm_scan(const unsigned (&tv)[W32], const uint8_t* rows, int pitch, int t0, int t1, const BriskMatchGate& g,
+                                         const BriskGateLane& TL, bool on, const char* kps, const MpModelOf<GUIDE>* __restrict__ M, bool guided,
+                                         int fallback, float band, int lane, unsigned& best) {
+  for (int base = t0; base < t1; base += 64) {
+    const int nblk = min(64, t1 - base);  // (wave-uniform)
+    const BriskKeyPoint* kp = mp_kp(kps, base + min(lane, nblk - 1));
+    float sx, sy;  // the centre, or the keypoint itself (the line form's window stays there)
+    const int so = kp->octave;
+    BriskEpiLine sl = {};
+    bool shas;
+    if constexpr (GUIDE == MP_GUIDE_LINE) {
+      BriskEpiLane L;
+      shas = mpe_lane(M, guided, g, band, fallback, kp, L);
+      sx = kp->x;
+      sy = kp->y;
+      sl = L.line;
+    } else {
+      const BriskHomography H{M->h[0], M->h[1], M->h[2], M->h[3], M->h[4], M->h[5], M->h[6], M->h[7], M->h[8]};
+      const BriskGuideCentre c = brisk_guide_centre(guided, fallback, H, kp->x, kp->y);
+      sx = c.x;
+      sy = c.y;
+      shas = c.has;
+    }
+    const unsigned long long has = __ballot(shas);
+    for (int jc = 0; jc < nblk; jc += MPG_CHUNK) {
+      bool ok[MPG_CHUNK];
+      unsigned long long live[MPG_CHUNK];
+#pragma unroll
+      for (int i = 0; i < MPG_CHUNK; ++i) {
+        const int j = min(jc + i, nblk - 1);
+        const bool hj = (has >> j) & 1;
+        const float x = mpm_readlane(sx, j), y = mpm_readlane(sy, j);
+        const int o = __builtin_amdgcn_readlane(so, j);
+        bool pass;
+        if constexpr (GUIDE == MP_GUIDE_LINE) {
+          BriskEpiLine E = {};
+          if (guided) E = BriskEpiLine{mpm_readlane(sl.l0, j), mpm_readlane(sl.l1, j), mpm_readlane(sl.l2, j), mpm_readlane(sl.w, j)};
+          pass = brisk_epiguide_train_row(g, guided, TL, hj, E, x, y, o);
+        } else {
+          pass = brisk_guide_train_row(g, TL, hj, x, y, o);
+        }
+        ok[i] = on && jc + i < nblk && pass;
+        live[i] = __ballot(ok[i]);
+      }
+#pragma unroll
+      for (int i = 0; i < MPG_CHUNK; ++i) {
+        if (live[i] == 0) continue;  // wave-uniform
+        const int t = base + jc + i;
+        const unsigned d = m_dist<W32, ALIGNED>(tv, rows + (long)t * pitch);
+        best = min(best, ok[i] ? m_key(d, t) : MF_NO_KEY);
+      }
+    }
+  }
+}
+
 // k-NN of a pair: k_match_knn_fused's scheme with MP_WAVES waves.
 // CROSS (k == 1): the forward match t of row q is kept only if the best match of row t of frame b among ALL rows of frame a is q.
 // Fused: once the forward keys are merged, lane q takes row t of frame b into its registers and the waves scan frame a the same
@@ -495,9 +570,11 @@ __device__ __forceinline__ void mp_scan_slice(const unsigned (&v)[W32], const ui
 // between workgroups.
 // GATE: a lane the gate forbids keeps MF_NO_KEY, so a row holds min(k, allowed rows) REAL matches and is never topped up; in the
 // cross check a lane without a forward match takes no part.
-// GUIDE (with GATE, without CROSS): `gate` is the guide's window, centred by models[p] (mpu_lane); a lane whose row has no centre
+// GUIDE (with GATE): `gate` is the guide's window, centred by models[p] (mpu_lane); a lane whose row has no centre
 // takes no part, and a pair without a usable model and without the fallback has empty rows.  GUIDE == MP_GUIDE_LINE: the window stays
 // at the lane's own keypoint, and the lane carries its epipolar line under models[p] and `band` (mpe_lane).
+// GUIDE with CROSS (the mutual forms, k == 1): the backward scan asks the SAME mask from the train side - row q' of frame a may claim the
+// lane's train row iff the guide allows (q', t) - through mpm_scan, which makes the centres / lines of the rows passing by on the way.
 template <int W32, bool CROSS, bool GATE, int GUIDE = MP_GUIDE_NONE>
 __device__ __forceinline__ void mp_body(const BriskDescSet& Q, const BriskDescSet& T, const BriskPairSpec& P, int pair0, int k, int rows_cap,
                                         BriskDMatch* __restrict__ out, int* __restrict__ out_count, int* __restrict__ pair_rows,
@@ -555,7 +632,16 @@ __device__ __forceinline__ void mp_body(const BriskDescSet& Q, const BriskDescSe
     mp_load_row<W32>(trows + (long)t * T.row_pitch, R.t_aligned, tv);
     unsigned c1 = MF_NO_KEY, c2 = MF_NO_KEY;
     // ALL rows q' of frame a, also those beyond rows_cap
-    mp_scan_slice<W32, GATE, true>(tv, qrows, Q.row_pitch, R.q_aligned, R.n_a, wave, gate, GATE ? mp_kp(tk, t) : nullptr, has, qk, c1, c2);
+    if constexpr (GUIDE != MP_GUIDE_NONE) {  // the guide's mask from the train side: mpm_scan
+      const BriskKeyPoint* tkp = mp_kp(tk, t);
+      const BriskGateLane TL = brisk_gate_lane(gate, tkp->x, tkp->y, tkp->octave);
+      const int per = (R.n_a + MP_WAVES - 1) / MP_WAVES;
+      const int t0 = __builtin_amdgcn_readfirstlane(wave * per), t1 = min(R.n_a, t0 + per);
+      if (R.q_aligned) mpm_scan<W32, true, GUIDE>(tv, qrows, Q.row_pitch, t0, t1, gate, TL, has, qk, models + p, guided, fallback, band, lane, c1);
+      else mpm_scan<W32, false, GUIDE>(tv, qrows, Q.row_pitch, t0, t1, gate, TL, has, qk, models + p, guided, fallback, band, lane, c1);
+    } else {
+      mp_scan_slice<W32, GATE, true>(tv, qrows, Q.row_pitch, R.q_aligned, R.n_a, wave, gate, GATE ? mp_kp(tk, t) : nullptr, has, qk, c1, c2);
+    }
     part[wave][0][lane] = c1;
     __syncthreads();
     if (wave == 0) {
@@ -617,6 +703,24 @@ __global__ void __launch_bounds__(MP_WAVES * 64) k_epiline_knn_pairs(const Brisk
                                                                       int* __restrict__ pair_rows) {
   mp_body<W32, false, true, MP_GUIDE_LINE>(Q, T, P, pair0, k, rows_cap, out, out_count, pair_rows, QK, TK, guide.window, models, guide.fallback,
                                            guide.band);
+}
+// the mutual guided forms: the guided / epipolar-guided k-NN kernel for k = 1 with the cross check fused (mp_body's CROSS with a guide)
+template <int W32>
+__global__ void __launch_bounds__(MP_WAVES * 64) k_mutual_centre_knn(const BriskDescSet Q, const BriskDescSet T, const BriskKpSet QK,
+                                                                      const BriskKpSet TK, const BriskPairModel* __restrict__ models,
+                                                                      const BriskMatchGuide guide, const BriskPairSpec P, int pair0, int rows_cap,
+                                                                      BriskDMatch* __restrict__ out, int* __restrict__ out_count,
+                                                                      int* __restrict__ pair_rows) {
+  mp_body<W32, true, true, MP_GUIDE_CENTRE>(Q, T, P, pair0, 1, rows_cap, out, out_count, pair_rows, QK, TK, guide.window, models, guide.fallback);
+}
+template <int W32>
+__global__ void __launch_bounds__(MP_WAVES * 64) k_mutual_line_knn(const BriskDescSet Q, const BriskDescSet T, const BriskKpSet QK,
+                                                                    const BriskKpSet TK, const BriskPairEpipolarModel* __restrict__ models,
+                                                                    const BriskMatchEpiGuide guide, const BriskPairSpec P, int pair0, int rows_cap,
+                                                                    BriskDMatch* __restrict__ out, int* __restrict__ out_count,
+                                                                    int* __restrict__ pair_rows) {
+  mp_body<W32, true, true, MP_GUIDE_LINE>(Q, T, P, pair0, 1, rows_cap, out, out_count, pair_rows, QK, TK, guide.window, models, guide.fallback,
+                                          guide.band);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1027,6 +1131,26 @@ bool brisk_launch_match_radius_pairs_epiline(const BriskDescSet& Q, const BriskD
     mp_launch_pairs(P.npairs, rows_cap, [&](dim3 grid, int p0) {
       hipLaunchKernelGGL(k_epiline_radius_pairs<decltype(W)::value>, grid, dim3(MP_WAVES * 64), 0, s, Q, T, QK, TK, models, guide, P, p0, max_distance,
                          cap, rows_cap, out, out_count, pair_rows);
+    });
+  });
+}
+bool brisk_launch_match_mutual_pairs_guided(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
+                                            const BriskPairModel* models, const BriskMatchGuide& guide, const BriskPairSpec& P, int words32,
+                                            int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s) {
+  return m_dispatch_words(words32, [&](auto W) {
+    mp_launch_pairs(P.npairs, rows_cap, [&](dim3 grid, int p0) {
+      hipLaunchKernelGGL(k_mutual_centre_knn<decltype(W)::value>, grid, dim3(MP_WAVES * 64), 0, s, Q, T, QK, TK, models, guide, P, p0, rows_cap, out,
+                         out_count, pair_rows);
+    });
+  });
+}
+bool brisk_launch_match_mutual_pairs_epiline(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
+                                             const BriskPairEpipolarModel* models, const BriskMatchEpiGuide& guide, const BriskPairSpec& P,
+                                             int words32, int rows_cap, BriskDMatch* out, int* out_count, int* pair_rows, hipStream_t s) {
+  return m_dispatch_words(words32, [&](auto W) {
+    mp_launch_pairs(P.npairs, rows_cap, [&](dim3 grid, int p0) {
+      hipLaunchKernelGGL(k_mutual_line_knn<decltype(W)::value>, grid, dim3(MP_WAVES * 64), 0, s, Q, T, QK, TK, models, guide, P, p0, rows_cap, out,
+                         out_count, pair_rows);
     });
   });
 }

@@ -79,6 +79,13 @@ BRISK_GATE_HD bool brisk_epiguide_query_lane(const BriskMatchGate& window, bool 
                                              float ty, int toct) {
   return (!guided || brisk_epiguide_band(E, tx, ty)) && brisk_gate_query_lane(window, q, tx, ty, toct);
 }
+// the lane holds the TRAIN keypoint (the mutual form's backward scan: t = brisk_gate_lane(window, T.x, T.y, T.octave)); the query row
+// passing by comes as what brisk_epiguide_lane made of it - `has` and the line E - with its own keypoint.  The SAME predicate as
+// brisk_epiguide_query_lane behind has, read from the other side: the band is still the train point against the QUERY's line
+BRISK_GATE_HD bool brisk_epiguide_train_row(const BriskMatchGate& window, bool guided, const BriskGateLane& t, bool has, const BriskEpiLine& E,
+                                            float qx, float qy, int qoct) {
+  return has && (!guided || brisk_epiguide_band(E, t.x, t.y)) && brisk_gate_train_lane(window, t, qx, qy, qoct);
+}
 // the predicate as the header states it: M[q][t]
 BRISK_GATE_HD bool brisk_epiguide_allows(const BriskMatchEpiGuide& g, bool guided, const BriskFundamental& F, float qx, float qy, int qoct,
                                          float tx, float ty, int toct) {

@@ -64,6 +64,12 @@ BRISK_GATE_HD bool brisk_guide_lane(const BriskMatchGuide& g, bool guided, const
   L = brisk_gate_lane(g.window, c.x, c.y, octave);
   return c.has;
 }
+// the lane holds the TRAIN keypoint (the mutual form's backward scan: t = brisk_gate_lane(window, T.x, T.y, T.octave)); the query row
+// passing by comes as what brisk_guide_centre made of it - has-centre and the centre - with its own octave.  The SAME predicate as
+// brisk_guide_lane + brisk_gate_query_lane, read from the other side: the difference is still T - C, the model is not inverted
+BRISK_GATE_HD bool brisk_guide_train_row(const BriskMatchGate& window, const BriskGateLane& t, bool has, float cx, float cy, int qoct) {
+  return has && brisk_gate_train_lane(window, t, cx, cy, qoct);
+}
 // the predicate as the header states it: M[q][t]
 BRISK_GATE_HD bool brisk_guide_allows(const BriskMatchGuide& g, bool guided, const BriskHomography& H, float qx, float qy, int qoct, float tx,
                                       float ty, int toct) {

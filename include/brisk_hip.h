@@ -792,9 +792,8 @@ typedef struct brisk_hip_match_guide {
  * holding min(k, allowed) real entries and never topped up (k = 1, 2), radius counts = matches found, descriptor sizes, error codes
  * (all checked before anything is launched), asynchronous on `stream`.  Additional BRISK_HIP_ERR_ARG with npairs > 0: a NULL or
  * misaligned d_models, a NULL guide, the gated calls' keypoint-set errors.  npairs == 0 is BRISK_HIP_OK.
- * NO CROSS CHECK in the guided form: its backward scan would need the centre of every passing query row.  The linker's claim rule
- * settles rows that compete for a train row; a caller who wants mutual matches runs the guided pass with k = 1 and lets
- * brisk_hip_link_tracks_device decide. */
+ * These two calls take no cross_check argument; the cross-checked k = 1 form is a call of its own,
+ * brisk_hip_match_mutual_pairs_guided_device ("the guided pair matchers' mutual forms" below). */
 int brisk_hip_match_knn_pairs_guided_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
                                             const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
                                             const brisk_hip_pair_spec* pairs, const brisk_hip_pair_model* d_models,
@@ -836,7 +835,8 @@ typedef struct brisk_hip_match_epipolar_guide {
 } brisk_hip_match_epipolar_guide;
 /* Everything not named here is exactly as in the guided call of the same kind above, with the mask M of this section: both pair
  * forms, d_pair_rows, rows_cap, memory that is never written, k-NN rows holding min(k, allowed) real entries and never topped up
- * (k = 1, 2), radius counts = matches found, the four descriptor sizes, no cross check, asynchronous on `stream`, no workspace.
+ * (k = 1, 2), radius counts = matches found, the four descriptor sizes, no cross_check argument (the cross-checked k = 1 form is
+ * brisk_hip_match_mutual_pairs_epipolar_guided_device below), asynchronous on `stream`, no workspace.
  * BRISK_HIP_ERR_ARG before anything is launched: the guided calls' list - with npairs > 0 a NULL or misaligned d_models, a NULL
  * guide, the gated calls' keypoint-set errors.  npairs == 0 is BRISK_HIP_OK. */
 int brisk_hip_match_knn_pairs_epipolar_guided_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
@@ -850,6 +850,41 @@ int brisk_hip_match_radius_pairs_epipolar_guided_device(brisk_hip_ctx* ctx, cons
                                                         const brisk_hip_match_epipolar_guide* guide, int dim_bytes, float max_distance,
                                                         int cap_per_query, int rows_cap, brisk_hip_dmatch* d_out, int* d_out_count,
                                                         int* d_pair_rows, void* stream);
+
+/* ---- the guided pair matchers' mutual forms: k = 1 with the cross check ---------------------------------------------------------
+ * The second pass has no ratio test left - the window or the band replaced it -, so mutuality is the one descriptor-side safeguard
+ * that remains; these two calls are the guided k-NN calls for k = 1 with the first-pass matchers' fused cross check.  Stated once,
+ * for both guides: pair p = (a, b), M[q][t] the mask of the guided section in question (the window around the centre above, or the
+ * band and the window of the epipolar section), exactly as that section defines it - guided pairs, fallback pairs, rows without a
+ * centre or a line, window, octave rule, band.
+ * FORWARD: for q < min(n_a, rows_cap), f(q) is the allowed train row of smallest key (distance, t): the record the guided k-NN call
+ * writes for k = 1.
+ * BACKWARD: for t = f(q), g(t) is the row q' among ALL n_a rows of frame a - also those at or beyond rows_cap - with M[q'][t] true and
+ * the smallest key (distance, q').
+ * KEPT iff g(t) == q: the row holds the guided k = 1 record byte for byte, count 1.  Otherwise the count is 0 and the row's record
+ * is not written.
+ * The backward mask is the SAME predicate as the forward one, read from the train side - the centre of q' is still H_p(q'), the
+ * difference still T - C; the band is still T against the line of q'.  It is not an inverse model, so the identity model, and an
+ * unguided pair with fallback != 0, give exactly brisk_hip_match_knn_pairs_gated_device with gate = window, k = 1, cross_check = 1
+ * (the epipolar form with band = +INFINITY: for the rows that have a line).
+ * Everything else is what the gated call with cross_check = 1 does: d_pair_rows holds the true count, -1 for a bad d_pairs entry or
+ * for n_a or n_b of 2^22 or more (the backward keys index frame a too); n_b == 0, and an unguided pair with fallback == 0, give counts
+ * of 0; nothing behind the counts or beyond `rows` is written; asynchronous on `stream`, no workspace, no synchronisation with the
+ * host.  d_out is [npairs][rows_cap][1].  The arguments are the guided k-NN calls' without k, and so are the errors, all checked
+ * before anything is launched; npairs == 0 is BRISK_HIP_OK; dim_bytes 16, 32, 48 or 64.
+ * The rule's two backward predicates are brisk_guide_train_row (csrc/brisk_match_guide.h) and brisk_epiguide_train_row
+ * (csrc/brisk_match_epiline.h).  Measured on one MI355X (tools/bench_match_pairs.py --guided --mutual, profiles/match_mutual_pairs.json):
+ * 2.10 times the guided k = 1 call's time, where the gated call's cross check costs 2.18 times the gated call's. */
+int brisk_hip_match_mutual_pairs_guided_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                               const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                               const brisk_hip_pair_spec* pairs, const brisk_hip_pair_model* d_models,
+                                               const brisk_hip_match_guide* guide, int dim_bytes, int rows_cap, brisk_hip_dmatch* d_out,
+                                               int* d_out_count, int* d_pair_rows, void* stream);
+int brisk_hip_match_mutual_pairs_epipolar_guided_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                                        const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                                        const brisk_hip_pair_spec* pairs, const brisk_hip_pair_epipolar_model* d_models,
+                                                        const brisk_hip_match_epipolar_guide* guide, int dim_bytes, int rows_cap,
+                                                        brisk_hip_dmatch* d_out, int* d_out_count, int* d_pair_rows, void* stream);
 
 /* ---- a batch's pair matches linked into feature tracks, on the device ----------------------------------------------------------
  * What every consumer of a frame-to-previous-frame matcher does next: "row q of frame i matched row t of frame i - 1" becomes

@@ -80,6 +80,14 @@ window beside k_match_knn_pairs_gated<12, false> at the same window and shapes (
 arithmetic), and with band 3 under an all-pass window beside the ungated k_match_knn_pairs<12, false> (whether skipping rows pays for the
 fp64 test): profiles/epiguided_pairs_kernel_stats.csv.
 
+With --guided --mutual or --epiguided --mutual (profiles/match_mutual_pairs.json, one entry per form) the mutual guided call beside its
+yardsticks, four windows of back-to-back calls on one batch's sets, every pair guided (identity models under a +-6 px window; rectified
+models under band = --max-error and a +-64 px window):
+  U  the guided (epipolar-guided) k-NN call, k = 1        M  the mutual call
+  N  the gated k-NN call at the same window, k = 1        X  N with cross_check = 1
+plus M / U beside X / N - the same backward scan with the lane's own position instead of a staged centre -, the HIP-event time of one
+call of each, and, under identity models, whether M's arrays equal X's byte for byte.
+
 With --guided (k-NN only, profiles/guided_pairs.json) what matching again under the pairs' models adds, two windows:
   V  --verify's window V: detect + describe + match + select + verify + link + list
   G  V followed by brisk_hip_match_knn_pairs_guided_device (k = 1, window +-6 px, octave difference 1, fallback 0) reading the verifier's
@@ -1060,6 +1068,108 @@ def epiguided_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
     ctx.close()
 
 
+def mutual_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, batch, line):
+    """--guided --mutual / --epiguided --mutual: the mutual guided call beside its yardsticks (see the module's text); writes a.out"""
+    st = work.cuda_stream
+    spec = B.PairSpec(n - 1, 1, 1, 0, 1, None)
+    if line:
+        guide = B.MatchEpipolarGuide.around(a.max_error, window=(-64.0, 64.0, -64.0, 64.0), max_octave_diff=1, fallback=0)
+        rec = np.zeros(n - 1, B.PAIR_EPIPOLAR_MODEL)
+        rec["f"] = (0.0, 0.0, 0.0, 0.0, 0.0, -1.0, 0.0, 1.0, 0.0)  # rectified: every row has a line
+    else:
+        guide = B.MatchGuide.around(6.0, max_octave_diff=1, fallback=0)
+        rec = np.zeros(n - 1, B.PAIR_MODEL)
+        rec["h"] = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0)   # the identity: every pair guided, the gated call's mask
+    models = torch.from_numpy(rec.view(np.int64).reshape(n - 1, 12).copy()).to(dev)
+    out = {v: (torch.zeros((n - 1, cap, 1, 4), dtype=torch.int32, device=dev), torch.zeros((n - 1, cap), dtype=torch.int32, device=dev),
+               torch.zeros(n - 1, dtype=torch.int32, device=dev)) for v in "UMNX"}
+    batch()                                                          # one batch: the four calls read its sets
+    torch.cuda.synchronize()
+    dset, dim = ctx.batch_desc_set()
+    kps = ctx.batch_kp_set()
+    guided_call = ctx.match_knn_pairs_epipolar_guided if line else ctx.match_knn_pairs_guided
+    mutual_call = ctx.match_mutual_pairs_epipolar_guided if line else ctx.match_mutual_pairs_guided
+    runs = {
+        "U": lambda: guided_call(dset, dset, spec, 1, models, guide, rows_cap=cap, query_kps=kps, train_kps=kps, stream=st, dim_bytes=dim, out=out["U"]),
+        "M": lambda: mutual_call(dset, dset, spec, models, guide, rows_cap=cap, query_kps=kps, train_kps=kps, stream=st, dim_bytes=dim, out=out["M"]),
+        "N": lambda: ctx.match_knn_pairs(dset, dset, spec, 1, rows_cap=cap, stream=st, dim_bytes=dim, out=out["N"], gate=guide.window, query_kps=kps,
+                                         train_kps=kps),
+        "X": lambda: ctx.match_knn_pairs(dset, dset, spec, 1, cross_check=True, rows_cap=cap, stream=st, dim_bytes=dim, out=out["X"],
+                                         gate=guide.window, query_kps=kps, train_kps=kps),
+    }
+    order = "UMNX"
+    for v in order + order:                                         # warm-up
+        runs[v]()
+        torch.cuda.synchronize()
+    kept = {v: int((out[v][1][:, :] == 1).sum().item()) for v in order}
+    same = bool(all(torch.equal(x, y) for x, y in zip(out["M"], out["X"]))) if not line else None
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    call_ms = {v: [] for v in order}
+    for _ in range(max(a.repeats, 5)):
+        for v in order:
+            ev[0].record(work)
+            runs[v]()
+            ev[1].record(work)
+            torch.cuda.synchronize()
+            call_ms[v].append(ev[0].elapsed_time(ev[1]))
+    per = {v: [] for v in order}
+    for _ in range(a.repeats):
+        for v in order:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            calls = 0
+            while True:
+                runs[v]()
+                calls += 1
+                if calls % 8 == 0:                                   # (the queue is drained now and then: the clock is the device's, not the enqueue's)
+                    torch.cuda.synchronize()
+                    if time.perf_counter() - t0 >= a.window:
+                        break
+            torch.cuda.synchronize()
+            per[v].append(1e3 * (time.perf_counter() - t0) / calls)
+    med = {v: float(np.median(per[v])) for v in order}
+    spread = {v: (max(per[v]) - min(per[v])) / med[v] for v in order}
+    res = {
+        "workload": "bench.py's stream: %dx%d, threshold %d, %d octaves, %d frames per batch (%d distinct) in HBM; frame-to-previous-frame, "
+                    "k = 1, rows_cap %d; every pair guided: %s; the four calls read one batch's sets"
+                    % (W, H, THRESHOLD, OCTAVES, n, nd, cap,
+                       "rectified models, band %g px, window +-64 px, octave difference 1" % a.max_error if line
+                       else "identity models, window +-6 px, octave difference 1 (the gated call's mask)"),
+        "kernel_revision": ctx.kernel_revision(),
+        "device": torch.cuda.get_device_name(0),
+        "windows": {"repeats": a.repeats, "seconds_each": a.window,
+                    "order": ", ".join(order) + " alternating; a window is back-to-back calls of ONE kind, synchronised every 8 calls and at its end"},
+        "ms_per_call": {v: round(med[v], 4) for v in order},
+        "ms_per_call_all": {v: [round(x, 4) for x in per[v]] for v in order},
+        "spread_rel": {v: round(spread[v], 4) for v in order},
+        "hip_event_ms_1_call": {v: {"median": round(float(np.median(call_ms[v])), 4), "all": [round(x, 4) for x in call_ms[v]]} for v in order},
+        "M_over_U": round(med["M"] / med["U"], 4),
+        "X_over_N": round(med["X"] / med["N"], 4),
+        "M_over_U_relative_to_X_over_N": round((med["M"] / med["U"]) / (med["X"] / med["N"]), 4),
+        "rows_with_a_match": kept,
+        "M_equals_X_bytewise": same,
+        "legend": {"U": "the guided k-NN call, k = 1" if not line else "the epipolar-guided k-NN call, k = 1",
+                   "M": "the mutual guided call" if not line else "the mutual epipolar-guided call",
+                   "N": "the gated k-NN call at the guide's window, k = 1, no cross check",
+                   "X": "the gated k-NN call at the guide's window, k = 1, cross_check = 1",
+                   "yardstick": "X / N: the same backward scan with the lane's own position instead of a staged centre"
+                                + ("" if not line else " (the line form's mask differs from the gate's: its ratio is reported without a bar)")},
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if os.path.exists(a.out):                                       # one file for both forms
+        with open(a.out) as f:
+            both = json.load(f)
+    else:
+        both = {}
+    both["line" if line else "centre"] = res
+    with open(a.out, "w") as f:
+        json.dump(both, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+    ext.close()
+    ctx.close()
+
+
 def tracks_download_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
     """--tracks-download: windows T, D and P (see the module's text); writes a.out"""
     st = work.cuda_stream
@@ -1233,6 +1343,9 @@ def main():
                     help="windows V (--verify's V) and G (V + match_knn_pairs_guided on the verifier's models + select + link)")
     ap.add_argument("--epiguided", action="store_true",
                     help="windows E (--epipolar's E) and L (E + match_knn_pairs_epipolar_guided on the verifier's models + select + link)")
+    ap.add_argument("--mutual", action="store_true",
+                    help="with --guided or --epiguided: the mutual call (k = 1 with the cross check) beside the guided k = 1 call and the gated "
+                         "k = 1 call with and without cross_check, every pair guided, in the same windows")
     ap.add_argument("--epi-case", choices=("window", "band"), default="window",
                     help="--epiguided --stats-pass: the new kernel with the band off under a +-6 px window beside the gated kernel, or with "
                          "band 3 under an all-pass window beside the ungated kernel (one rocprofv3 run each: the stats merge a kernel's launches)")
@@ -1276,6 +1389,11 @@ def main():
                      "--guided / --refit")
         if a.out is None:
             a.out = os.path.join(ROOT, "profiles", "epipolar_pairs.json")
+    if a.mutual:
+        if a.guided == a.epiguided:
+            ap.error("--mutual goes with --guided or with --epiguided")
+        if a.out is None:
+            a.out = os.path.join(ROOT, "profiles", "match_mutual_pairs.json")
     if a.guided:
         if radius is not None or gate or a.export or a.tracks or a.tracks_download or a.verify:
             ap.error("--guided measures the k-NN pair call: without --radius / --gate / --export / --tracks / --tracks-download / --verify")
@@ -1351,6 +1469,9 @@ def main():
         return
     if a.epipolar:
         verify_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b, epipolar=True)
+        return
+    if a.mutual:
+        mutual_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, batch, line=a.epiguided)
         return
     if a.guided:
         guided_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b)
