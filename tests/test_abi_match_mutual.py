@@ -169,9 +169,14 @@ def restated_mask(form, window, band, fallback, model, hypothesis, flags, kq, kt
     return M, np.asarray(has, bool)
 
 
-def distances(dq, dt):
-    a, b = np.unpackbits(dq, axis=1).astype(np.float32), np.unpackbits(dt, axis=1).astype(np.float32)
-    return (a @ (1 - b).T + (1 - a) @ b.T).astype(np.int64)
+def distances(dq, dt, step=1 << 16):
+    """all Hamming distances [len(dq), len(dt)]; `step` rows of dq at a time: the unpacked bits of millions of rows are never held"""
+    b = np.unpackbits(dt, axis=1).astype(np.float32)
+    out = np.zeros((len(dq), len(dt)), np.int64)
+    for r0 in range(0, len(dq), step):
+        a = np.unpackbits(dq[r0:r0 + step], axis=1).astype(np.float32)
+        out[r0:r0 + step] = a @ (1 - b).T + (1 - a) @ b.T
+    return out
 
 
 def restated_mutual(case, pair):
