@@ -226,6 +226,8 @@ __device__ __forceinline__ uint32_t brisk_pk_max(uint32_t a, uint32_t b) { retur
 __device__ __forceinline__ uint32_t brisk_pk_min(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(BRISK_PK_S(a), BRISK_PK_S(b))); }
 __device__ __forceinline__ uint32_t brisk_pk_mul(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, (brisk_v2u)(BRISK_PK_U(a) * BRISK_PK_U(b))); }
 __device__ __forceinline__ uint32_t brisk_pk_shr(uint32_t a, uint32_t s) { return __builtin_bit_cast(uint32_t, (brisk_v2u)(BRISK_PK_U(a) >> BRISK_PK_U(s))); }
+// bytes 1 and 3 of lo, then bytes 1 and 3 of hi (v_perm_b32)
+__device__ __forceinline__ uint32_t brisk_high_bytes(uint32_t lo, uint32_t hi) { return __builtin_amdgcn_perm(hi, lo, 0x07050301u); }
 #else
 #define BRISK_PK_LANES(expr)                                                              \
   const int a0 = (int16_t)(a & 0xFFFFu), a1 = (int16_t)(a >> 16);                         \
@@ -238,6 +240,9 @@ static inline uint32_t brisk_pk_max(uint32_t a, uint32_t b) { BRISK_PK_LANES(bri
 static inline uint32_t brisk_pk_min(uint32_t a, uint32_t b) { BRISK_PK_LANES(brisk_pk_pack(a0 < b0 ? a0 : b0, a1 < b1 ? a1 : b1)) }
 static inline uint32_t brisk_pk_mul(uint32_t a, uint32_t b) { return brisk_pk_pack((int)(((a & 0xFFFFu) * (b & 0xFFFFu)) & 0xFFFFu), (int)(((a >> 16) * (b >> 16)) & 0xFFFFu)); }
 static inline uint32_t brisk_pk_shr(uint32_t a, uint32_t s) { return brisk_pk_pack((int)((a & 0xFFFFu) >> (s & 0xFFFFu)), (int)((a >> 16) >> (s >> 16))); }
+static inline uint32_t brisk_high_bytes(uint32_t lo, uint32_t hi) {
+  return ((lo >> 8) & 0xFFu) | ((lo >> 16) & 0xFF00u) | ((hi << 8) & 0xFF0000u) | (hi & 0xFF000000u);
+}
 #endif
 
 // a against b with its 16-bit halves exchanged: (min(a.lo, b.hi), min(a.hi, b.lo)) - on the device the exchange is the
@@ -258,45 +263,66 @@ static inline uint32_t brisk_pk_min_sw(uint32_t a, uint32_t b) { return brisk_pk
 static inline uint32_t brisk_pk_max_sw(uint32_t a, uint32_t b) { return brisk_pk_max(a, (b >> 16) | (b << 16)); }
 #endif
 
-// brisk_oast9_16_M_from_d on packed lanes: P[i] = (d[i], d[i + 8]) as signed 16-bit halves, i = 0 ... 7.  The minimum over
-// the nine consecutive ring differences starting at i (and, in the other half, at i + 8) by doubling - windows of 2, 4, 8,
-// then the ninth element - where an index beyond 7 is the same register with its halves exchanged: 32 packed operations per
-// polarity for all 16 arcs instead of 48 three-input ones, and the maximum over the arcs on packed lanes too.
-// (ring pixels i and i + 8 minus the centre in both halves: one packed lane pair of brisk_oast9_16_M_from_pk)
-BRISK_HD uint32_t brisk_pk_ring_pair(uint32_t px_i, uint32_t px_i8, uint32_t centre_both) { return brisk_pk_sub(px_i | (px_i8 << 16), centre_both); }
-BRISK_HD int brisk_oast9_16_M_from_pk(const uint32_t* P) {
-  uint32_t lo2[8], hi2[8], lo4[8], hi4[8], lo8[8], hi8[8];
+// brisk_oast9_16_M_from_d on packed lanes: P[i] = (e[i], e[i + 8]) as signed 16-bit halves, i = 0 ... 7, e the 16 ring
+// elements.  The nine consecutive elements starting at i <= 7 are the suffix i ... 7 of the ring's first half followed by
+// the prefix 8 ... 8 + i of its second half, and those starting at i + 8 the same with the halves' roles exchanged.  So with
+//   S[i] = min(P[i], ..., P[7])  (suffix minima of both halves at once),  Pre[i] = min(P[0], ..., P[i])  (prefix minima)
+// the arcs that start at i and at i + 8 are S[i] against Pre[i] with its halves exchanged: 7 + 6 + 8 = 21 packed operations
+// per polarity for all 16 arcs (S[0] and Pre[7] are the same value) instead of the 32 of window doubling (2, 4, 8, then the
+// ninth element; tests/emul keeps that form as the reference) or 48 three-input ones.  *bb / *bd receive the maximum of the
+// arcs' minima / the minimum of their maxima, per half.
+BRISK_HD void brisk_oast9_16_arcs_pk(const uint32_t* P, uint32_t* bb_, uint32_t* bd_) {
+  uint32_t Smin[8], Smax[8], Pmin[8], Pmax[8];
+  Smin[7] = Smax[7] = P[7];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    lo2[i] = (i < 7) ? brisk_pk_min(P[i], P[i + 1]) : brisk_pk_min_sw(P[7], P[0]);
-    hi2[i] = (i < 7) ? brisk_pk_max(P[i], P[i + 1]) : brisk_pk_max_sw(P[7], P[0]);
+  for (int i = 6; i >= 0; --i) {
+    Smin[i] = brisk_pk_min(P[i], Smin[i + 1]);
+    Smax[i] = brisk_pk_max(P[i], Smax[i + 1]);
   }
+  Pmin[0] = Pmax[0] = P[0];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    lo4[i] = (i < 6) ? brisk_pk_min(lo2[i], lo2[i + 2]) : brisk_pk_min_sw(lo2[i], lo2[i - 6]);
-    hi4[i] = (i < 6) ? brisk_pk_max(hi2[i], hi2[i + 2]) : brisk_pk_max_sw(hi2[i], hi2[i - 6]);
+  for (int i = 1; i < 7; ++i) {
+    Pmin[i] = brisk_pk_min(P[i], Pmin[i - 1]);
+    Pmax[i] = brisk_pk_max(P[i], Pmax[i - 1]);
   }
+  Pmin[7] = Smin[0];
+  Pmax[7] = Smax[0];
+  uint32_t bb = 0, bd = 0;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
-    lo8[i] = (i < 4) ? brisk_pk_min(lo4[i], lo4[i + 4]) : brisk_pk_min_sw(lo4[i], lo4[i - 4]);
-    hi8[i] = (i < 4) ? brisk_pk_max(hi4[i], hi4[i + 4]) : brisk_pk_max_sw(hi4[i], hi4[i - 4]);
-  }
-  uint32_t bb = 0, bd = 0;  // running maximum of the arcs' minima / minimum of their maxima, both halves
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const uint32_t lo9 = brisk_pk_min_sw(lo8[i], P[i]), hi9 = brisk_pk_max_sw(hi8[i], P[i]);  // (element i + 8)
+    const uint32_t lo9 = brisk_pk_min_sw(Smin[i], Pmin[i]), hi9 = brisk_pk_max_sw(Smax[i], Pmax[i]);
     bb = (i == 0) ? lo9 : brisk_pk_max(bb, lo9);
     bd = (i == 0) ? hi9 : brisk_pk_min(bd, hi9);
   }
+  *bb_ = bb;
+  *bd_ = bd;
+}
+// M from the packed ring differences P[i] = (d[i], d[i + 8])
+BRISK_HD int brisk_oast9_16_M_from_pk(const uint32_t* P) {
+  uint32_t bb, bd;
+  brisk_oast9_16_arcs_pk(P, &bb, &bd);
   const int best_bright = brisk_max((int)(int16_t)(bb & 0xFFFFu), (int)(int16_t)(bb >> 16));
   const int best_dark = brisk_min((int)(int16_t)(bd & 0xFFFFu), (int)(int16_t)(bd >> 16));
   return brisk_max(best_bright, -best_dark);
 }
+// M from the packed ring PIXELS Q[i] = (ring_i, ring_(i + 8)), values 0 ... 255, and the centre c: minima and maxima commute
+// with subtracting the centre, max_arcs min_arc(p - c) = (max_arcs min_arc p) - c, so the centre comes off the two reduced
+// values instead of the 16 ring pixels (what the kernels evaluate)
+BRISK_HD uint32_t brisk_pk_ring_pair(uint32_t px_i, uint32_t px_i8) { return px_i | (px_i8 << 16); }
+BRISK_HD int brisk_oast9_16_M_from_px(const uint32_t* Q, int c) {
+  uint32_t bb, bd;
+  brisk_oast9_16_arcs_pk(Q, &bb, &bd);
+  const int best_bright = brisk_max((int)(bb & 0xFFFFu), (int)(bb >> 16)) - c;
+  const int best_dark = brisk_min((int)(bd & 0xFFFFu), (int)(bd >> 16)) - c;
+  return brisk_max(best_bright, -best_dark);
+}
 
 // c, n, s, w, e: centre and compass pixels (ring radius 3) of two pixels, one per 16-bit lane (values 0..255).
-// Returns bit 15 of the lane (0x8000) set for a pixel that passes the pre-gate, the lane zero otherwise.
-BRISK_HD uint32_t brisk_pregate_pair(uint32_t c, uint32_t n, uint32_t s, uint32_t w, uint32_t e, const BriskPregate& g) {
-  // on the pixel values themselves (max(n - c, s - c) = max(n, s) - c): 18 packed operations instead of 21
+// brisk_pregate_pair_d returns b2' - ev per lane: negative (bit 15 of the lane set) for a pixel that passes the pre-gate,
+// the lane's other bits carry no meaning.  brisk_pregate_pair returns bit 15 of the lane (0x8000) set for a pixel that
+// passes, the lane zero otherwise.
+BRISK_HD uint32_t brisk_pregate_pair_d(uint32_t c, uint32_t n, uint32_t s, uint32_t w, uint32_t e, const BriskPregate& g) {
+  // on the pixel values themselves (max(n - c, s - c) = max(n, s) - c): 17 packed operations instead of 20
   const uint32_t mxNS = brisk_pk_max(n, s), mnNS = brisk_pk_min(n, s);
   const uint32_t mxWE = brisk_pk_max(w, e), mnWE = brisk_pk_min(w, e);
   const uint32_t vb = brisk_pk_min(mxNS, mxWE);   // - c > b2: two adjacent compass points brighter
@@ -308,10 +334,27 @@ BRISK_HD uint32_t brisk_pregate_pair(uint32_t c, uint32_t n, uint32_t s, uint32_
   const uint32_t tc = brisk_pk_min(brisk_pk_max(t5, g.lower), upper);
   const uint32_t b2p = brisk_pk_shr(brisk_pk_mul(tc, g.K), g.shift);
   const uint32_t ev = brisk_pk_max(brisk_pk_sub(vb, c), brisk_pk_sub(c, vd));
-  // passes <=> ev > b2' <=> b2' - ev < 0: the lane's sign bit (one subtraction and one 32-bit AND; a 0 / 1 result
-  // would cost a compare and a select per lane)
-  return brisk_pk_sub(b2p, ev) & 0x80008000u;
+  // passes <=> ev > b2' <=> b2' - ev < 0: the lane's sign bit (a 0 / 1 result would cost a compare and a select per lane)
+  return brisk_pk_sub(b2p, ev);
 }
+BRISK_HD uint32_t brisk_pregate_pair(uint32_t c, uint32_t n, uint32_t s, uint32_t w, uint32_t e, const BriskPregate& g) {
+  return brisk_pregate_pair_d(c, n, s, w, e, g) & 0x80008000u;
+}
+
+// Pass flags of a thread's 4 columns x up to 8 rows of pixels, collected from the pre-gate's sign bits: a row's two
+// brisk_pregate_pair_d results (columns 0 | 1 and 2 | 3) carry the flags in bits 15 and 31, i.e. in bit 7 of their bytes 1
+// and 3.  One byte permute gathers a row's four such bytes, column j in byte j; row rr is merged into the collection at
+// bit 7 - rr of every byte (one shift and one bit-field insert per row instead of an AND, a shift and an OR per pair).  The
+// other bits of the gathered bytes carry no meaning: brisk_pregate_flags_mask removes the rows never merged.
+BRISK_HD uint32_t brisk_pregate_flags_row(uint32_t acc, uint32_t d01, uint32_t d23, int rr) {
+  const uint32_t f = brisk_high_bytes(d01, d23);
+  if (rr == 0) return f;
+  const uint32_t sel = 0x80808080u >> rr;
+  return (acc & ~sel) | ((f >> rr) & sel);
+}
+BRISK_HD uint32_t brisk_pregate_flags_mask(uint32_t acc, int rows) { return acc & (0x01010101u * ((0xFF00u >> rows) & 0xFFu)); }
+// bit of the collection -> the pixel's column and row in the thread's block
+BRISK_HD void brisk_pregate_flags_decode(int bit, int* col, int* row) { *col = bit >> 3; *row = 7 - (bit & 7); }
 
 // Per-pixel detection (agast/src/oast9-16.cc:79-100 + SURVEY F5): returns D (= thrmap value) if
 // (x,y) is an AGAST point at threshold thr, else 0.  Caller guarantees 3 <= x <= w-4, 3 <= y <= h-4.

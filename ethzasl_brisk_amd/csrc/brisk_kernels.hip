@@ -530,8 +530,8 @@ __global__ void __launch_bounds__(256) k_detect(BriskGeom G, BriskTileTable T, c
       CB[r] = __builtin_amdgcn_perm(0u, R[r][1], 0x0c030c02u);   // (col 2, col 3)
     }
     DT_T(2);  // window: 30 LDS dword reads + the centre / N / S byte pairs
-    // pass flags of the thread's 16 pixels: every pair's two sign bits (15 and 31) are shifted in from the top, so
-    // pair k = 2 * rr + (j >> 1) ends at bits 16 - 2 DT_R + k (column j even) and 32 - 2 DT_R + k (column j odd)
+    // pass flags of the thread's 16 pixels: column j of row rr at bit 8 j + 7 - rr (brisk_pregate_flags_row)
+    static_assert(DT_R <= 8, "a byte of the pass flags holds one column's rows");
     unsigned m = 0;
 #pragma unroll
     for (int rr = 0; rr < DT_R; ++rr) {
@@ -540,11 +540,11 @@ __global__ void __launch_bounds__(256) k_detect(BriskGeom G, BriskTileTable T, c
       const unsigned WB = __builtin_amdgcn_perm(R[ci][1], R[ci][0], 0x0c040c03u);  // (col -1, col 0)
       const unsigned EA = __builtin_amdgcn_perm(R[ci][2], R[ci][1], 0x0c040c03u);  // (col 3, col 4)
       const unsigned EB = __builtin_amdgcn_perm(0u, R[ci][2], 0x0c020c01u);        // (col 5, col 6)
-      const unsigned gA = brisk_pregate_pair(CA[ci], CA[rr], CA[rr + 6], WA, EA, pg);
-      const unsigned gB = brisk_pregate_pair(CB[ci], CB[rr], CB[rr + 6], WB, EB, pg);
-      m = (m >> 1) | gA;
-      m = (m >> 1) | gB;
+      const unsigned gA = brisk_pregate_pair_d(CA[ci], CA[rr], CA[rr + 6], WA, EA, pg);
+      const unsigned gB = brisk_pregate_pair_d(CB[ci], CB[rr], CB[rr + 6], WB, EB, pg);
+      m = brisk_pregate_flags_row(m, gA, gB, rr);
     }
+    m = brisk_pregate_flags_mask(m, DT_R);
     DT_T(3);  // W / E byte pairs + the packed pre-gate on 16 pixels
     // compaction: wave prefix sum of the per-thread counts, one LDS atomic per wave
     const int cnt = __popc(m);
@@ -558,8 +558,9 @@ __global__ void __launch_bounds__(256) k_detect(BriskGeom G, BriskTileTable T, c
       while (m) {
         const int bit = __ffs(m) - 1;
         m &= m - 1;
-        const int k = (bit & 15) - (16 - 2 * DT_R), half = bit >> 4;
-        queue[pos++] = (uint16_t)((ly + (k >> 1)) * DT_W + lx + ((k & 1) << 1) + half);
+        int col, row;
+        brisk_pregate_flags_decode(bit, &col, &row);
+        queue[pos++] = (uint16_t)((ly + row) * DT_W + lx + col);
       }
     }
   }
@@ -598,13 +599,12 @@ __global__ void __launch_bounds__(256) k_detect(BriskGeom G, BriskTileTable T, c
     const int c = v[3][3];
     if (mx - c <= b2 && c - mn <= b2) continue;  // no ring pixel can differ by more than b2
     // ring order of brisk_oast9_16_M (agast/include/agast/oast9-16.h:99-116), pixels i and i + 8 in one packed lane pair
-    const uint32_t cc = (uint32_t)c * 0x10001u;
     uint32_t P[8];
-    P[0] = brisk_pk_ring_pair(v[3][0], v[3][6], cc); P[1] = brisk_pk_ring_pair(v[2][0], v[4][6], cc);
-    P[2] = brisk_pk_ring_pair(v[1][1], v[5][5], cc); P[3] = brisk_pk_ring_pair(v[0][2], v[6][4], cc);
-    P[4] = brisk_pk_ring_pair(v[0][3], v[6][3], cc); P[5] = brisk_pk_ring_pair(v[0][4], v[6][2], cc);
-    P[6] = brisk_pk_ring_pair(v[1][5], v[5][1], cc); P[7] = brisk_pk_ring_pair(v[2][6], v[4][0], cc);
-    if (brisk_oast9_16_M_from_pk(P) > b2) {
+    P[0] = brisk_pk_ring_pair(v[3][0], v[3][6]); P[1] = brisk_pk_ring_pair(v[2][0], v[4][6]);
+    P[2] = brisk_pk_ring_pair(v[1][1], v[5][5]); P[3] = brisk_pk_ring_pair(v[0][2], v[6][4]);
+    P[4] = brisk_pk_ring_pair(v[0][3], v[6][3]); P[5] = brisk_pk_ring_pair(v[0][4], v[6][2]);
+    P[6] = brisk_pk_ring_pair(v[1][5], v[5][1]); P[7] = brisk_pk_ring_pair(v[2][6], v[4][0]);
+    if (brisk_oast9_16_M_from_px(P, c) > b2) {
       const int D = tt;
       // the score-state map is all zero between batches (k_smap_clear): only detections are written
       smap[base + (long)gyy * stride + gx] = (uint16_t)D;
@@ -795,15 +795,15 @@ __global__ void __launch_bounds__(SB_WAVES * 64) k_score_blocks(BriskGeom G, con
       const int c = pc[0];
       // every lane reads the 9_16 ring at fixed offsets (the lanes of the 5_8 block too: their ring lies inside the own-layer
       // patch, the result is not used) - a per-lane choice between the two rings cost a select and an add per read
-      // ring differences (d[i], d[i + 8]) as signed 16-bit halves: the 16 arcs on packed lanes (brisk_oast9_16_M_from_pk)
+      // ring pixels (i, i + 8) as 16-bit halves: the 16 arcs on packed lanes, the centre subtracted from the reduced values
+      // (brisk_oast9_16_M_from_px)
       uint32_t P[8];
-      const uint32_t cc = (uint32_t)c * 0x10001u;
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const uint32_t a = pc[sb_dx16(i) + sb_dy16(i) * 16], b = pc[sb_dx16(i + 8) + sb_dy16(i + 8) * 16];
-        P[i] = brisk_pk_ring_pair(a, b, cc);
+        P[i] = brisk_pk_ring_pair(a, b);
       }
-      int v = brisk_Kp_from_M(brisk_oast9_16_M_from_pk(P));
+      int v = brisk_Kp_from_M(brisk_oast9_16_M_from_px(P, c));
       const int D = BRISK_SM_D(smv[k]);
       if (D > 2) v = D;
       if (__any(is8[k])) {  // (wave-uniform per candidate: only layer-0 candidates carry the 5_8 block)
