@@ -690,12 +690,17 @@ class Context:
         self.check(self._L.brisk_hip_batch_kp_set(self._h, C.byref(kps)))
         return kps
 
-    def _gate_args(self, gate, query_kps, train_kps):
-        """the three extra arguments of the gated calls; keypoint sets left out = the last batch's"""
+    def _kp_sets(self, query_kps, train_kps):
+        """keypoint sets left out = the last batch's"""
         if query_kps is None or train_kps is None:
             own = self.batch_kp_set()
             query_kps = own if query_kps is None else query_kps
             train_kps = own if train_kps is None else train_kps
+        return query_kps, train_kps
+
+    def _gate_args(self, gate, query_kps, train_kps):
+        """the three extra arguments of the gated calls"""
+        query_kps, train_kps = self._kp_sets(query_kps, train_kps)
         return C.byref(query_kps), C.byref(train_kps), C.byref(gate)
 
     def _pairs_prologue(self, pairs, dim_bytes, rows_cap, per_row, out):
@@ -785,13 +790,22 @@ class Context:
 
     # -- the pairs matched again inside a window around each pair's model --
     def _guide_args(self, models, guide, query_kps, train_kps):
-        """keypoint sets left out = the last batch's; models: the tensor verify_pair_matches returns, or a device pointer"""
-        if query_kps is None or train_kps is None:
-            own = self.batch_kp_set()
-            query_kps = own if query_kps is None else query_kps
-            train_kps = own if train_kps is None else train_kps
+        """the four extra arguments of the guided calls; models: the tensor verify_pair_matches returns, or a device pointer"""
+        query_kps, train_kps = self._kp_sets(query_kps, train_kps)
         ptr = models.data_ptr() if hasattr(models, "data_ptr") else models
         return C.byref(query_kps), C.byref(train_kps), (C.c_void_p(int(ptr)) if ptr else None), C.byref(guide)
+
+    def _guided_call(self, fn, rows_form, query, train, pairs, models, guide, rows_cap, query_kps, train_kps, stream, dim_bytes, out, download,
+                     per_row, scalars=()):
+        """what the six guided matchers share.  fn: the entry point; rows_form: what download=True returns, _knn_rows or _radius_rows;
+        per_row: the entries of a row; scalars: fn's arguments between dim_bytes and rows_cap"""
+        n = pairs.npairs
+        dim_bytes, rows_cap, out = self._pairs_prologue(pairs, dim_bytes, rows_cap, per_row, out)
+        m, cnt, pair_rows = out
+        qk, tk, mp, gp = self._guide_args(models, guide, query_kps, train_kps)
+        self.check(fn(self._h, C.byref(query), C.byref(train), qk, tk, C.byref(pairs), mp, gp, int(dim_bytes), *scalars, int(rows_cap),
+                      m.data_ptr(), cnt.data_ptr(), pair_rows.data_ptr(), C.c_void_p(stream) if stream else None))
+        return rows_form(out, n, rows_cap, per_row) if download else out
 
     def match_knn_pairs_guided(self, query, train, pairs, k, models, guide, rows_cap=None, query_kps=None, train_kps=None, stream=None,
                                dim_bytes=None, out=None, download=False):
@@ -799,27 +813,16 @@ class Context:
         p's model models[p] puts each query keypoint.  models: the tensor verify_pair_matches returns ([npairs, 12] int64, PAIR_MODEL
         records), or any device pointer to npairs records.  No cross_check argument (match_mutual_pairs_guided).  Everything else, and what is returned, as match_knn_pairs
         with a gate."""
-        n = pairs.npairs
-        dim_bytes, rows_cap, out = self._pairs_prologue(pairs, dim_bytes, rows_cap, k, out)
-        m, cnt, rows = out
-        qk, tk, mp, gp = self._guide_args(models, guide, query_kps, train_kps)
-        self.check(self._L.brisk_hip_match_knn_pairs_guided_device(self._h, C.byref(query), C.byref(train), qk, tk, C.byref(pairs), mp, gp,
-                                                                   int(dim_bytes), int(k), int(rows_cap), m.data_ptr(), cnt.data_ptr(),
-                                                                   rows.data_ptr(), C.c_void_p(stream) if stream else None))
-        return self._knn_rows(out, n, rows_cap, k) if download else out
+        return self._guided_call(self._L.brisk_hip_match_knn_pairs_guided_device, self._knn_rows, query, train, pairs, models, guide, rows_cap,
+                                 query_kps, train_kps, stream, dim_bytes, out, download, per_row=k, scalars=(int(k),))
 
     def match_radius_pairs_guided(self, query, train, pairs, max_distance, cap_per_query, models, guide, rows_cap=None, query_kps=None,
                                   train_kps=None, stream=None, dim_bytes=None, out=None, download=False):
         """brisk_hip_match_radius_pairs_guided_device: match_radius_pairs behind the guide; the conventions of
         match_knn_pairs_guided, and what is returned as match_radius_pairs."""
-        n, cpq = pairs.npairs, int(cap_per_query)
-        dim_bytes, rows_cap, out = self._pairs_prologue(pairs, dim_bytes, rows_cap, cpq, out)
-        m, cnt, rows = out
-        qk, tk, mp, gp = self._guide_args(models, guide, query_kps, train_kps)
-        self.check(self._L.brisk_hip_match_radius_pairs_guided_device(self._h, C.byref(query), C.byref(train), qk, tk, C.byref(pairs), mp, gp,
-                                                                      int(dim_bytes), float(max_distance), cpq, int(rows_cap), m.data_ptr(),
-                                                                      cnt.data_ptr(), rows.data_ptr(), C.c_void_p(stream) if stream else None))
-        return self._radius_rows(out, n, rows_cap, cpq) if download else out
+        cpq = int(cap_per_query)
+        return self._guided_call(self._L.brisk_hip_match_radius_pairs_guided_device, self._radius_rows, query, train, pairs, models, guide, rows_cap,
+                                 query_kps, train_kps, stream, dim_bytes, out, download, per_row=cpq, scalars=(float(max_distance), cpq))
 
     # -- the pairs matched again inside a band around each epipolar line --
     def match_knn_pairs_epipolar_guided(self, query, train, pairs, k, models, guide, rows_cap=None, query_kps=None, train_kps=None, stream=None,
@@ -829,28 +832,17 @@ class Context:
         tensor verify_pair_matches_epipolar returns ([npairs, 12] int64, PAIR_EPIPOLAR_MODEL records), or any device pointer to npairs
         records.  No cross_check argument (match_mutual_pairs_epipolar_guided).  Everything else, and what is returned, as match_knn_pairs
         with a gate."""
-        n = pairs.npairs
-        dim_bytes, rows_cap, out = self._pairs_prologue(pairs, dim_bytes, rows_cap, k, out)
-        m, cnt, rows = out
-        qk, tk, mp, gp = self._guide_args(models, guide, query_kps, train_kps)
-        self.check(self._L.brisk_hip_match_knn_pairs_epipolar_guided_device(self._h, C.byref(query), C.byref(train), qk, tk, C.byref(pairs), mp, gp,
-                                                                            int(dim_bytes), int(k), int(rows_cap), m.data_ptr(), cnt.data_ptr(),
-                                                                            rows.data_ptr(), C.c_void_p(stream) if stream else None))
-        return self._knn_rows(out, n, rows_cap, k) if download else out
+        return self._guided_call(self._L.brisk_hip_match_knn_pairs_epipolar_guided_device, self._knn_rows, query, train, pairs, models, guide,
+                                 rows_cap, query_kps, train_kps, stream, dim_bytes, out, download, per_row=k, scalars=(int(k),))
 
     def match_radius_pairs_epipolar_guided(self, query, train, pairs, max_distance, cap_per_query, models, guide, rows_cap=None, query_kps=None,
                                            train_kps=None, stream=None, dim_bytes=None, out=None, download=False):
         """brisk_hip_match_radius_pairs_epipolar_guided_device: match_radius_pairs behind the epipolar guide; the conventions of
         match_knn_pairs_epipolar_guided, and what is returned as match_radius_pairs."""
-        n, cpq = pairs.npairs, int(cap_per_query)
-        dim_bytes, rows_cap, out = self._pairs_prologue(pairs, dim_bytes, rows_cap, cpq, out)
-        m, cnt, rows = out
-        qk, tk, mp, gp = self._guide_args(models, guide, query_kps, train_kps)
-        self.check(self._L.brisk_hip_match_radius_pairs_epipolar_guided_device(self._h, C.byref(query), C.byref(train), qk, tk, C.byref(pairs), mp, gp,
-                                                                               int(dim_bytes), float(max_distance), cpq, int(rows_cap),
-                                                                               m.data_ptr(), cnt.data_ptr(), rows.data_ptr(),
-                                                                               C.c_void_p(stream) if stream else None))
-        return self._radius_rows(out, n, rows_cap, cpq) if download else out
+        cpq = int(cap_per_query)
+        return self._guided_call(self._L.brisk_hip_match_radius_pairs_epipolar_guided_device, self._radius_rows, query, train, pairs, models,
+                                 guide, rows_cap, query_kps, train_kps, stream, dim_bytes, out, download, per_row=cpq,
+                                 scalars=(float(max_distance), cpq))
 
     # -- the guided pair matchers' mutual forms: k = 1 with the cross check --
     def match_mutual_pairs_guided(self, query, train, pairs, models, guide, rows_cap=None, query_kps=None, train_kps=None, stream=None,
@@ -858,27 +850,15 @@ class Context:
         """brisk_hip_match_mutual_pairs_guided_device: match_knn_pairs_guided for k = 1 with the cross check - row q keeps its record
         iff, under the same mask asked from the train side, its train row's best match among ALL rows of the query frame is q.
         Arguments, and what is returned, as match_knn_pairs_guided with k = 1."""
-        n = pairs.npairs
-        dim_bytes, rows_cap, out = self._pairs_prologue(pairs, dim_bytes, rows_cap, 1, out)
-        m, cnt, rows = out
-        qk, tk, mp, gp = self._guide_args(models, guide, query_kps, train_kps)
-        self.check(self._L.brisk_hip_match_mutual_pairs_guided_device(self._h, C.byref(query), C.byref(train), qk, tk, C.byref(pairs), mp, gp,
-                                                                      int(dim_bytes), int(rows_cap), m.data_ptr(), cnt.data_ptr(),
-                                                                      rows.data_ptr(), C.c_void_p(stream) if stream else None))
-        return self._knn_rows(out, n, rows_cap, 1) if download else out
+        return self._guided_call(self._L.brisk_hip_match_mutual_pairs_guided_device, self._knn_rows, query, train, pairs, models, guide, rows_cap,
+                                 query_kps, train_kps, stream, dim_bytes, out, download, per_row=1)
 
     def match_mutual_pairs_epipolar_guided(self, query, train, pairs, models, guide, rows_cap=None, query_kps=None, train_kps=None, stream=None,
                                            dim_bytes=None, out=None, download=False):
         """brisk_hip_match_mutual_pairs_epipolar_guided_device: match_knn_pairs_epipolar_guided for k = 1 with the cross check; the
         conventions of match_mutual_pairs_guided."""
-        n = pairs.npairs
-        dim_bytes, rows_cap, out = self._pairs_prologue(pairs, dim_bytes, rows_cap, 1, out)
-        m, cnt, rows = out
-        qk, tk, mp, gp = self._guide_args(models, guide, query_kps, train_kps)
-        self.check(self._L.brisk_hip_match_mutual_pairs_epipolar_guided_device(self._h, C.byref(query), C.byref(train), qk, tk, C.byref(pairs), mp,
-                                                                               gp, int(dim_bytes), int(rows_cap), m.data_ptr(), cnt.data_ptr(),
-                                                                               rows.data_ptr(), C.c_void_p(stream) if stream else None))
-        return self._knn_rows(out, n, rows_cap, 1) if download else out
+        return self._guided_call(self._L.brisk_hip_match_mutual_pairs_epipolar_guided_device, self._knn_rows, query, train, pairs, models, guide,
+                                 rows_cap, query_kps, train_kps, stream, dim_bytes, out, download, per_row=1)
 
     # -- the pair matchers' exit: selected matches, packed --
     def select_pair_matches(self, out_triple, per_row, select, matches_cap=None, stream=None):
@@ -919,6 +899,29 @@ class Context:
         self.check(rc)
         return n.value
 
+    # -- a batch's pair matches checked against a model of the pair --
+    @staticmethod
+    def _pair_lists(n, out_cap, dev):
+        """the five device tensors the pair-model calls return: matches, counts, flags, offsets, models"""
+        import torch
+        n = max(n, 0)
+        return (torch.empty((max(int(out_cap), 0), 4), dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+                torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n + 1, dtype=torch.int64, device=dev),
+                torch.empty((n, 12), dtype=torch.int64, device=dev))
+
+    def _pair_models_call(self, fn, query, train, pairs, rows_cap, offsets, matches, rule, out_cap, query_kps, train_kps, stream, models=()):
+        """what the two verifiers and the refit share.  fn: the entry point; rule: its PairVerify or PairRefit; models: the
+        arguments in front of it (the refit's input models)"""
+        n, in_cap = int(pairs.npairs), int(matches.shape[0])
+        if out_cap is None:
+            out_cap = in_cap
+        query_kps, train_kps = self._kp_sets(query_kps, train_kps)
+        res = self._pair_lists(n, out_cap, matches.device)
+        self.check(fn(self._h, C.byref(query), C.byref(train), C.byref(query_kps), C.byref(train_kps), C.byref(pairs), int(rows_cap),
+                      offsets.data_ptr(), matches.data_ptr(), in_cap, *models, C.byref(rule), int(out_cap), res[4].data_ptr(),
+                      res[1].data_ptr(), res[2].data_ptr(), res[3].data_ptr(), res[0].data_ptr(), C.c_void_p(stream) if stream else None))
+        return res
+
     # -- a batch's pair matches checked against a homography --
     def verify_pair_matches(self, query, train, pairs, rows_cap, offsets, matches, verify, out_cap=None, query_kps=None, train_kps=None,
                             stream=None):
@@ -928,24 +931,8 @@ class Context:
         (matches [out_cap, 4] int32 - the kept DMATCH records, in order -, counts [npairs], flags [npairs], offsets [npairs + 1]
         int64, models [npairs, 12] int64 - PAIR_MODEL records); the first four are what link_tracks and the exits take.
         Asynchronous on `stream`."""
-        import torch
-        n, in_cap = int(pairs.npairs), int(matches.shape[0])
-        if out_cap is None:
-            out_cap = in_cap
-        if query_kps is None or train_kps is None:
-            own = self.batch_kp_set()
-            query_kps = own if query_kps is None else query_kps
-            train_kps = own if train_kps is None else train_kps
-        dev = matches.device
-        res = (torch.empty((max(int(out_cap), 0), 4), dtype=torch.int32, device=dev), torch.empty(max(n, 0), dtype=torch.int32, device=dev),
-               torch.empty(max(n, 0), dtype=torch.int32, device=dev), torch.empty(max(n, 0) + 1, dtype=torch.int64, device=dev),
-               torch.empty((max(n, 0), 12), dtype=torch.int64, device=dev))
-        self.check(self._L.brisk_hip_verify_pair_matches_device(self._h, C.byref(query), C.byref(train), C.byref(query_kps), C.byref(train_kps),
-                                                                C.byref(pairs), int(rows_cap), offsets.data_ptr(), matches.data_ptr(), in_cap,
-                                                                C.byref(verify), int(out_cap), res[4].data_ptr(), res[1].data_ptr(),
-                                                                res[2].data_ptr(), res[3].data_ptr(), res[0].data_ptr(),
-                                                                C.c_void_p(stream) if stream else None))
-        return res
+        return self._pair_models_call(self._L.brisk_hip_verify_pair_matches_device, query, train, pairs, rows_cap, offsets, matches, verify,
+                                      out_cap, query_kps, train_kps, stream)
 
     # -- a batch's pair matches checked against an epipolar geometry --
     def verify_pair_matches_epipolar(self, query, train, pairs, rows_cap, offsets, matches, verify, out_cap=None, query_kps=None,
@@ -955,25 +942,8 @@ class Context:
         verify: a PairVerify whose max_error is the Sampson distance in pixels and whose min_inliers is >= 8.  Returns the same
         five device tensors; models [npairs, 12] int64 holds PAIR_EPIPOLAR_MODEL records - not homographies: they are not for
         refit_pair_models or the guided matchers.  Asynchronous on `stream`."""
-        import torch
-        n, in_cap = int(pairs.npairs), int(matches.shape[0])
-        if out_cap is None:
-            out_cap = in_cap
-        if query_kps is None or train_kps is None:
-            own = self.batch_kp_set()
-            query_kps = own if query_kps is None else query_kps
-            train_kps = own if train_kps is None else train_kps
-        dev = matches.device
-        res = (torch.empty((max(int(out_cap), 0), 4), dtype=torch.int32, device=dev), torch.empty(max(n, 0), dtype=torch.int32, device=dev),
-               torch.empty(max(n, 0), dtype=torch.int32, device=dev), torch.empty(max(n, 0) + 1, dtype=torch.int64, device=dev),
-               torch.empty((max(n, 0), 12), dtype=torch.int64, device=dev))
-        self.check(self._L.brisk_hip_verify_pair_matches_epipolar_device(self._h, C.byref(query), C.byref(train), C.byref(query_kps),
-                                                                         C.byref(train_kps), C.byref(pairs), int(rows_cap), offsets.data_ptr(),
-                                                                         matches.data_ptr(), in_cap, C.byref(verify), int(out_cap),
-                                                                         res[4].data_ptr(), res[1].data_ptr(), res[2].data_ptr(),
-                                                                         res[3].data_ptr(), res[0].data_ptr(),
-                                                                         C.c_void_p(stream) if stream else None))
-        return res
+        return self._pair_models_call(self._L.brisk_hip_verify_pair_matches_epipolar_device, query, train, pairs, rows_cap, offsets, matches,
+                                      verify, out_cap, query_kps, train_kps, stream)
 
     # -- each pair's homography fitted again to all its inliers --
     def refit_pair_models(self, query, train, pairs, rows_cap, offsets, matches, models, refit, out_cap=None, query_kps=None, train_kps=None,
@@ -982,25 +952,9 @@ class Context:
         selection's output), not what it returned; models: the models tensor it returned ([npairs, 12] int64, PAIR_MODEL records) or
         a device pointer to npairs records; refit: a PairRefit.  Everything else, and what is returned (matches, counts, flags,
         offsets, models), as verify_pair_matches.  Asynchronous on `stream`."""
-        import torch
-        n, in_cap = int(pairs.npairs), int(matches.shape[0])
-        if out_cap is None:
-            out_cap = in_cap
-        if query_kps is None or train_kps is None:
-            own = self.batch_kp_set()
-            query_kps = own if query_kps is None else query_kps
-            train_kps = own if train_kps is None else train_kps
-        dev = matches.device
         ptr = models.data_ptr() if hasattr(models, "data_ptr") else models
-        res = (torch.empty((max(int(out_cap), 0), 4), dtype=torch.int32, device=dev), torch.empty(max(n, 0), dtype=torch.int32, device=dev),
-               torch.empty(max(n, 0), dtype=torch.int32, device=dev), torch.empty(max(n, 0) + 1, dtype=torch.int64, device=dev),
-               torch.empty((max(n, 0), 12), dtype=torch.int64, device=dev))
-        self.check(self._L.brisk_hip_refit_pair_models_device(self._h, C.byref(query), C.byref(train), C.byref(query_kps), C.byref(train_kps),
-                                                              C.byref(pairs), int(rows_cap), offsets.data_ptr(), matches.data_ptr(), in_cap,
-                                                              C.c_void_p(int(ptr)) if ptr else None, C.byref(refit), int(out_cap),
-                                                              res[4].data_ptr(), res[1].data_ptr(), res[2].data_ptr(), res[3].data_ptr(),
-                                                              res[0].data_ptr(), C.c_void_p(stream) if stream else None))
-        return res
+        return self._pair_models_call(self._L.brisk_hip_refit_pair_models_device, query, train, pairs, rows_cap, offsets, matches, refit,
+                                      out_cap, query_kps, train_kps, stream, models=(C.c_void_p(int(ptr)) if ptr else None,))
 
     # -- a batch's pair matches linked into feature tracks --
     @staticmethod

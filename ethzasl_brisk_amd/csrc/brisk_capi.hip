@@ -1944,6 +1944,23 @@ static const char* match_gated_check(const brisk_hip_kp_set* qk, const brisk_hip
   return nullptr;
 }
 
+// npairs > 0: the first and the last pair of the arithmetic form name frames inside the two sets.  (A list on the device is checked
+// there: the matchers set d_pair_rows = -1, the pair-model calls flag the pair bad)
+static bool pair_frames_in_sets(const brisk_hip_pair_spec* pairs, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train) {
+  if (pairs->d_pairs) return true;
+  const long q0 = pairs->query_first, q1 = q0 + (long)(pairs->npairs - 1) * pairs->query_step;
+  const long t0 = pairs->train_first, t1 = t0 + (long)(pairs->npairs - 1) * pairs->train_step;
+  return q0 >= 0 && q0 < query->frames && q1 >= 0 && q1 < query->frames && t0 >= 0 && t0 < train->frames && t1 >= 0 && t1 < train->frames;
+}
+// the public sets and the pair spec as the kernels take them
+static BriskDescSet device_desc_set(const brisk_hip_desc_set* s) {
+  return BriskDescSet{s->d_desc, s->d_counts, s->count_stride, s->frame_pitch, s->row_pitch, s->frames};
+}
+static BriskKpSet device_kp_set(const brisk_hip_kp_set* s) { return BriskKpSet{reinterpret_cast<const char*>(s->d_kps), s->frame_pitch}; }
+static BriskPairSpec device_pair_spec(const brisk_hip_pair_spec* p) {
+  return BriskPairSpec{p->npairs, p->query_first, p->query_step, p->train_first, p->train_step, p->d_pairs};
+}
+
 // What the eight pair matchers (k-NN and radius, each plain, gated, guided and epipolar-guided) share.  An entry point runs its own checks and the shared
 // ones in ITS order - the k-NN forms look at the sets before npairs == 0 returns OK, the radius forms behind it - and ends in run().
 // name: "match_pairs" or "match_radius_pairs", the head of the messages; the keypoint sets and the gate: the gated forms only.
@@ -1986,27 +2003,18 @@ struct PairCall {
     if (gated)
       if (const char* msg = match_gated_check(query_kps, train_kps, window())) return fail(ctx, BRISK_HIP_ERR_ARG, msg);
     if (rows_cap < 1 || !d_out || !d_out_count || !d_pair_rows) return err(BRISK_HIP_ERR_ARG, "bad output argument");
-    const int np = pairs->npairs;
-    if (!pairs->d_pairs) {  // (a list on the device is checked there: d_pair_rows = -1)
-      const long q0 = pairs->query_first, q1 = q0 + (long)(np - 1) * pairs->query_step;
-      const long t0 = pairs->train_first, t1 = t0 + (long)(np - 1) * pairs->train_step;
-      if (q0 < 0 || q0 >= query->frames || q1 < 0 || q1 >= query->frames || t0 < 0 || t0 >= train->frames || t1 < 0 || t1 >= train->frames)
-        return err(BRISK_HIP_ERR_ARG, "a pair names a frame outside its set");
-    }
+    if (!pair_frames_in_sets(pairs, query, train)) return err(BRISK_HIP_ERR_ARG, "a pair names a frame outside its set");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
     // no workspace of the context is written, but the sets usually ARE the last batch's result buffers: the stream is ordered
     // behind that batch, and the next batch (which overwrites them) behind this call
     if (workspace_acquire(ctx, st)) return fail(ctx, BRISK_HIP_ERR_HIP, "hipStreamWaitEvent failed");
     WorkspaceGuard guard(ctx, st);
-    const BriskDescSet Q{query->d_desc, query->d_counts, query->count_stride, query->frame_pitch, query->row_pitch, query->frames};
-    const BriskDescSet T{train->d_desc, train->d_counts, train->count_stride, train->frame_pitch, train->row_pitch, train->frames};
-    const BriskPairSpec P{np, pairs->query_first, pairs->query_step, pairs->train_first, pairs->train_step, pairs->d_pairs};
-    BriskKpSet QK{}, TK{};
+    const BriskDescSet Q = device_desc_set(query), T = device_desc_set(train);
+    const BriskPairSpec P = device_pair_spec(pairs);
+    const BriskKpSet QK = gated ? device_kp_set(query_kps) : BriskKpSet{}, TK = gated ? device_kp_set(train_kps) : BriskKpSet{};
     BriskMatchGate G{};
     if (gated) {
-      QK = BriskKpSet{reinterpret_cast<const char*>(query_kps->d_kps), query_kps->frame_pitch};
-      TK = BriskKpSet{reinterpret_cast<const char*>(train_kps->d_kps), train_kps->frame_pitch};
       const brisk_hip_match_gate* g = window();
       G = BriskMatchGate{g->dx_min, g->dx_max, g->dy_min, g->dy_max, g->max_octave_diff};
     }
@@ -2261,8 +2269,8 @@ static int pair_lists_check_sizes(brisk_hip_ctx* ctx, const std::string& name, i
 static int pair_lists_check_arrays(brisk_hip_ctx* ctx, const std::string& name, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
                                    const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps, const brisk_hip_pair_spec* pairs,
                                    const long long* d_offsets, const brisk_hip_dmatch* d_matches, long long in_cap, long long out_cap,
-                                   const brisk_hip_pair_model* d_models, const int* d_out_counts, const int* d_out_flags,
-                                   const long long* d_out_offsets, const brisk_hip_dmatch* d_out_matches) {
+                                   const void* d_models, const int* d_out_counts, const int* d_out_flags, const long long* d_out_offsets,
+                                   const brisk_hip_dmatch* d_out_matches) {
   auto err = [&](const char* what) { return fail(ctx, BRISK_HIP_ERR_ARG, (name + ": " + what).c_str()); };
   const int np = pairs->npairs;
   if (((((uintptr_t)d_matches | (uintptr_t)d_out_matches) & 15)) || (((uintptr_t)d_offsets | (uintptr_t)d_out_offsets | (uintptr_t)d_models) & 7) ||
@@ -2280,12 +2288,7 @@ static int pair_lists_check_arrays(brisk_hip_ctx* ctx, const std::string& name, 
     }
     if (!d_offsets || (in_cap > 0 && !d_matches)) return err("null match lists");
     if (!d_models || !d_out_counts || !d_out_flags || !d_out_offsets || (out_cap > 0 && !d_out_matches)) return err("null output array");
-    if (!pairs->d_pairs) {  // (a list on the device is checked there: the pair is flagged bad)
-      const long q0 = pairs->query_first, q1 = q0 + (long)(np - 1) * pairs->query_step;
-      const long t0 = pairs->train_first, t1 = t0 + (long)(np - 1) * pairs->train_step;
-      if (q0 < 0 || q0 >= query->frames || q1 < 0 || q1 >= query->frames || t0 < 0 || t0 >= train->frames || t1 < 0 || t1 >= train->frames)
-        return err("a pair names a frame outside its set");
-    }
+    if (!pair_frames_in_sets(pairs, query, train)) return err("a pair names a frame outside its set");
   }
   return BRISK_HIP_OK;
 }
@@ -2313,15 +2316,38 @@ static int pair_lists_run(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, c
     HIPCHK(ctx, ctx->d_verify.grow(bytes));
   }
   unsigned char* base = ctx->d_verify.as<unsigned char>();
-  const BriskDescSet Q{query->d_desc, query->d_counts, query->count_stride, query->frame_pitch, query->row_pitch, query->frames};
-  const BriskDescSet T{train->d_desc, train->d_counts, train->count_stride, train->frame_pitch, train->row_pitch, train->frames};
-  const BriskPairSpec P{np, pairs->query_first, pairs->query_step, pairs->train_first, pairs->train_step, pairs->d_pairs};
-  const BriskKpSet QK{reinterpret_cast<const char*>(query_kps->d_kps), query_kps->frame_pitch};
-  const BriskKpSet TK{reinterpret_cast<const char*>(train_kps->d_kps), train_kps->frame_pitch};
-  launch(Q, T, QK, TK, P, base, reinterpret_cast<long long*>(base + at_kept), st);
+  launch(device_desc_set(query), device_desc_set(train), device_kp_set(query_kps), device_kp_set(train_kps), device_pair_spec(pairs), base,
+         reinterpret_cast<long long*>(base + at_kept), st);
   HIPCHK(ctx, hipGetLastError());
   if (guard.release()) return fail(ctx, BRISK_HIP_ERR_HIP, "hipEventRecord failed");
   return BRISK_HIP_OK;
+}
+
+// the two verifiers.  name: the head of the messages; min_sample with sample_msg: the least min_inliers and what a call below it
+// is told; launch: brisk_launch_pair_verify or brisk_launch_pair_epipolar, Model: the records it writes (d_models)
+template <class Model, class Launch>
+static int pair_verify_call(brisk_hip_ctx* ctx, const std::string& name, int min_sample, const char* sample_msg, const brisk_hip_desc_set* query,
+                            const brisk_hip_desc_set* train, const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                            const brisk_hip_pair_spec* pairs, int rows_cap, const long long* d_offsets, const brisk_hip_dmatch* d_matches,
+                            long long in_cap, const brisk_hip_pair_verify* verify, long long out_cap, void* d_models, int* d_out_counts,
+                            int* d_out_flags, long long* d_out_offsets, brisk_hip_dmatch* d_out_matches, void* stream, Launch launch) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (!pairs || !verify) return fail(ctx, BRISK_HIP_ERR_ARG, (name + ": null pairs or verify").c_str());
+  if (int rc = pair_lists_check_sizes(ctx, name, pairs->npairs, rows_cap, in_cap, out_cap)) return rc;
+  if (verify->hypotheses < 1 || verify->hypotheses > BRISK_VERIFY_MAX_HYPOTHESES || verify->min_inliers < min_sample)
+    return fail(ctx, BRISK_HIP_ERR_ARG, (name + ": " + sample_msg).c_str());
+  if (int rc = pair_lists_check_arrays(ctx, name, query, train, query_kps, train_kps, pairs, d_offsets, d_matches, in_cap, out_cap, d_models,
+                                       d_out_counts, d_out_flags, d_out_offsets, d_out_matches))
+    return rc;
+  const BriskPairVerify V{verify->max_error, verify->hypotheses, verify->min_inliers, verify->keep_unverified, verify->seed};
+  return pair_lists_run(ctx, query, train, query_kps, train_kps, pairs, in_cap, d_out_offsets, stream,
+                        [&](const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK, const BriskPairSpec& P,
+                            unsigned char* keep, long long* kept, hipStream_t st) {
+                          launch(Q, T, QK, TK, P, rows_cap, d_offsets, reinterpret_cast<const BriskDMatch*>(d_matches), in_cap, V, keep, kept,
+                                 out_cap, static_cast<Model*>(d_models), d_out_counts, d_out_flags, d_out_offsets,
+                                 reinterpret_cast<BriskDMatch*>(d_out_matches), st);
+                        });
 }
 }
 
@@ -2331,23 +2357,9 @@ int brisk_hip_verify_pair_matches_device(brisk_hip_ctx* ctx, const brisk_hip_des
                                          const brisk_hip_dmatch* d_matches, long long in_cap, const brisk_hip_pair_verify* verify,
                                          long long out_cap, brisk_hip_pair_model* d_models, int* d_out_counts, int* d_out_flags,
                                          long long* d_out_offsets, brisk_hip_dmatch* d_out_matches, void* stream) {
-  if (!ctx) return BRISK_HIP_ERR_ARG;
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  if (!pairs || !verify) return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: null pairs or verify");
-  if (int rc = pair_lists_check_sizes(ctx, "verify_pair_matches", pairs->npairs, rows_cap, in_cap, out_cap)) return rc;
-  if (verify->hypotheses < 1 || verify->hypotheses > BRISK_VERIFY_MAX_HYPOTHESES || verify->min_inliers < BRISK_VERIFY_MIN_SAMPLE)
-    return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches: hypotheses outside 1 ... 4096, or min_inliers below 4");
-  if (int rc = pair_lists_check_arrays(ctx, "verify_pair_matches", query, train, query_kps, train_kps, pairs, d_offsets, d_matches, in_cap, out_cap,
-                                       d_models, d_out_counts, d_out_flags, d_out_offsets, d_out_matches))
-    return rc;
-  const BriskPairVerify V{verify->max_error, verify->hypotheses, verify->min_inliers, verify->keep_unverified, verify->seed};
-  return pair_lists_run(ctx, query, train, query_kps, train_kps, pairs, in_cap, d_out_offsets, stream,
-                        [&](const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK, const BriskPairSpec& P,
-                            unsigned char* keep, long long* kept, hipStream_t st) {
-                          brisk_launch_pair_verify(Q, T, QK, TK, P, rows_cap, d_offsets, reinterpret_cast<const BriskDMatch*>(d_matches), in_cap, V,
-                                                   keep, kept, out_cap, reinterpret_cast<BriskPairModel*>(d_models), d_out_counts, d_out_flags,
-                                                   d_out_offsets, reinterpret_cast<BriskDMatch*>(d_out_matches), st);
-                        });
+  return pair_verify_call<BriskPairModel>(ctx, "verify_pair_matches", BRISK_VERIFY_MIN_SAMPLE, "hypotheses outside 1 ... 4096, or min_inliers below 4",
+                                          query, train, query_kps, train_kps, pairs, rows_cap, d_offsets, d_matches, in_cap, verify, out_cap,
+                                          d_models, d_out_counts, d_out_flags, d_out_offsets, d_out_matches, stream, brisk_launch_pair_verify);
 }
 
 // ---- a batch's pair matches checked against an epipolar geometry (kernel: k_epipolar_ransac, brisk_pair_verify.hip; the rule:
@@ -2361,24 +2373,10 @@ int brisk_hip_verify_pair_matches_epipolar_device(brisk_hip_ctx* ctx, const bris
                                                   const brisk_hip_dmatch* d_matches, long long in_cap, const brisk_hip_pair_verify* verify,
                                                   long long out_cap, brisk_hip_pair_epipolar_model* d_models, int* d_out_counts,
                                                   int* d_out_flags, long long* d_out_offsets, brisk_hip_dmatch* d_out_matches, void* stream) {
-  if (!ctx) return BRISK_HIP_ERR_ARG;
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  if (!pairs || !verify) return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches_epipolar: null pairs or verify");
-  if (int rc = pair_lists_check_sizes(ctx, "verify_pair_matches_epipolar", pairs->npairs, rows_cap, in_cap, out_cap)) return rc;
-  if (verify->hypotheses < 1 || verify->hypotheses > BRISK_VERIFY_MAX_HYPOTHESES || verify->min_inliers < BRISK_EPIPOLAR_MIN_SAMPLE)
-    return fail(ctx, BRISK_HIP_ERR_ARG, "verify_pair_matches_epipolar: hypotheses outside 1 ... 4096, or min_inliers below 8");
-  if (int rc = pair_lists_check_arrays(ctx, "verify_pair_matches_epipolar", query, train, query_kps, train_kps, pairs, d_offsets, d_matches, in_cap,
-                                       out_cap, reinterpret_cast<const brisk_hip_pair_model*>(d_models), d_out_counts, d_out_flags, d_out_offsets,
-                                       d_out_matches))
-    return rc;
-  const BriskPairVerify V{verify->max_error, verify->hypotheses, verify->min_inliers, verify->keep_unverified, verify->seed};
-  return pair_lists_run(ctx, query, train, query_kps, train_kps, pairs, in_cap, d_out_offsets, stream,
-                        [&](const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK, const BriskPairSpec& P,
-                            unsigned char* keep, long long* kept, hipStream_t st) {
-                          brisk_launch_pair_epipolar(Q, T, QK, TK, P, rows_cap, d_offsets, reinterpret_cast<const BriskDMatch*>(d_matches), in_cap,
-                                                     V, keep, kept, out_cap, reinterpret_cast<BriskPairEpipolarModel*>(d_models), d_out_counts,
-                                                     d_out_flags, d_out_offsets, reinterpret_cast<BriskDMatch*>(d_out_matches), st);
-                        });
+  return pair_verify_call<BriskPairEpipolarModel>(ctx, "verify_pair_matches_epipolar", BRISK_EPIPOLAR_MIN_SAMPLE,
+                                                  "hypotheses outside 1 ... 4096, or min_inliers below 8", query, train, query_kps, train_kps, pairs,
+                                                  rows_cap, d_offsets, d_matches, in_cap, verify, out_cap, d_models, d_out_counts, d_out_flags,
+                                                  d_out_offsets, d_out_matches, stream, brisk_launch_pair_epipolar);
 }
 
 // ---- the pairs' models fitted again to all their inliers (kernel: k_refit_models, brisk_pair_verify.hip; the rule: brisk_pair_refit.h) ----

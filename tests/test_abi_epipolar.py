@@ -71,6 +71,7 @@ def test_epipolar_kernel_uses_no_scratch():
     for k, v in new.items():
         assert v["scratch"] == 0, (k, v)
         assert v["lds"] >= 1024 * 16                                  # the staged chunk: 1 024 records of four floats
+        assert v["occupancy"] >= 1                                    # waves per SIMD: the solve has one wave's registers, no fewer
     # the packing kernels are the verifier's: no kernel of this call carries its prefix
     assert sorted(re.search(r"k_verify_[a-z]+", k).group(0) for k in res if "k_verify_" in k) == ["k_verify_offsets", "k_verify_ransac",
                                                                                                 "k_verify_scatter"]

@@ -66,6 +66,7 @@ def test_refit_kernel_uses_no_scratch():
     v = list(new.values())[0]
     assert v["scratch"] == 0, v
     assert v["lds"] >= 1024 * 16                                     # the staged chunk: 1 024 records of four floats
+    assert v["occupancy"] >= 2                                       # waves per SIMD: what the kernel had before its pieces were shared
 
 
 # ---- the rule, restated ---------------------------------------------------------------------------------------------------------

@@ -84,6 +84,7 @@ def test_verify_kernels_use_no_scratch():
         assert v["scratch"] == 0, (k, v)
     ransac = [v for k, v in new.items() if "k_verify_ransac" in k][0]
     assert ransac["lds"] >= 1024 * 16                                  # the staged chunk: 1 024 records of four floats
+    assert ransac["occupancy"] >= 5                                    # waves per SIMD: what the kernel had before its pieces were shared
 
 
 # ---- the rule, restated ---------------------------------------------------------------------------------------------------------
