@@ -45,7 +45,7 @@ ABI_SYMBOLS = [
     "brisk_hip_batch_kp_set", "brisk_hip_match_knn_pairs_gated_device", "brisk_hip_match_radius_pairs_gated_device",
     "brisk_hip_select_pair_matches_device", "brisk_hip_pair_matches_download", "brisk_hip_pair_matches_wait",
     "brisk_hip_verify_pair_matches_device", "brisk_hip_refit_pair_models_device",
-    "brisk_hip_verify_pair_matches_epipolar_device",
+    "brisk_hip_verify_pair_matches_epipolar_device", "brisk_hip_refit_pair_models_epipolar_device",
     "brisk_hip_match_knn_pairs_guided_device", "brisk_hip_match_radius_pairs_guided_device",
     "brisk_hip_match_knn_pairs_epipolar_guided_device", "brisk_hip_match_radius_pairs_epipolar_guided_device",
     "brisk_hip_match_mutual_pairs_guided_device", "brisk_hip_match_mutual_pairs_epipolar_guided_device",
@@ -159,6 +159,13 @@ class PairRefit(C.Structure):
     _fields_ = [("max_error", C.c_float), ("rounds", C.c_int), ("min_inliers", C.c_int), ("keep_unverified", C.c_int)]
 
 
+class PairEpipolarRefit(C.Structure):
+    """brisk_hip_pair_epipolar_refit: max_error - the epipolar verifier's threshold, the Sampson distance in pixels; rounds (1 ... 8)
+    of fit and recount; a model needs min_inliers (>= 8) inliers; keep_unverified: as PairVerify; rank2: 0 = the least-squares F as
+    fitted, else its rank-2 projection"""
+    _fields_ = [("max_error", C.c_float), ("rounds", C.c_int), ("min_inliers", C.c_int), ("keep_unverified", C.c_int), ("rank2", C.c_int)]
+
+
 # brisk_hip_pair_model: the winner's normalised H and the pair's counts
 PAIR_MODEL = np.dtype([("h", "<f8", (9,)), ("records", "<i4"), ("usable", "<i4"), ("inliers", "<i4"), ("hypothesis", "<i4"),
                        ("valid", "<i4"), ("flags", "<i4")])
@@ -192,7 +199,7 @@ class HostTracks(C.Structure):
 # flags of a pair in the selected lists (ROWS_CUT: the pair and every pair behind it did not fit matches_cap)
 PAIR_ROWS_CUT, PAIR_BAD, PAIR_ENTRIES_CUT = 1, 2, 4
 PAIR_NO_MODEL = 8   # verify_pair_matches: the pair has no accepted model
-PAIR_REFIT = 0x10   # refit_pair_models: at least one round replaced the input model
+PAIR_REFIT = 0x10   # refit_pair_models / refit_pair_models_epipolar: at least one round replaced the input model
 
 
 def _host_array(n, dtype, pinned, keep):
@@ -383,6 +390,9 @@ def load_library():
     L.brisk_hip_refit_pair_models_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
                                                      C.POINTER(PairSpec), C.c_int, vp, vp, C.c_longlong, vp, C.POINTER(PairRefit),
                                                      C.c_longlong, vp, vp, vp, vp, vp, vp]
+    L.brisk_hip_refit_pair_models_epipolar_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
+                                                              C.POINTER(PairSpec), C.c_int, vp, vp, C.c_longlong, vp,
+                                                              C.POINTER(PairEpipolarRefit), C.c_longlong, vp, vp, vp, vp, vp, vp]
     L.brisk_hip_match_knn_pairs_guided_device.argtypes = [vp, C.POINTER(DescSet), C.POINTER(DescSet), C.POINTER(KpSet), C.POINTER(KpSet),
                                                           C.POINTER(PairSpec), vp, C.POINTER(MatchGuide), C.c_int, C.c_int, C.c_int,
                                                           vp, vp, vp, vp]
@@ -955,6 +965,19 @@ class Context:
         ptr = models.data_ptr() if hasattr(models, "data_ptr") else models
         return self._pair_models_call(self._L.brisk_hip_refit_pair_models_device, query, train, pairs, rows_cap, offsets, matches, refit,
                                       out_cap, query_kps, train_kps, stream, models=(C.c_void_p(int(ptr)) if ptr else None,))
+
+    # -- each pair's fundamental matrix fitted again to all its inliers, rank 2 enforced --
+    def refit_pair_models_epipolar(self, query, train, pairs, rows_cap, offsets, matches, models, refit, out_cap=None, query_kps=None,
+                                   train_kps=None, stream=None):
+        """brisk_hip_refit_pair_models_epipolar_device behind verify_pair_matches_epipolar: refit_pair_models for the epipolar branch.
+        offsets / matches: what the VERIFIER was given (the selection's output); models: the models tensor it returned ([npairs, 12]
+        int64, PAIR_EPIPOLAR_MODEL records) or a device pointer to npairs records; refit: a PairEpipolarRefit.  Returns (matches,
+        counts, flags, offsets, models) as verify_pair_matches_epipolar; a record with PAIR_REFIT in its flags holds the refitted F
+        (rank 2 if refit.rank2), any other still the verifier's.  The epipolar-guided matchers take the models in place.
+        Asynchronous on `stream`."""
+        ptr = models.data_ptr() if hasattr(models, "data_ptr") else models
+        return self._pair_models_call(self._L.brisk_hip_refit_pair_models_epipolar_device, query, train, pairs, rows_cap, offsets, matches,
+                                      refit, out_cap, query_kps, train_kps, stream, models=(C.c_void_p(int(ptr)) if ptr else None,))
 
     # -- a batch's pair matches linked into feature tracks --
     @staticmethod

@@ -2412,6 +2412,39 @@ int brisk_hip_refit_pair_models_device(brisk_hip_ctx* ctx, const brisk_hip_desc_
                         });
 }
 
+// ---- the pairs' fundamental matrices fitted again to all their inliers (kernel: k_refit_epipolar, brisk_pair_verify.hip; the rule:
+// brisk_pair_epipolar_refit.h).  The refit's checks with 8 in the place of 4, the verifier's scratch and packing
+static_assert(sizeof(brisk_hip_pair_epipolar_refit) == 20 && sizeof(BriskPairEpipolarRefit) == 20, "pair epipolar refit layout");
+
+int brisk_hip_refit_pair_models_epipolar_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                                const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                                const brisk_hip_pair_spec* pairs, int rows_cap, const long long* d_offsets,
+                                                const brisk_hip_dmatch* d_matches, long long in_cap,
+                                                const brisk_hip_pair_epipolar_model* d_models, const brisk_hip_pair_epipolar_refit* refit,
+                                                long long out_cap, brisk_hip_pair_epipolar_model* d_out_models, int* d_out_counts,
+                                                int* d_out_flags, long long* d_out_offsets, brisk_hip_dmatch* d_out_matches, void* stream) {
+  if (!ctx) return BRISK_HIP_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (!pairs || !refit) return fail(ctx, BRISK_HIP_ERR_ARG, "refit_pair_models_epipolar: null pairs or refit");
+  if (int rc = pair_lists_check_sizes(ctx, "refit_pair_models_epipolar", pairs->npairs, rows_cap, in_cap, out_cap)) return rc;
+  if (refit->rounds < 1 || refit->rounds > BRISK_REFIT_MAX_ROUNDS || refit->min_inliers < BRISK_EPIPOLAR_MIN_SAMPLE)
+    return fail(ctx, BRISK_HIP_ERR_ARG, "refit_pair_models_epipolar: rounds outside 1 ... 8, or min_inliers below 8");
+  if (((uintptr_t)d_models & 7) || (pairs->npairs > 0 && !d_models))
+    return fail(ctx, BRISK_HIP_ERR_ARG, "refit_pair_models_epipolar: d_models null or not 8-byte aligned");
+  if (int rc = pair_lists_check_arrays(ctx, "refit_pair_models_epipolar", query, train, query_kps, train_kps, pairs, d_offsets, d_matches, in_cap,
+                                       out_cap, d_out_models, d_out_counts, d_out_flags, d_out_offsets, d_out_matches))
+    return rc;
+  const BriskPairEpipolarRefit R{refit->max_error, refit->rounds, refit->min_inliers, refit->keep_unverified, refit->rank2};
+  return pair_lists_run(ctx, query, train, query_kps, train_kps, pairs, in_cap, d_out_offsets, stream,
+                        [&](const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK, const BriskPairSpec& P,
+                            unsigned char* keep, long long* kept, hipStream_t st) {
+                          brisk_launch_pair_epipolar_refit(Q, T, QK, TK, P, rows_cap, d_offsets, reinterpret_cast<const BriskDMatch*>(d_matches),
+                                                           in_cap, reinterpret_cast<const BriskPairEpipolarModel*>(d_models), R, keep, kept,
+                                                           out_cap, reinterpret_cast<BriskPairEpipolarModel*>(d_out_models), d_out_counts,
+                                                           d_out_flags, d_out_offsets, reinterpret_cast<BriskDMatch*>(d_out_matches), st);
+                        });
+}
+
 // ---- a batch's pair matches linked into feature tracks (kernels: brisk_track.hip) --------------------------------------------
 static_assert(sizeof(brisk_hip_track_seed) == 32 && sizeof(brisk_hip_track_obs) == 8 && BRISK_TRACK_LIST_CUT == BRISK_HIP_TRACKS_CUT,
               "track seed / observation layout");

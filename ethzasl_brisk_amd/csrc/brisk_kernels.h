@@ -10,6 +10,7 @@
 #include "brisk_pair_verify.h"
 #include "brisk_pair_refit.h"
 #include "brisk_pair_epipolar.h"
+#include "brisk_pair_epipolar_refit.h"
 #include "brisk_track_link.h"
 #include "brisk_track_points.h"
 
@@ -258,6 +259,13 @@ void brisk_launch_pair_refit(const BriskDescSet& Q, const BriskDescSet& T, const
                              int rows_cap, const long long* offsets, const BriskDMatch* matches, long long in_cap,
                              const BriskPairModel* in_models, const BriskPairRefit& R, unsigned char* keep, long long* kept, long long out_cap,
                              BriskPairModel* models, int* counts, int* flags, long long* out_offsets, BriskDMatch* out, hipStream_t s);
+// the same for the epipolar verifier's models (the rule: brisk_pair_epipolar_refit.h): F fitted again to all its inliers, rank 2
+// enforced if R.rank2
+void brisk_launch_pair_epipolar_refit(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
+                                      const BriskPairSpec& P, int rows_cap, const long long* offsets, const BriskDMatch* matches, long long in_cap,
+                                      const BriskPairEpipolarModel* in_models, const BriskPairEpipolarRefit& R, unsigned char* keep,
+                                      long long* kept, long long out_cap, BriskPairEpipolarModel* models, int* counts, int* flags,
+                                      long long* out_offsets, BriskDMatch* out, hipStream_t s);
 
 // ---- a batch's pair matches linked into feature tracks (brisk_track.hip; the rule: brisk_track_link.h) ----
 enum { BRISK_TRACK_C_LINKS = 0, BRISK_TRACK_C_LOST = 1, BRISK_TRACK_C_IGNORED = 2, BRISK_TRACK_COUNTERS = 4 };  // the link call's counters

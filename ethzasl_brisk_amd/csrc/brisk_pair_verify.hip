@@ -20,8 +20,11 @@
 //                     per pair, the same staging; lane = record scores the pair's model and adds the partials of the least-squares
 //                     sums, wave shuffles plus one LDS step combine them in the rule's order, one lane solves the 8 x 8 system in
 //                     LDS; then the keep bytes, the kept count and the model record.
-// The three share the record helpers (VfPair, vf_resolve, vf_stage), the record writer and the two kernels that pack the result;
-// k_verify_ransac and k_refit_models also the pair's resolution (vf_pair, vf_pair_frames), the reductions and the keep sweep, which
+//   k_refit_epipolar  brisk_hip_refit_pair_models_epipolar_device (the rule: brisk_pair_epipolar_refit.h): k_refit_models with the
+//                     fundamental matrix in the homography's place - the 44 sums of the 9 x 9 normal matrix in three sweeps of at
+//                     most 15 over the chunk in LDS, one lane solves the 9 x 9 system and the 3 x 3 one of the rank-2 step in LDS
+// The four share the record helpers (VfPair, vf_resolve, vf_stage), the record writer and the two kernels that pack the result;
+// k_verify_ransac and the two refits also the pair's resolution (vf_pair, vf_pair_frames), the reductions and the keep sweep, which
 // k_epipolar_ransac writes out for the reason given at that kernel:
 //   k_verify_offsets  one workgroup: exclusive prefix sums of the kept counts, counts / flags / offsets, the cut at out_cap (the
 //                     chunked scan and the cut of k_pair_select_offsets, brisk_match_export.hip)
@@ -700,6 +703,152 @@ __global__ void __launch_bounds__(VF_THREADS) k_epipolar_ransac(BriskDescSet Q, 
   }
 }
 
+// ---- the epipolar refit (brisk_pair_epipolar_refit.h) ----
+// one sweep of the normal matrix's sums: the terms K0 .. K0 + CNT - 1 of the pair's inliers under F, lane = record, combined in the
+// rule's order; lane 0 leaves them in W.s.  A lane carries CNT running sums, not 44: k_refit_models' 22 already take 252 VGPRs.  The
+// order inside each sum is the rule's, so the number of sweeps changes no bit
+template <int K0, int CNT>
+__device__ __forceinline__ void vf_epirefit_sweep(float4* __restrict__ pts, const BriskDMatch* __restrict__ matches, const VfPair& pr,
+                                                  const BriskFundamental& F, double thr2, const BriskRefitNorm& N,
+                                                  double (*red)[BRISK_EPIREFIT_SWEEP], BriskEpirefitWork& W, int lane, int wave) {
+  double s[CNT];
+#pragma unroll
+  for (int i = 0; i < CNT; ++i) s[i] = 0.0;
+  vf_each(pts, matches, pr, [&](const float4& r, int) {
+    const double x = (double)r.x, y = (double)r.y, xt = (double)r.z, yt = (double)r.w;
+    const bool in = brisk_epipolar_inlier(F, thr2, x, y, xt, yt);
+    double a[9], t[CNT];
+    brisk_epirefit_row(N, x, y, xt, yt, a);
+    brisk_epirefit_terms<K0, CNT>(a, t);
+#pragma unroll
+    for (int i = 0; i < CNT; ++i) s[i] = s[i] + (in ? t[i] : 0.0);
+  });
+  vf_block_sums(s, red, lane, wave);
+  if (threadIdx.x == 0)
+#pragma unroll
+    for (int i = 0; i < CNT; ++i) W.s[K0 + i] = s[i];
+}
+
+// k_refit_models with the fundamental matrix in the homography's place: one workgroup per pair, the same staging, lane = record for
+// the score and for the sums' partials, every lane carries the same model and count, so the round loop is uniform.  The 44 sums of
+// the 9 x 9 normal matrix are taken in three sweeps over the chunk that stays in LDS; lane 0 solves the 9 x 9 and the 3 x 3 system
+// in LDS (BriskEpirefitWork: every dynamic index goes there).  in_models may be models: every lane has read its pair's record
+// before the first barrier, lane 0 writes behind the last
+__global__ void __launch_bounds__(VF_THREADS) k_refit_epipolar(BriskDescSet Q, BriskDescSet T, BriskKpSet QK, BriskKpSet TK, BriskPairSpec P,
+                                                               int rows_cap, const long long* __restrict__ offsets,
+                                                               const BriskDMatch* __restrict__ matches, long long in_cap,
+                                                               const BriskPairEpipolarModel* in_models, BriskPairEpipolarRefit R,
+                                                               unsigned char* __restrict__ keep, long long* __restrict__ kept,
+                                                               BriskPairEpipolarModel* models) {
+  __shared__ float4 pts[VF_CHUNK];
+  __shared__ double red[VF_WAVES][BRISK_EPIREFIT_SWEEP];
+  __shared__ int ired[VF_WAVES][2];
+  __shared__ BriskEpirefitWork work;
+  __shared__ double fit[10];  // the fitted model; [9] != 0: the fit failed
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+  VfPair pr;
+  if (!vf_pair(Q, T, P, offsets, in_cap, kept, models, pr)) return;
+  vf_pair_frames(Q, T, QK, TK, rows_cap, pr);
+  const double thr2 = brisk_verify_thr2(R.max_error);
+
+  // the input record: one address for the whole workgroup
+  double fin[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) fin[i] = in_models[p].f[i];
+  const int in_hypothesis = in_models[p].hypothesis;
+  const bool has_model = brisk_refit_has_model(fin, in_hypothesis, in_models[p].flags, R.max_error);
+
+  if (pr.nchunks == 1) vf_stage(pts, matches, pr, 0);  // stays for every pass
+  __syncthreads();
+
+  BriskFundamental F{fin[0], fin[1], fin[2], fin[3], fin[4], fin[5], fin[6], fin[7], fin[8]};
+  int n = 0, replaced = 0;
+  if (has_model) {
+    int c[2] = {0, 0};
+    vf_each(pts, matches, pr, [&](const float4& r, int) {
+      c[0] += brisk_epipolar_inlier(F, thr2, (double)r.x, (double)r.y, (double)r.z, (double)r.w) ? 1 : 0;
+    });
+    vf_block_sums(c, ired, lane, wave);
+    n = c[0];
+    for (int round = 1; round <= R.rounds && n >= BRISK_EPIPOLAR_MIN_SAMPLE; ++round) {
+      BriskRefitNorm N;
+      double s4[4] = {0.0, 0.0, 0.0, 0.0};
+      vf_each(pts, matches, pr, [&](const float4& r, int) {
+        const double x = (double)r.x, y = (double)r.y, xt = (double)r.z, yt = (double)r.w;
+        const bool in = brisk_epipolar_inlier(F, thr2, x, y, xt, yt);
+        s4[0] = s4[0] + (in ? x : 0.0);
+        s4[1] = s4[1] + (in ? y : 0.0);
+        s4[2] = s4[2] + (in ? xt : 0.0);
+        s4[3] = s4[3] + (in ? yt : 0.0);
+      });
+      vf_block_sums(s4, red, lane, wave);
+      brisk_refit_centroids(s4, n, N);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) s4[i] = 0.0;
+      vf_each(pts, matches, pr, [&](const float4& r, int) {
+        const double x = (double)r.x, y = (double)r.y, xt = (double)r.z, yt = (double)r.w;
+        const bool in = brisk_epipolar_inlier(F, thr2, x, y, xt, yt);
+        double t[4];
+        brisk_refit_spread_terms(N, x, y, xt, yt, t);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s4[i] = s4[i] + (in ? t[i] : 0.0);
+      });
+      vf_block_sums(s4, red, lane, wave);
+      if (!brisk_refit_scales(s4, n, N)) break;
+      vf_epirefit_sweep<0, BRISK_EPIREFIT_SWEEP>(pts, matches, pr, F, thr2, N, red, work, lane, wave);
+      vf_epirefit_sweep<BRISK_EPIREFIT_SWEEP, BRISK_EPIREFIT_SWEEP>(pts, matches, pr, F, thr2, N, red, work, lane, wave);
+      vf_epirefit_sweep<2 * BRISK_EPIREFIT_SWEEP, BRISK_EPIREFIT_SUMS - 2 * BRISK_EPIREFIT_SWEEP>(pts, matches, pr, F, thr2, N, red, work, lane,
+                                                                                                 wave);
+      if (tid == 0) {  // the solve: one lane, in LDS (it wrote work.s itself)
+        BriskFundamental G;
+        int free_index;
+        const bool ok = brisk_epirefit_fit(n, N, R.rank2, work, G, free_index);
+        fit[0] = G.f0; fit[1] = G.f1; fit[2] = G.f2; fit[3] = G.f3; fit[4] = G.f4; fit[5] = G.f5; fit[6] = G.f6; fit[7] = G.f7; fit[8] = G.f8;
+        fit[9] = ok ? 0.0 : 1.0;
+      }
+      __syncthreads();
+      const BriskFundamental G{fit[0], fit[1], fit[2], fit[3], fit[4], fit[5], fit[6], fit[7], fit[8]};
+      const bool failed = fit[9] != 0.0;
+      __syncthreads();  // (fit is written again in the next round)
+      if (failed) break;
+      // the fitted model's score; d[1]: the records whose membership differs from the present set's
+      int d[2] = {0, 0};
+      vf_each(pts, matches, pr, [&](const float4& r, int) {
+        const double x = (double)r.x, y = (double)r.y, xt = (double)r.z, yt = (double)r.w;
+        const bool in = brisk_epipolar_inlier(F, thr2, x, y, xt, yt);
+        const bool in1 = brisk_epipolar_inlier(G, thr2, x, y, xt, yt);
+        d[0] += in1 ? 1 : 0;
+        d[1] += in1 != in ? 1 : 0;
+      });
+      vf_block_sums(d, ired, lane, wave);
+      if (!brisk_refit_replaces(d[0], n)) break;
+      F = G;
+      n = d[0];
+      ++replaced;
+      if (d[1] == 0) {  // a fixed point: every round left fits the same set again
+        replaced = R.rounds;
+        break;
+      }
+    }
+  }
+  const bool accepted = brisk_refit_accepted(has_model, n, R.min_inliers);
+
+  int e[2];  // kept, usable
+  vf_keep_sweep(pts, matches, pr, keep, ired, lane, wave, accepted, R.keep_unverified, e, [&](const float4& r) {
+    return brisk_epipolar_inlier(F, thr2, (double)r.x, (double)r.y, (double)r.z, (double)r.w);
+  });
+  if (tid == 0) {
+    kept[p] = e[0];
+    const double fout[9] = {F.f0, F.f1, F.f2, F.f3, F.f4, F.f5, F.f6, F.f7, F.f8};
+    double f[9];  // the input's nine doubles, byte for byte, when no round replaced them
+#pragma unroll
+    for (int i = 0; i < 9; ++i) f[i] = replaced > 0 ? fout[i] : fin[i];
+    vf_write_model(models + p, f, has_model, pr.m, e[1], n, has_model ? in_hypothesis : -1, replaced,
+                   (replaced > 0 ? BRISK_PAIR_REFIT : 0) | (accepted ? 0 : BRISK_PAIR_NO_MODEL));
+  }
+}
+
 // what the three calls end in: the kept counts -> counts, flags (the model records' too) and offsets, then the kept records packed
 static void vf_launch_pack(int np, const long long* offsets, const BriskDMatch* matches, long long in_cap, const unsigned char* keep,
                            long long* kept, long long out_cap, BriskPairModel* models, int* counts, int* flags, long long* out_offsets,
@@ -725,6 +874,17 @@ void brisk_launch_pair_refit(const BriskDescSet& Q, const BriskDescSet& T, const
   hipLaunchKernelGGL(k_refit_models, dim3(P.npairs), dim3(VF_THREADS), 0, s, Q, T, QK, TK, P, rows_cap, offsets, matches, in_cap, in_models, R,
                      keep, kept, models);
   vf_launch_pack(P.npairs, offsets, matches, in_cap, keep, kept, out_cap, models, counts, flags, out_offsets, out, s);
+}
+
+void brisk_launch_pair_epipolar_refit(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK,
+                                      const BriskPairSpec& P, int rows_cap, const long long* offsets, const BriskDMatch* matches, long long in_cap,
+                                      const BriskPairEpipolarModel* in_models, const BriskPairEpipolarRefit& R, unsigned char* keep,
+                                      long long* kept, long long out_cap, BriskPairEpipolarModel* models, int* counts, int* flags,
+                                      long long* out_offsets, BriskDMatch* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_refit_epipolar, dim3(P.npairs), dim3(VF_THREADS), 0, s, Q, T, QK, TK, P, rows_cap, offsets, matches, in_cap, in_models,
+                     R, keep, kept, models);
+  vf_launch_pack(P.npairs, offsets, matches, in_cap, keep, kept, out_cap, reinterpret_cast<BriskPairModel*>(models), counts, flags, out_offsets,
+                 out, s);
 }
 
 void brisk_launch_pair_epipolar(const BriskDescSet& Q, const BriskDescSet& T, const BriskKpSet& QK, const BriskKpSet& TK, const BriskPairSpec& P,

@@ -598,7 +598,8 @@ int brisk_hip_pair_matches_wait(brisk_hip_ctx* ctx, unsigned ticket, int* pairs_
  * keep_unverified != 0, else nothing.  A pair whose d_pairs entry lies outside its sets, or whose offsets are no range inside
  * [0, in_cap] (or span 2^31 records or more), is BAD: nothing of it is read or kept.
  * Not done here: essential matrices, adaptive stopping.  The refit of the model to all its inliers is a call of its own,
- * brisk_hip_refit_pair_models_device below; scenes that are no plane have brisk_hip_verify_pair_matches_epipolar_device further below. */
+ * brisk_hip_refit_pair_models_device below; scenes that are no plane have brisk_hip_verify_pair_matches_epipolar_device and its own
+ * refit, brisk_hip_refit_pair_models_epipolar_device, further below. */
 typedef struct brisk_hip_pair_verify {
   float max_error;     /* pixels, in the train frame */
   int hypotheses;      /* 1 ... 4096 */
@@ -719,9 +720,10 @@ int brisk_hip_refit_pair_models_device(brisk_hip_ctx* ctx, const brisk_hip_desc_
  * F is the linear eight-point solution and in general has no epipoles; it is not meant for rectification or for recovering a pose.
  * Eight coplanar points (and a scene that is a plane) give a degenerate system; its null vector still vanishes on the plane's
  * records, so the plane is kept - with more random records beside it than a proper F lets through.
- * Not done here: essential matrices (no intrinsics enter), the refit of F to all its inliers, seven- or five-point samples, adaptive
- * stopping.  The second pass - guided matching along epipolar lines - reads these models in place: "a batch's pairs matched again
- * inside a band around each epipolar line" below. */
+ * Not done here: essential matrices (no intrinsics enter), seven- or five-point samples, adaptive stopping; the refit of F to all its
+ * inliers, with rank 2 enforced, is a call of its own, brisk_hip_refit_pair_models_epipolar_device below.  The second pass -
+ * guided matching along epipolar lines - reads these models, or the refitted ones, in place: "a batch's pairs matched again inside a
+ * band around each epipolar line" below. */
 typedef struct brisk_hip_pair_epipolar_model { /* 96 bytes, 8-byte aligned.  A type of its own ON PURPOSE: brisk_hip_refit_pair_models_device
                                                   and the guided matchers read a brisk_hip_pair_model as a homography and must not be
                                                   handed an F */
@@ -760,6 +762,56 @@ int brisk_hip_verify_pair_matches_epipolar_device(brisk_hip_ctx* ctx, const bris
                                                   const brisk_hip_dmatch* d_matches, long long in_cap, const brisk_hip_pair_verify* verify,
                                                   long long out_cap, brisk_hip_pair_epipolar_model* d_models, int* d_out_counts,
                                                   int* d_out_flags, long long* d_out_offsets, brisk_hip_dmatch* d_out_matches, void* stream);
+
+/* ---- each pair's fundamental matrix fitted again to all its inliers, rank 2 enforced, on the device ------------------------------
+ * The epipolar verifier reports the linear solution of eight noisy keypoints: exact for its sample and nothing more, and without
+ * epipoles.  The band of the epipolar-guided matchers is drawn around the lines of that F.  This call stands where
+ * brisk_hip_refit_pair_models_device stands in the homography branch (select -> verify_epipolar -> refit_epipolar -> epipolar-guided
+ * matchers / linker / exits): it fits every pair's F again to ALL its inliers by least squares, optionally projects the result to
+ * rank 2, and counts the inliers again, for `rounds` rounds.  It reads the lists the VERIFIER read, so a kept list can grow.
+ * csrc/brisk_pair_epipolar_refit.h is the one definition of the rule; all of its arithmetic is IEEE fp64 + - x / in a fixed order, no
+ * square root and no eigen-solver, so models and kept lists are reproducible bit for bit.
+ * Pairs, records, USABLE records and BAD pairs are the verifier's.
+ * THE INPUT MODEL: the test of brisk_hip_refit_pair_models_device, on f, hypothesis and flags of d_models[p].  A pair without one is
+ * treated as that call treats it: BRISK_HIP_PAIR_NO_MODEL, nine zeros, hypothesis -1, inliers 0, valid 0.
+ * THE SCORE of a model F: the epipolar verifier's Sampson test, Sampson distance <= max_error pixels; no sign enters.
+ * THE FIT to an inlier set of n >= 8 records: both sides are normalised as in brisk_hip_refit_pair_models_device; the symmetric
+ * 9 x 9 normal matrix of the rows [U X, U Y, U, V X, V Y, V, X, Y, 1] is summed in that call's fixed order and eliminated with
+ * DIAGONAL pivoting: the element of F that is held at 1 is the one whose index is left last, chosen by the data, so rectified stereo
+ * (the last element of F is 0) is no special case.  With rank2 != 0 the normalised solution Fn is projected to rank 2: N = Fn^T Fn,
+ * the same pivoted elimination on this 3 x 3 gives e, and Fn' = Fn - (Fn e) e^T / (e . e), so Fn' e = 0: e is the epipole in the query
+ * frame, and Fn' is the SVD truncation up to the error of one step of inverse iteration.  The result is denormalised and divided by
+ * its element of largest magnitude.  The fit FAILS if a side has no extent, a pivot is not > 0 and finite (inliers on one
+ * axis-parallel line, at one point), e . e is not finite and > 0, or an element of the result is not finite.
+ * THE ROUNDS, ACCEPTED and KEPT: those of brisk_hip_refit_pair_models_device with 8 in the place of 4; the count never falls.
+ * THE OUTPUT RECORD: f = the final model - the input record's nine doubles, byte for byte, when no round replaced it -, records and
+ * usable as the verifier writes them, inliers = the final count, hypothesis = the input's, valid = the number of rounds that
+ * replaced the model, flags = BRISK_HIP_PAIR_REFIT iff that number is > 0, plus BRISK_HIP_PAIR_NO_MODEL if not accepted (and
+ * BRISK_HIP_ROWS_CUT as for the verifier).  A model that no round replaced is still the verifier's F, rank 2 NOT enforced, and its
+ * record does not carry BRISK_HIP_PAIR_REFIT: the flag is how a caller knows that the record holds a refitted F, and a rank-2 one
+ * if it asked for that.  The epipolar-guided matchers read f, hypothesis and flags only: they take these records in place. */
+typedef struct brisk_hip_pair_epipolar_refit {
+  float max_error;     /* Sampson distance in pixels: the epipolar verifier's threshold */
+  int rounds;          /* 1 ... 8 */
+  int min_inliers;     /* >= 8 */
+  int keep_unverified; /* pairs without an accepted model: as brisk_hip_pair_verify */
+  int rank2;           /* 0: the least-squares F as fitted; else its rank-2 projection */
+} brisk_hip_pair_epipolar_refit;
+/* The arguments, the outputs, the cut at out_cap and the BAD-pair rules are brisk_hip_refit_pair_models_device's, one for one, with
+ * brisk_hip_pair_epipolar_model records: d_offsets / d_matches / in_cap are what the epipolar VERIFIER was given for these pairs,
+ * d_models [npairs] the models it wrote (DEVICE memory, 8-byte aligned); d_out_models may be the same array as d_models (a pair's
+ * record is read before it is written); no other overlap is allowed.
+ * Asynchronous on `stream`, no host synchronisation, no allocation once the context's scratch has the verifier's size for this in_cap
+ * and npairs (it is the same scratch).  Ordered behind the context's previous call and in front of its next, like every call.
+ * BRISK_HIP_ERR_ARG, before anything is launched: the errors of brisk_hip_refit_pair_models_device with min_inliers < 8 in the place
+ * of < 4; rounds outside 1 ... 8.  npairs == 0: BRISK_HIP_OK, d_out_offsets[0] = 0. */
+int brisk_hip_refit_pair_models_epipolar_device(brisk_hip_ctx* ctx, const brisk_hip_desc_set* query, const brisk_hip_desc_set* train,
+                                                const brisk_hip_kp_set* query_kps, const brisk_hip_kp_set* train_kps,
+                                                const brisk_hip_pair_spec* pairs, int rows_cap, const long long* d_offsets,
+                                                const brisk_hip_dmatch* d_matches, long long in_cap,
+                                                const brisk_hip_pair_epipolar_model* d_models, const brisk_hip_pair_epipolar_refit* refit,
+                                                long long out_cap, brisk_hip_pair_epipolar_model* d_out_models, int* d_out_counts,
+                                                int* d_out_flags, long long* d_out_offsets, brisk_hip_dmatch* d_out_matches, void* stream);
 
 /* ---- a batch's pairs matched again inside a window around each pair's model ----------------------------------------------------
  * What reaches the linker after the verification is the part of the first pass that survived the descriptor test (Lowe's ratio

@@ -68,6 +68,14 @@ frames are unrelated, so no pair there has a model (as with --guided): the call'
 (as many pairs, 1 024 points a frame seen through mild homographies with 0.5 px noise, --related-records 200 records a pair, three
 quarters of them true), whose result is compared with the restated rule.  --refit --stats-pass runs the related batch only, so
 that a `rocprofv3 --kernel-trace --stats` pass around it gives k_refit_models on pairs that have models.
+With --epirefit (profiles/epipolar_refit_pairs.json) the refit of the epipolar branch beside its yardstick, two windows of back-to-back
+calls on --refit's related batch (--batch - 1 pairs, the same lists, the same --rounds, one process; no frame is detected):
+  H  brisk_hip_refit_pair_models_device on the homography verifier's models            (the yardstick)
+  F  brisk_hip_refit_pair_models_epipolar_device (--rank2 1) on the epipolar verifier's models
+plus F / H of the windows' medians and of the HIP-event times of one call each, the rounds that replaced a model in either, and
+whether F's arrays equal the restated rule (tests/test_abi_epipolar_refit.py).  The related batch is a PLANE seen through homographies:
+both verifiers find models on it.  --epirefit --stats-pass runs ten calls of each, for a `rocprofv3 --kernel-trace --stats` pass:
+k_refit_epipolar beside k_refit_models (profiles/epipolar_refit_pairs_kernel_stats.csv).
 With --epiguided (k-NN only, profiles/epiguided_pairs.json) the second pass of the epipolar branch, two windows:
   E  --epipolar's E
   L  E followed by brisk_hip_match_knn_pairs_epipolar_guided_device (k = 1, band = --max-error, window +-64 px, octave difference 1,
@@ -541,6 +549,129 @@ def related_batch(dev, npairs, rows, per_pair, noise, seed=2024):
     d_rec = torch.from_numpy(rec.view(np.int32).reshape(-1, 4).copy()).to(dev)
     return (B.DescSet(None, d_counts.data_ptr(), 1, 0, 0, nf), B.KpSet(d_kps.data_ptr(), rows * 28), d_off, d_rec, (d_counts, d_kps),
             [np.stack([kps["x"][f], kps["y"][f]], axis=1) for f in range(nf)], rec.reshape(-1))
+
+
+def epirefit_mode(a, dev):
+    """--epirefit: windows H and F (see the module's text); writes a.out"""
+    from test_abi_epipolar_refit import restated_epipolar_refit
+    ctx = B.Context(0)
+    work = torch.cuda.Stream(device=dev)
+    torch.cuda.set_stream(work)
+    st = work.cuda_stream
+    L, h = ctx._L, ctx._h
+    min_inl = max(a.min_inliers, 8)
+    verify = B.PairVerify(a.max_error, a.hypotheses, min_inl, 1, 2024)
+    refit_h = B.PairRefit(a.max_error, a.rounds, min_inl, 1)
+    refit_f = B.PairEpipolarRefit(a.max_error, a.rounds, min_inl, 1, a.rank2)
+    rp, rrows, rper = a.batch - 1, 1024, a.related_records
+    rset, rkps, roff, rrec, keep_alive, rxy, rhost = related_batch(dev, rp, rrows, rper, 0.5)
+    rspec = B.PairSpec(rp, 1, 1, 0, 1, None)
+    rcap = rp * rper
+
+    def arrays():
+        return (torch.zeros((rcap, 4), dtype=torch.int32, device=dev), torch.zeros(rp, dtype=torch.int32, device=dev),
+                torch.zeros(rp, dtype=torch.int32, device=dev), torch.zeros(rp + 1, dtype=torch.int64, device=dev),
+                torch.zeros((rp, 12), dtype=torch.int64, device=dev))
+
+    ver = {"H": arrays(), "F": arrays()}
+    out = {"H": arrays(), "F": arrays()}
+    entry = {"H": (L.brisk_hip_verify_pair_matches_device, L.brisk_hip_refit_pair_models_device, refit_h),
+             "F": (L.brisk_hip_verify_pair_matches_epipolar_device, L.brisk_hip_refit_pair_models_epipolar_device, refit_f)}
+    for v in "HF":                                                  # the input models of either call: written once, read by every call
+        ctx.check(entry[v][0](h, C.byref(rset), C.byref(rset), C.byref(rkps), C.byref(rkps), C.byref(rspec), rrows, roff.data_ptr(),
+                              rrec.data_ptr(), rcap, C.byref(verify), rcap, ver[v][4].data_ptr(), ver[v][1].data_ptr(), ver[v][2].data_ptr(),
+                              ver[v][3].data_ptr(), ver[v][0].data_ptr(), st))
+
+    def call(v):
+        o = out[v]
+        ctx.check(entry[v][1](h, C.byref(rset), C.byref(rset), C.byref(rkps), C.byref(rkps), C.byref(rspec), rrows, roff.data_ptr(),
+                              rrec.data_ptr(), rcap, ver[v][4].data_ptr(), C.byref(entry[v][2]), rcap, o[4].data_ptr(), o[1].data_ptr(),
+                              o[2].data_ptr(), o[3].data_ptr(), o[0].data_ptr(), st))
+
+    order = "HF"
+    for v in order + order:                                         # warm-up: the scratch grown
+        call(v)
+    torch.cuda.synchronize()
+    if a.stats_pass:
+        for _ in range(10):
+            for v in order:
+                call(v)
+        torch.cuda.synchronize()
+        ctx.close()
+        return
+    # F against the restatement of the rule
+    fm = ver["F"][4].cpu().numpy().reshape(-1).view(B.PAIR_EPIPOLAR_MODEL).copy()
+    hm = ver["H"][4].cpu().numpy().reshape(-1).view(B.PAIR_MODEL).copy()
+    counts_r = [rrows] * (rp + 1)
+    want = restated_epipolar_refit([(p + 1, p) for p in range(rp)], counts_r, counts_r, rrows, rxy, rxy, roff.cpu().numpy(), rhost, fm,
+                                   (a.max_error, a.rounds, min_inl, 1, a.rank2), rcap, rcap)
+    o = out["F"]
+    stored = int(want[3][-1])
+    identical = bool(o[4].cpu().numpy().reshape(-1).view(B.PAIR_EPIPOLAR_MODEL).tobytes() == want[0].tobytes() and
+                     o[1].cpu().numpy().tobytes() == want[1].tobytes() and o[2].cpu().numpy().tobytes() == want[2].tobytes() and
+                     o[3].cpu().numpy().tobytes() == want[3].tobytes() and o[0].cpu().numpy()[:stored].tobytes() == want[4].tobytes())
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    event_ms = {v: [] for v in order}
+    for _ in range(max(a.repeats, 5)):
+        for v in order:
+            ev[0].record(work)
+            call(v)
+            ev[1].record(work)
+            torch.cuda.synchronize()
+            event_ms[v].append(ev[0].elapsed_time(ev[1]))
+    ms = {v: [] for v in order}
+    for _ in range(a.repeats):
+        for v in order:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            calls = 0
+            while True:
+                call(v)
+                calls += 1
+                if calls % 8 == 0:
+                    torch.cuda.synchronize()
+                    if time.perf_counter() - t0 >= a.window:
+                        break
+            torch.cuda.synchronize()
+            ms[v].append(1e3 * (time.perf_counter() - t0) / calls)
+    med = {v: float(np.median(ms[v])) for v in order}
+    emed = {v: float(np.median(event_ms[v])) for v in order}
+    spread = {v: (max(ms[v]) - min(ms[v])) / med[v] for v in order}
+    hr = out["H"][4].cpu().numpy().reshape(-1).view(B.PAIR_MODEL)
+    fr = want[0]
+    has_h, has_f = (hm["flags"] & B.PAIR_NO_MODEL) == 0, (fm["flags"] & B.PAIR_NO_MODEL) == 0
+
+    def side(vm, rm, has):
+        return {"pairs_with_an_input_model": int(has.sum()), "pairs_refitted": int(((rm["flags"] & B.PAIR_REFIT) != 0).sum()),
+                "inliers_per_model_mean_verifier": round(float(vm["inliers"][has].mean()), 2) if has.any() else 0.0,
+                "inliers_per_model_mean_refit": round(float(rm["inliers"][has].mean()), 2) if has.any() else 0.0,
+                "rounds_that_replaced_mean": round(float(rm["valid"][has].mean()), 2) if has.any() else 0.0}
+
+    res = {
+        "workload": "a related batch: %d pairs, %d points a frame on a plane seen through mild homographies with 0.5 px noise, %d records a pair, "
+                    "three quarters of them true; both verifiers: %d hypotheses, max_error %g, min_inliers %d, keep_unverified 1; both refits: "
+                    "%d rounds, rank2 %d, the same lists, one process" % (rp, rrows, rper, a.hypotheses, a.max_error, min_inl, a.rounds, a.rank2),
+        "kernel_revision": ctx.kernel_revision(),
+        "device": torch.cuda.get_device_name(0),
+        "windows": {"repeats": a.repeats, "seconds_each": a.window,
+                    "order": ", ".join(order) + " alternating; a window is back-to-back calls of ONE kind, synchronised every 8 calls and at its end"},
+        "ms_per_call": {v: round(med[v], 4) for v in order},
+        "ms_per_call_all": {v: [round(x, 4) for x in ms[v]] for v in order},
+        "spread_rel": {v: round(spread[v], 4) for v in order},
+        "F_over_H_ms_per_call": round(med["F"] / med["H"], 4),
+        "hip_event_ms": {v: {"median": round(emed[v], 4), "all": [round(x, 4) for x in event_ms[v]]} for v in order},
+        "F_over_H_hip_event_ms": round(emed["F"] / emed["H"], 4),
+        "related_batch": {"pairs": rp, "rows_per_frame": rrows, "records_per_pair": rper, "true_share": 0.75, "noise_px": 0.5,
+                          "H": side(hm, hr, has_h), "F": side(fm, fr, has_f), "F_equals_the_restated_rule": identical},
+        "legend": {"H": "brisk_hip_refit_pair_models_device on the homography verifier's models (three launches): the yardstick",
+                   "F": "brisk_hip_refit_pair_models_epipolar_device on the epipolar verifier's models (three launches)"},
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+    ctx.close()
 
 
 def refit_mode(a, ctx, ext, n, nd, k, cap, dev, work, outs, run_b0):
@@ -1351,7 +1482,10 @@ def main():
                          "band 3 under an all-pass window beside the ungated kernel (one rocprofv3 run each: the stats merge a kernel's launches)")
     ap.add_argument("--refit", action="store_true",
                     help="windows V (--verify's V) and R (V with refit_pair_models between verify and link), and the call on a related batch")
-    ap.add_argument("--rounds", type=int, default=2, help="--refit: rounds of fit and recount")
+    ap.add_argument("--epirefit", action="store_true",
+                    help="windows H (refit_pair_models) and F (refit_pair_models_epipolar) of back-to-back calls on the related batch")
+    ap.add_argument("--rank2", type=int, default=1, help="--epirefit: 0 = the least-squares F as fitted, else its rank-2 projection")
+    ap.add_argument("--rounds", type=int, default=2, help="--refit / --epirefit: rounds of fit and recount")
     ap.add_argument("--related-records", type=int, default=200, help="--refit: records per pair of the related batch")
     ap.add_argument("--hypotheses", type=int, default=256, help="--verify: hypotheses per pair")
     ap.add_argument("--max-error", type=float, default=3.0, help="--verify: the inlier threshold in pixels")
@@ -1410,6 +1544,11 @@ def main():
             ap.error("--refit measures the k-NN pair call: without --radius / --gate / --export / --tracks / --tracks-download / --verify / --guided")
         if a.out is None:
             a.out = os.path.join(ROOT, "profiles", "refit_pairs.json")
+    if a.epirefit:
+        if radius is not None or gate or a.export or a.tracks or a.tracks_download or a.verify or a.guided or a.refit or a.epipolar or a.epiguided:
+            ap.error("--epirefit times the two refit calls on the related batch: without any other mode")
+        if a.out is None:
+            a.out = os.path.join(ROOT, "profiles", "epipolar_refit_pairs.json")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", ("match_radius_pairs" if radius is not None else "match_pairs") +
                              ("_gated" if gate else "") + ".json")
@@ -1417,6 +1556,9 @@ def main():
     LIST = 32                                  # MRP_LIST of brisk_match.hip: rows with more hits take the dense path
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
+    if a.epirefit:                             # (no frame is detected: the related batch is made on the host)
+        epirefit_mode(a, dev)
+        return
     nd = min(a.distinct, n)
     ring = torch.from_numpy(np.stack(gen_frames(synth.frame_1080p, list(range(nd))))).to(dev)
     frames = ring[torch.arange(n, device=dev) % nd].contiguous()
