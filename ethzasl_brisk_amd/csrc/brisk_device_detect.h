@@ -1744,6 +1744,86 @@ BRISK_HD unsigned brisk_state_static(const BriskLayerView& L, const bool float_p
   return (unsigned)Kp | ((unsigned)t_last << 8) | ((unsigned)last_static << 16) | (cached ? 1u << 22 : 0u) | (any ? 1u << 23 : 0u);
 }
 
+// brisk_state_static as a loop over the candidates of the tie's window instead of over the pixel's 24 neighbours.  A
+// neighbour q acts on the pixel only if it is a candidate itself (BRISK_SM_D != 0) and not later in raster order than the
+// tie, i.e. one of entries 0 ... 40 of the 9 x 9 window centred on the tie (entry 40 = the tie): at threshold 80 that is 3
+// entries on average where the unrolled form runs 24 iterations.
+// sm_local: the window, BRISK_TIE_WIN wide, origin (cx - 4, cy - 4).  list: bit e set = entry e (e <= 40) has D != 0.  The
+// entry's value is the same for every pixel of the tie - in the tie kernel a scalar: lane e's window register v0, read by
+// lane index; on the host sm_local[e].  So everything that depends on the entry alone is worked out once per entry as sets
+// of neighbour indices i = (oy + 2) * 5 + ox + 2, (ox, oy) = q - p: the neighbours whose probe of p the entry has issued
+// (its probe count), the ones its touch reaches (E5, the touch geometry), whether that touch is decided.  The pixel's part
+// is its own bit 1 << i, if q is one of its 24 neighbours at all, and a test of that bit against the sets.
+// For a fixed pixel ascending entry order is ascending i, so the events come in the order of the unrolled loop and `packed`
+// and `*dynmask` are bit-identical to brisk_state_static's.  No branch depends on the pixel: the tie kernel calls this with
+// all lanes (a lane without a slot passes the centre).
+#define BRISK_TIE_WIN 9
+#define BRISK_TIE_WIN_SELF (4 * BRISK_TIE_WIN + 4)
+// longest list the tie kernel runs in this form (longer ones take the unrolled form)
+#ifndef BRISK_TIE_LIST_CAP  // (A / B builds: -DBRISK_TIE_LIST_CAP=n)
+#define BRISK_TIE_LIST_CAP 6
+#endif
+#if defined(__HIP_DEVICE_COMPILE__)
+#define BRISK_TIE_WIN_ENTRY(sm_local_, v0_, e_) ((unsigned)__builtin_amdgcn_readlane((int)(v0_), (e_)))
+#else
+#define BRISK_TIE_WIN_ENTRY(sm_local_, v0_, e_) ((unsigned)(sm_local_)[(e_)])
+#endif
+// sets of neighbour indices (bit 12, the pixel itself, in none): |ox|, |oy| <= 1; p - q in [0, 1]^2 (the 2 x 2 footprint of a
+// pass); p - q in [-1, 2]^2 (the 4 x 4 patch of the e5 access)
+#define BRISK_NB_NEAR 0x729C0u
+#define BRISK_NB_2X2 0x8C0u
+#define BRISK_NB_4X4 0x7ADEFu
+// neighbours whose probe of p is among q's first n: probe k of q lands on p = q + (brisk_probe_dx(k), brisk_probe_dy(k)), i.e.
+// i = 13, 11, 17, 7, 8, 6, 16, 18 for k = 0 ... 7.  Bits 6 ... 18 of the set for n = 0 ... 3 and 4 ... 7, 13 bits each
+// (n >= 8: BRISK_NB_NEAR)
+#define BRISK_NB_PROBED_LO (0x0ull | (0x80ull << 13) | (0xA0ull << 26) | (0x8A0ull << 39))
+#define BRISK_NB_PROBED_HI (0x8A2ull | (0x8A6ull << 13) | (0x8A7ull << 26) | (0xCA7ull << 39))
+BRISK_HD unsigned brisk_state_static_list(const BriskLayerView& L, const bool float_patch, const bool pass_touch2x2, int px,
+                                          int py, int cx, int cy, bool own, const uint16_t* sm_local, const uint8_t* kp5,
+                                          unsigned long long list, unsigned v0, unsigned* dynmask) {
+  (void)v0;
+  const int wx = px - cx + 4, wy = py - cy + 4;  // the pixel inside the window
+  const unsigned smp = sm_local[wy * BRISK_TIE_WIN + wx];
+  const int D = BRISK_SM_D(smp);
+  const int Kp = (int)kp5[(wy - 2) * 5 + (wx - 2)];
+  bool cached = (smp & BRISK_SM_TOUCH) != 0, any = cached;
+  int t_last = cached ? 1 : 0;
+  int last_static = 0;  // index + 1 of the last static event
+  unsigned dyn = 0;     // (bit i + 1 in here: the pixel's bit is 1 << (i + 1), which is what last_static takes)
+  const int wx2 = wx - 2, wy2 = wy - 2, w5 = wy2 * 5 + wx2 - 1;
+  const unsigned ownbits = own ? ~0u : 0u;
+  for (unsigned long long m = list; m; m &= m - 1) {
+    // the entry's part
+    const int e = __builtin_ctzll(m);
+    const unsigned smq = BRISK_TIE_WIN_ENTRY(sm_local, v0, e);
+    const int Dq = BRISK_SM_D(smq);
+    const int ey = e / BRISK_TIE_WIN, ex = e - ey * BRISK_TIE_WIN;
+    const bool self = e == BRISK_TIE_WIN_SELF;
+    const unsigned np = BRISK_SM_NPROBED(smq);
+    const unsigned probed = np >= 8 ? BRISK_NB_NEAR << 1 : (unsigned)(((np < 4 ? BRISK_NB_PROBED_LO : BRISK_NB_PROBED_HI) >> (13 * (np & 3))) & 0x1FFFu) << 7;
+    const bool e5 = (smq & BRISK_SM_E5) != 0;
+    const unsigned touch = self ? 0u : !float_patch ? (e5 ? BRISK_NB_NEAR << 1 : 0u) : ((pass_touch2x2 ? BRISK_NB_2X2 << 1 : 0u) | (e5 ? BRISK_NB_4X4 << 1 : 0u));
+    const unsigned stq = BRISK_SM_STATUS(smq);
+    const unsigned touch_pass = (stq == BRISK_ST_PASS) ? touch : 0u, touch_tie = (stq == BRISK_ST_TIE) ? touch : 0u;
+    // the pixel's part: q as a neighbour of p (the tie itself acts on the pixels that see its own probes done)
+    const unsigned ox2 = (unsigned)(ex - wx2), oy2 = (unsigned)(ey - wy2);
+    const int i1 = ey * 5 + ex - w5;  // i + 1
+    unsigned bit = (ox2 <= 4u && oy2 <= 4u) ? 1u << (i1 & 31) : 0u;
+    bit &= self ? ownbits : ~0u;
+    const bool pr = (bit & probed) != 0, tc = (bit & touch_pass) != 0;
+    any = any || pr || tc;
+    cached = cached || (pr && Dq <= Kp) || tc;
+    t_last = tc ? 1 : pr ? Dq : t_last;  // (a neighbour's probe event precedes its touch event)
+    last_static = (pr || tc) ? i1 : last_static;
+    dyn |= bit & touch_tie;
+  }
+  if (brisk_border3(L, px, py)) { *dynmask = 0; return BRISK_SS_FINAL; }
+  if (D > 2) { *dynmask = 0; return BRISK_SS_FINAL | (unsigned)D; }
+  if (Kp == 0) { *dynmask = 0; return BRISK_SS_FINAL; }
+  *dynmask = dyn >> 1;
+  return (unsigned)Kp | ((unsigned)t_last << 8) | ((unsigned)last_static << 16) | (cached ? 1u << 22 : 0u) | (any ? 1u << 23 : 0u);
+}
+
 // sm_local now carries the decided statuses of the neighbours listed in dynmask
 BRISK_HD int brisk_state_resolve(unsigned packed, unsigned dynmask, int px, int py, const uint16_t* sm_local, int lx0,
                                  int ly0, int lw) {
@@ -1794,6 +1874,21 @@ BRISK_HD unsigned brisk_tie_slot_static_m(const BriskLayerView& L, const bool fl
   *dynmask = 0;
   if (slot >= 8 && sx == 0 && sy == 0) return BRISK_SS_FINAL;  // (the centre: the caller substitutes it)
   return brisk_state_static_m(L, float_patch, pass_touch2x2, cx + sx, cy + sy, cx, cy, actmask, nselfmask, sm_local, lx0, ly0, lw, kp5, dynmask);
+}
+// the static step of slot 0..32 over the window's candidate list (brisk_state_static_list); slot < 0: a lane without a slot
+// runs the loop on the centre and gets "final"
+BRISK_HD unsigned brisk_tie_slot_static_list(const BriskLayerView& L, const bool float_patch, const bool pass_touch2x2, int cx,
+                                             int cy, int slot, const uint16_t* sm_local, const uint8_t* kp5,
+                                             unsigned long long list, unsigned v0, unsigned* dynmask) {
+  int sx = 0, sy = 0;
+  bool own = true;
+  if (slot >= 0) brisk_tie_slot_offset(slot, &sx, &sy, &own);
+  const unsigned packed = brisk_state_static_list(L, float_patch, pass_touch2x2, cx + sx, cy + sy, cx, cy, own, sm_local, kp5, list, v0, dynmask);
+  if (slot < 0 || (slot >= 8 && sx == 0 && sy == 0)) {  // (the centre: the caller substitutes it)
+    *dynmask = 0;
+    return BRISK_SS_FINAL;
+  }
+  return packed;
 }
 BRISK_HD int brisk_tie_slot_resolve(const BriskLayerView& L, unsigned packed, unsigned dynmask, int cx, int cy, int centre,
                                     int slot, const uint16_t* sm_local, int lx0, int ly0, int lw, const uint8_t* kp5) {

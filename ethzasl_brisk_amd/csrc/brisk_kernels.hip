@@ -1263,17 +1263,21 @@ __global__ void __launch_bounds__(64) k_compute_scale(BriskGeom G, uint8_t* pyr,
 // k_tie_resolve_small (fewer than 32 frames: nothing competes for the CUs) runs the static step of the cache replay with
 // the lane's precomputed act / not-self masks (brisk_state_masks; TR_KERNEL_MASKS): 13 % fewer instructions per tie, 98
 // VGPRs; one 640 x 480 frame: detect 294 -> 281 us, 1080p 415 -> 386 us.
+static_assert(TR_WIN == BRISK_TIE_WIN, "brisk_state_static_list walks the tie kernel's window");
 #define TR_KERNEL_NAME k_tie_resolve
 #define TR_SORT_NAME tie_sort_large
 #define TR_KERNEL_MASKS 0
 #define TR_KERNEL_PAIR 0
+#define TR_KERNEL_LIST 1
 #include "brisk_tie_kernel.inc"
 #undef TR_KERNEL_NAME
 #undef TR_KERNEL_MASKS
+#undef TR_KERNEL_LIST
 #undef TR_SORT_NAME
 #define TR_KERNEL_NAME k_tie_resolve_small
 #define TR_SORT_NAME tie_sort_large_small
 #define TR_KERNEL_MASKS 1
+#define TR_KERNEL_LIST 0
 #include "brisk_tie_kernel.inc"
 #undef TR_KERNEL_NAME
 #undef TR_SORT_NAME

@@ -709,7 +709,14 @@ __global__ void __launch_bounds__(TR_THREADS) TR_KERNEL_NAME(BriskGeom G, uint8_
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       const int centre = BRISK_SM_D(wl[4 * TR_WIN + 4]);
       // lanes 0-7: the 8 probe values, lanes 32-56: the 5x5 raw block (vals[8..32])
-      const int slot = (lane < 8) ? lane : (lane >= 32 && lane < 57) ? lane - 24 : -1;
+      int slot_v = (lane < 8) ? lane : (lane >= 32 && lane < 57) ? lane - 24 : -1;
+#if TR_KERNEL_LIST
+      // (opaque to the compiler: what the static step derives from the slot - the pixel's offsets in the window and in the
+      // block, for either form - is worked out per tie instead of living in registers across all loops of the kernel:
+      // 104 -> 90 VGPRs, the bound is 96)
+      asm volatile("" : "+v"(slot_v));
+#endif
+      const int slot = slot_v;
       // raster-earlier ties of the window (entries 0..39 of the 81) that were pending: where their decisions will appear
       int lo = -1;
       {
@@ -733,7 +740,17 @@ __global__ void __launch_bounds__(TR_THREADS) TR_KERNEL_NAME(BriskGeom G, uint8_
       TR_T(3)
       // everything of the cache replay that does not depend on those decisions, before waiting for them
       unsigned spk = BRISK_SS_FINAL, sdyn = 0;
-      if (slot >= 0) {
+#if TR_KERNEL_LIST
+      // the window's candidates that can act (entries 0 ... 40 with a score, the tie itself among them): a short list is
+      // walked entry by entry (brisk_state_static_list, all lanes: the entry's value is lane e's v0), a long one - all-tie
+      // images reach 41 - takes the unrolled loop over the pixel's 24 neighbours
+      const unsigned long long clist = __ballot(lane <= BRISK_TIE_WIN_SELF && BRISK_SM_D(v0) != 0);
+      const bool by_list = __builtin_popcountll(clist) <= BRISK_TIE_LIST_CAP;
+      if (by_list) spk = brisk_tie_slot_static_list(L, float_patch, touch2x2, cx, cy, slot, wl, kp5s[wave * TR_NW], clist, v0, &sdyn);
+#else
+      const bool by_list = false;
+#endif
+      if (slot >= 0 && !by_list) {
         if (masks) {
           int tsx, tsy;
           bool town;
