@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_prefill import settled
 from test_abi_epipolar import planted_depth
 from test_abi_epipolar_refit import SEAMS, degenerate_scenes, hand_views, restated_epipolar_refit, winner_of
 from test_abi_refit import PAIR_REFIT
@@ -276,7 +277,7 @@ def test_in_place_and_a_second_call_on_the_stream(B, ctx, seam_scene):
     r1, r2 = (1.5, 2, 8, 0, 1), (1.5, 1, 9, 1, 0)
     cap1, cap2 = int(big.offsets[-1]), 77
     want1 = expect(sc, sc, chain_frames(n), big, models, r1, cap1)
-    inplace = d_models.clone()                                       # [npairs + 1, 24] int32: a sentinel record behind the pairs'
+    inplace = settled(d_models.clone())                                 # [npairs + 1, 24] int32: a sentinel record behind the pairs'
     out = filled_outputs(n, cap1)
     rc, _ = raw_refit(B, ctx, sc, sc, spec, big, inplace.data_ptr(), r1, cap1, out=out, out_models_ptr=inplace.data_ptr())
     assert rc == 0

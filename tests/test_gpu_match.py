@@ -3,6 +3,7 @@
 import numpy as np
 import pytest
 
+from gpu_prefill import settled
 import oracle_lib as O
 from test_oracle_golden import homography_outliers
 
@@ -138,8 +139,7 @@ def test_device_resident_knn(B):
     q = rng.integers(0, 256, (500, 48), dtype=np.uint8)
     t = rng.integers(0, 256, (700, 64), dtype=np.uint8)   # rows at pitch 64, 48 bytes used
     dq, dt = torch.from_numpy(q).cuda(), torch.from_numpy(t).cuda()
-    out = torch.zeros((500, 2, 4), dtype=torch.int32, device="cuda")
-    cnt = torch.zeros(500, dtype=torch.int32, device="cuda")
+    out, cnt = settled(torch.zeros((500, 2, 4), dtype=torch.int32, device="cuda"), torch.zeros(500, dtype=torch.int32, device="cuda"))
     ctx = B.default_context(0)
     stream = torch.cuda.current_stream().cuda_stream
     ctx.check(ctx._L.brisk_hip_match_knn_device(ctx._h, dq.data_ptr(), 500, 48, dt.data_ptr(), 700, 64, 48, 2,
@@ -171,8 +171,7 @@ def test_pipeline_in_hbm_detect_describe_match(B, golden_ast):
     torch.cuda.synchronize()
     k0, d0 = ctx.batch_download(0, True)
     k1, d1 = ctx.batch_download(1, True)
-    out = torch.zeros((len(k0), 1, 4), dtype=torch.int32, device="cuda")
-    cnt = torch.zeros(len(k0), dtype=torch.int32, device="cuda")
+    out, cnt = settled(torch.zeros((len(k0), 1, 4), dtype=torch.int32, device="cuda"), torch.zeros(len(k0), dtype=torch.int32, device="cuda"))
     ctx.check(ctx._L.brisk_hip_match_knn_device(ctx._h, d_desc.value, len(k0), pitch.value,
                                                 d_desc.value + cap.value * pitch.value, len(k1), pitch.value, 48, 1,
                                                 out.data_ptr(), cnt.data_ptr(), stream))

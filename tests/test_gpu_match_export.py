@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_prefill import settled
 from test_abi_match_export import restated_row
 from test_gpu_match_gated import GRID_GATE, SynthKp
 from test_gpu_match_pairs import CAP, COUNTS_A, COUNTS_B, SENTINEL, SynthSet, batch_frames, run_pairs
@@ -188,8 +189,9 @@ def raw_select(ctx, triple, per_row, sel, matches_cap, outs, npairs=None, rows_c
 
 def sentinel_select_outputs(npairs, matches):
     import torch
-    return (torch.full((matches, 4), SENTINEL, dtype=torch.int32, device="cuda"), torch.full((npairs,), SENTINEL, dtype=torch.int32, device="cuda"),
-            torch.full((npairs,), SENTINEL, dtype=torch.int32, device="cuda"), torch.full((npairs + 1,), SENTINEL, dtype=torch.int64, device="cuda"))
+    return settled(torch.full((matches, 4), SENTINEL, dtype=torch.int32, device="cuda"), torch.full((npairs,), SENTINEL, dtype=torch.int32, device="cuda"),
+                   torch.full((npairs,), SENTINEL, dtype=torch.int32, device="cuda"),
+                   torch.full((npairs + 1,), SENTINEL, dtype=torch.int64, device="cuda"))
 
 
 @pytest.mark.parametrize("short", ["one", "all", "middle"])

@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_prefill import settled
 import oracle_lib as O
 from test_gpu_match_pairs import CAP, COUNTS_A, COUNTS_B, SENTINEL, SynthSet, batch_frames, pair_list, same_rows
 from test_oracle_golden import H_1TO2, homography_outliers
@@ -325,9 +326,9 @@ def test_caller_sets_and_pair_forms(B, dim, pitch, base_off, slack):
 
 def sentinel_outputs(npairs, rows_cap, k):
     import torch
-    return (torch.full((npairs, rows_cap, k, 4), SENTINEL, dtype=torch.int32, device="cuda"),
-            torch.full((npairs, rows_cap), SENTINEL, dtype=torch.int32, device="cuda"),
-            torch.full((npairs,), SENTINEL, dtype=torch.int32, device="cuda"))
+    return settled(torch.full((npairs, rows_cap, k, 4), SENTINEL, dtype=torch.int32, device="cuda"),
+                   torch.full((npairs, rows_cap), SENTINEL, dtype=torch.int32, device="cuda"),
+                   torch.full((npairs,), SENTINEL, dtype=torch.int32, device="cuda"))
 
 
 @pytest.mark.parametrize("mode", ["k1", "k2", "cross", "radius"])
@@ -454,6 +455,7 @@ def test_a_gate_that_allows_nothing_and_one_that_allows_one_pair(B):
     rec = B.KEYPOINT.itemsize
     for K, f, r in ((Ak, 5, q0), (Bk, 1, t0)):
         K.t_buf[f * K.set.frame_pitch + r * rec:f * K.set.frame_pitch + (r + 1) * rec] = torch.from_numpy(K.kps[f][r:r + 1].view(np.uint8).copy()).cuda()
+    settled()                                                        # the two records are in place before a call reads them
     one = (1000.0, 1000.0, -INF, INF, -1)
     M = gate_mask(one, Ak.kps[5], Bk.kps[1])
     assert M.sum() == 1 and M[q0, t0] == 1

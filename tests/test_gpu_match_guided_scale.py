@@ -16,6 +16,7 @@ import itertools
 import numpy as np
 import pytest
 
+from gpu_prefill import settled
 import ethzasl_brisk_amd as B
 import oracle_lib as O
 from test_abi_match_epiline import RECTIFIED, cross, scaled
@@ -723,6 +724,7 @@ def test_a_count_the_keys_do_not_hold(lib, form):
     d_kps = torch.zeros(total * rec, dtype=torch.uint8, device="cuda")
     d_desc[:rows.size] = torch.from_numpy(rows.reshape(-1)).cuda()
     d_kps[:kps.nbytes] = torch.from_numpy(kps.view(np.uint8).copy()).cuda()
+    settled(d_desc, d_kps)
     d_cnt = torch.tensor([CLAIM_ROWS, 1 << IDX_BITS, CLAIM_ROWS], dtype=torch.int32).cuda()
     S = B.DescSet(d_desc.data_ptr(), d_cnt.data_ptr(), 1, CLAIM_ROWS * 16, 16, 3)
     K = B.KpSet(d_kps.data_ptr(), CLAIM_ROWS * rec)

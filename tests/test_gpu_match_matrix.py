@@ -19,6 +19,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_prefill import settled
 import match_plain as P
 import oracle_lib as O
 
@@ -160,8 +161,8 @@ class DevCall:
         ht[t_offset:].reshape(-1, self.t_pitch)[:self.nt, :self.dim] = t
         self.dq, self.dt_all = torch.from_numpy(hq).cuda(), torch.from_numpy(ht).cuda()
         self.t_ptr = self.dt_all.data_ptr() + t_offset
-        self.out = torch.full((self.nq + PAD, max(k_or_cap, 1), 4), SENTINEL, dtype=torch.int32, device="cuda")
-        self.cnt = torch.full((self.nq + PAD,), SENTINEL, dtype=torch.int32, device="cuda")
+        self.out, self.cnt = settled(torch.full((self.nq + PAD, max(k_or_cap, 1), 4), SENTINEL, dtype=torch.int32, device="cuda"),
+                                     torch.full((self.nq + PAD,), SENTINEL, dtype=torch.int32, device="cuda"))
 
     def knn(self, ctx, stream=0):
         ctx.check(ctx._L.brisk_hip_match_knn_device(ctx._h, self.dq.data_ptr(), self.nq, self.q_pitch, self.t_ptr, self.nt, self.t_pitch,

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_prefill import settled
 import oracle_lib as O
 from test_oracle_golden import homography_outliers
 
@@ -235,9 +236,9 @@ def test_cross_check_with_heavy_ties(B):
 
 def sentinel_outputs(npairs, rows_cap, k):
     import torch
-    return (torch.full((npairs, rows_cap, k, 4), SENTINEL, dtype=torch.int32, device="cuda"),
-            torch.full((npairs, rows_cap), SENTINEL, dtype=torch.int32, device="cuda"),
-            torch.full((npairs,), SENTINEL, dtype=torch.int32, device="cuda"))
+    return settled(torch.full((npairs, rows_cap, k, 4), SENTINEL, dtype=torch.int32, device="cuda"),
+                   torch.full((npairs, rows_cap), SENTINEL, dtype=torch.int32, device="cuda"),
+                   torch.full((npairs,), SENTINEL, dtype=torch.int32, device="cuda"))
 
 
 @pytest.mark.parametrize("k,cross", [(1, False), (2, False), (1, True)])

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from gpu_prefill import settled
 import oracle_lib as O
 from test_gpu_match_pairs import CAP, COUNTS_A, COUNTS_B, SENTINEL, SynthSet, batch_frames, pair_list, same_rows
 from test_oracle_golden import homography_outliers
@@ -185,9 +186,9 @@ def test_caller_sets_and_pair_forms(B, dim, pitch, base_off, slack):
 
 def sentinel_outputs(npairs, rows_cap, cap):
     import torch
-    return (torch.full((npairs, rows_cap, cap, 4), SENTINEL, dtype=torch.int32, device="cuda"),
-            torch.full((npairs, rows_cap), SENTINEL, dtype=torch.int32, device="cuda"),
-            torch.full((npairs,), SENTINEL, dtype=torch.int32, device="cuda"))
+    return settled(torch.full((npairs, rows_cap, cap, 4), SENTINEL, dtype=torch.int32, device="cuda"),
+                   torch.full((npairs, rows_cap), SENTINEL, dtype=torch.int32, device="cuda"),
+                   torch.full((npairs,), SENTINEL, dtype=torch.int32, device="cuda"))
 
 
 @pytest.mark.parametrize("max_distance,cap", [(0.5, 4), (4 * 48 + 0.5, 8), (1e9, 40), (1e9, 140)])
@@ -307,9 +308,8 @@ def test_single_set_device_form(B, dim, pitch):
             t[2] = q[1]                                             # a planted identical row
         dq, dt = torch.from_numpy(qb).cuda(), torch.from_numpy(tb).cuda()
         for r in (0.5, 4 * dim + 0.5, float(4 * dim), 1e9):
-            m = torch.full((nq, cpq, 4), SENTINEL, dtype=torch.int32, device="cuda")
-            c = torch.full((nq,), SENTINEL, dtype=torch.int32, device="cuda")
-            torch.cuda.synchronize()
+            m, c = settled(torch.full((nq, cpq, 4), SENTINEL, dtype=torch.int32, device="cuda"),
+                           torch.full((nq,), SENTINEL, dtype=torch.int32, device="cuda"))
             ctx.match_radius_device(dq.data_ptr(), nq, pitch, dt.data_ptr() if nt else None, nt, pitch, dim, r, cpq, m.data_ptr(),
                                     c.data_ptr())
             torch.cuda.synchronize()

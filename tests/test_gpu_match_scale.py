@@ -13,6 +13,7 @@ import types
 import numpy as np
 import pytest
 
+from gpu_prefill import settled
 import oracle_lib as O
 import test_gpu_match_gated as G
 import test_gpu_match_radius_pairs as R
@@ -669,6 +670,7 @@ def edge_kps(B, rng, q_n, t_n, moved):
     Tk.kps[0]["x"][moved] = 100.0
     for K in (Qk, Tk):                                               # (the calls synchronise before they start)
         K.t_buf[:K.kps[0].nbytes] = torch.from_numpy(K.kps[0].view(np.uint8).copy()).cuda()
+    settled()
     return Qk, Tk
 
 

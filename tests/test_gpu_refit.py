@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_prefill import settled
 from test_abi_refit import IDENTITY, PAIR_REFIT, REJECTED, grid_rms, refit_of, restated_refit, seeded_scene
 from test_abi_tracks import SENT32, restated_link
 from test_abi_verify import PAIR_BAD, PAIR_NO_MODEL, ROWS_CUT, restated_verify
@@ -287,7 +288,7 @@ def test_in_place_and_a_second_call_on_the_stream(B, ctx, seam_scene):
     r1, r2 = (2.0, 2, 4, 0), (2.0, 1, 5, 1)
     cap1, cap2 = int(big.offsets[-1]), 77
     want1 = expect(sc, sc, chain_frames(n), big, models, r1, cap1)
-    inplace = d_models.clone()                                       # [npairs + 1, 24] int32: a sentinel record behind the pairs'
+    inplace = settled(d_models.clone())                                 # [npairs + 1, 24] int32: a sentinel record behind the pairs'
     out = sentinel_outputs(n, cap1)
     rc, _ = raw_refit(B, ctx, sc, sc, spec, big, inplace.data_ptr(), r1, cap1, out=out, out_models_ptr=inplace.data_ptr())
     assert rc == 0

@@ -6,6 +6,7 @@ import socket
 import numpy as np
 import pytest
 
+from gpu_prefill import settled
 import oracle_lib as O
 import synth
 from test_gpu_parity import same_kps, explain  # noqa: F401
@@ -93,7 +94,7 @@ def test_config3_512_frames_with_result_gather_on_one_rank(B):
         nd = 8
         distinct = [synth.frame_1080p(700 + i) for i in range(nd)]
         ring = torch.from_numpy(np.stack(distinct)).to(dev)
-        frames = ring[torch.arange(n, device=dev) % nd].contiguous()
+        frames = settled(ring[torch.arange(n, device=dev) % nd].contiguous())   # (a gather on the null stream)
         ctx = B.Context(0)
         ext = B.BriskDescriptorExtractor(context=ctx)
         stream = torch.cuda.current_stream().cuda_stream

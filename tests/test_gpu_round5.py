@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_prefill import settled
 import oracle_lib as O
 import synth
 from test_gpu_parity import same_kps, explain  # noqa: F401
@@ -112,8 +113,7 @@ def test_batch_results_pitch_after_a_packed_host_describe(B):
     # the device rows against the host copy of the same descriptors (shifted by one row: no trivial zero distances)
     train = torch.from_numpy(np.roll(desc, 1, axis=0).copy()).cuda()
     nq = len(k2)
-    out = torch.zeros((nq, 2, 4), dtype=torch.int32, device="cuda")
-    cnt = torch.zeros(nq, dtype=torch.int32, device="cuda")
+    out, cnt = settled(torch.zeros((nq, 2, 4), dtype=torch.int32, device="cuda"), torch.zeros(nq, dtype=torch.int32, device="cuda"))
     stream = torch.cuda.current_stream().cuda_stream
     ctx.check(ctx._L.brisk_hip_match_knn_device(ctx._h, d_desc.value, nq, pitch.value, train.data_ptr(), nq, 48, 48, 2,
                                                 out.data_ptr(), cnt.data_ptr(), stream))

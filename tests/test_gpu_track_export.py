@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_prefill import settled
 from test_abi_track_export import restated_points
 from test_abi_tracks import SENT32, SENT64, restated_link, restated_list
 from test_gpu_match_pairs import SENTINEL, batch_frames
@@ -94,7 +95,7 @@ def raw_points(ctx, ch, lo, obs_cap, kps, kp_first, kp_step, points=None):
     """the device form on what raw_list returned; the points pre-filled"""
     import torch
     if points is None:
-        points = torch.full((obs_cap + SLACK, 9), SENTINEL, dtype=torch.int32, device="cuda")
+        points = settled(torch.full((obs_cap + SLACK, 9), SENTINEL, dtype=torch.int32, device="cuda"))
     rc = ctx._L.brisk_hip_track_points_device(ctx._h, ch.d_rows.data_ptr(), ch.stride, ch.nodes, ch.rows_cap, lo[2].data_ptr(), lo[3].data_ptr(),
                                               lo[4].data_ptr(), int(obs_cap), C.byref(kps), kp_first, kp_step, points.data_ptr(), None)
     return rc, points
@@ -287,6 +288,7 @@ def test_keypoints_beyond_four_gib(B, ctx):
         lim = min(n, cap)
         rows[i] = ((np.arange(lim * 7, dtype=np.uint32) + 1) * np.uint32(2654435761)) ^ np.uint32(0x01010101 * (i + 1))
         big[i * pitch:i * pitch + lim * 28] = torch.from_numpy(rows[i].view(np.uint8).copy()).cuda()
+    settled(big)                                                            # the rows are in place before a call reads them
 
     def kp_words(first, n):
         i, at = divmod(first * 4, pitch)
@@ -453,7 +455,7 @@ def test_arguments(B, ctx):
     # the device form
     rc, lo = raw_list(B, ctx, ch, out, 2, 50, 200)
     assert rc == 0
-    pts = torch.full((200 + SLACK, 9), SENTINEL, dtype=torch.int32, device="cuda")
+    pts = settled(torch.full((200 + SLACK, 9), SENTINEL, dtype=torch.int32, device="cuda"))
     gdev = [ch.d_rows.data_ptr(), 1, 3, CAP, lo[2].data_ptr(), lo[3].data_ptr(), lo[4].data_ptr(), 200, kset(), 1, 2, pts.data_ptr(), None]
     bad = [(2, 0), (3, 0), (1, 0), (0, None), (0, gdev[0] + 2), (4, None), (5, None), (6, None), (7, -1), (11, None),
            (4, gdev[4] + 4), (5, gdev[5] + 4), (6, gdev[6] + 4), (11, gdev[11] + 2),

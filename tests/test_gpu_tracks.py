@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_prefill import settled
 from test_abi_tracks import SENT32, SENT64, restated_link, restated_list
 from test_gpu_match_pairs import SENTINEL, batch_frames
 
@@ -87,7 +88,7 @@ class Chain:
         self.d_offsets = torch.from_numpy(offsets).cuda()
         self.d_matches = torch.from_numpy(np.ascontiguousarray(matches).view(np.int32).reshape(-1, 4).copy()).cuda()
         if len(matches) == 0:
-            self.d_matches = torch.zeros((1, 4), dtype=torch.int32, device="cuda")
+            self.d_matches = settled(torch.zeros((1, 4), dtype=torch.int32, device="cuda"))
 
     def sub(self, B, a, b):
         """nodes [a, b) as a chain of their own (the same records: the offsets are absolute)"""
@@ -96,10 +97,10 @@ class Chain:
 
 def sentinel_link_outputs(nodes, rows_cap):
     import torch
-    return (torch.full((nodes, rows_cap), SENTINEL, dtype=torch.int32, device="cuda"),
-            torch.full((nodes, rows_cap), int(SENT64), dtype=torch.int64, device="cuda"),
-            torch.full((nodes, rows_cap), SENTINEL, dtype=torch.int32, device="cuda"),
-            torch.full((8,), int(SENT64), dtype=torch.int64, device="cuda"))
+    return settled(torch.full((nodes, rows_cap), SENTINEL, dtype=torch.int32, device="cuda"),
+                   torch.full((nodes, rows_cap), int(SENT64), dtype=torch.int64, device="cuda"),
+                   torch.full((nodes, rows_cap), SENTINEL, dtype=torch.int32, device="cuda"),
+                   torch.full((8,), int(SENT64), dtype=torch.int64, device="cuda"))
 
 
 def raw_link(B, ctx, ch, seed=None, out=None):
@@ -139,11 +140,11 @@ def seed_arrays(rng, rows_cap):
 
 def sentinel_list_outputs(tracks_cap, obs_cap, slack=16):
     import torch
-    return (torch.full((tracks_cap + slack,), int(SENT64), dtype=torch.int64, device="cuda"),
-            torch.full((tracks_cap + slack,), SENTINEL, dtype=torch.int32, device="cuda"),
-            torch.full((tracks_cap + 1 + slack,), int(SENT64), dtype=torch.int64, device="cuda"),
-            torch.full((obs_cap + slack, 2), SENTINEL, dtype=torch.int32, device="cuda"),
-            torch.full((4,), int(SENT64), dtype=torch.int64, device="cuda"))
+    return settled(torch.full((tracks_cap + slack,), int(SENT64), dtype=torch.int64, device="cuda"),
+                   torch.full((tracks_cap + slack,), SENTINEL, dtype=torch.int32, device="cuda"),
+                   torch.full((tracks_cap + 1 + slack,), int(SENT64), dtype=torch.int64, device="cuda"),
+                   torch.full((obs_cap + slack, 2), SENTINEL, dtype=torch.int32, device="cuda"),
+                   torch.full((4,), int(SENT64), dtype=torch.int64, device="cuda"))
 
 
 def raw_list(B, ctx, ch, link_out, min_len, tracks_cap, obs_cap, out=None):
@@ -275,6 +276,7 @@ def test_first_new_from_the_call_s_own_summary(B, ctx, chain65):
     st, sa = torch.from_numpy(chain65["st"]).cuda(), torch.from_numpy(chain65["sa"]).cuda()
     out = sentinel_link_outputs(ch.nodes, ch.rows_cap)
     out[3][0] = 2 ** 40
+    settled()                                                           # (a fill on the null stream, like the sentinel's)
     rc, out = raw_link(B, ctx, ch, (st, sa, 0, out[3]), out=out)
     assert rc == 0
     same_link(host(out), chain65["want"])
@@ -429,8 +431,7 @@ def test_arguments(B, ctx):
     L, h = ctx._L, ctx._h
     good = [ch.d_rows.data_ptr(), 1, 3, CAP, ch.d_offsets.data_ptr(), ch.d_matches.data_ptr(), None, out[0].data_ptr(), out[1].data_ptr(),
             out[2].data_ptr(), out[3].data_ptr(), None]
-    st = torch.zeros(CAP + 1, dtype=torch.int64, device="cuda")
-    sa = torch.zeros(CAP + 1, dtype=torch.int32, device="cuda")
+    st, sa = settled(torch.zeros(CAP + 1, dtype=torch.int64, device="cuda"), torch.zeros(CAP + 1, dtype=torch.int32, device="cuda"))
 
     def seed(t, a, w=None):
         return C.byref(B.TrackSeed(t, a, 0, w))

@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_prefill import settled
 from test_abi_tracks import SENT32, restated_link, restated_list
 from test_abi_verify import PAIR_BAD, PAIR_NO_MODEL, ROWS_CUT, restated_pair, restated_verify
 from test_gpu_match_pairs import SENTINEL, batch_frames
@@ -120,10 +121,10 @@ class Lists:
 
 def sentinel_outputs(npairs, out_cap):
     import torch
-    return (torch.full((max(out_cap, 0) + PAD, 4), SENTINEL, dtype=torch.int32, device="cuda"),
-            torch.full((npairs,), SENTINEL, dtype=torch.int32, device="cuda"), torch.full((npairs,), SENTINEL, dtype=torch.int32, device="cuda"),
-            torch.full((npairs + 2,), int(np.int64(0x5A5A5A5A5A5A5A5A)), dtype=torch.int64, device="cuda"),
-            torch.full((npairs + 1, 24), SENTINEL, dtype=torch.int32, device="cuda"))
+    return settled(torch.full((max(out_cap, 0) + PAD, 4), SENTINEL, dtype=torch.int32, device="cuda"),
+                   torch.full((npairs,), SENTINEL, dtype=torch.int32, device="cuda"), torch.full((npairs,), SENTINEL, dtype=torch.int32, device="cuda"),
+                   torch.full((npairs + 2,), int(np.int64(0x5A5A5A5A5A5A5A5A)), dtype=torch.int64, device="cuda"),
+                   torch.full((npairs + 1, 24), SENTINEL, dtype=torch.int32, device="cuda"))
 
 
 def raw_verify(B, ctx, qs, ts, spec, lists, verify, out_cap, out=None, stream=None, in_cap=None):
